@@ -8,14 +8,17 @@ gathered through the communicator: proof of how many ranks really ran.
 
 One "step" = the full iteration of train.py:221-272 on a resident synthetic batch: student fwd
 (2 views), teacher fwd, seg + DINO loss, centre update, backward, per-tensor clip, AdamW, teacher EMA.  bf16 MFMA
-operands, fp32 accumulation / master weights.  Prints ONE JSON line on rank 0 (contract in the task statement) with
-the extra `roofline` (dominant kernel, timed live with HIP events) and `cpu_baseline` (the CPU oracle on this host).
+operands, fp32 accumulation / master weights.  Prints ONE JSON line on rank 0 (contract in the task statement).
+A plain run only sets up, warms up, times the steps and prints the line; `--full` adds the `roofline` (dominant kernel,
+timed live with HIP events) and `cpu_baseline` (the CPU oracle on this host) legs.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32; a fixed sample of the larger ones).
 """
 import argparse
 import json
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -109,6 +112,24 @@ def kernel_sources_digest():
     return h.hexdigest()
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of a larger output: the same seeded positions in every run
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float32) per array the timed path handed back in its last step.  A tensor of more
+    than DUMP_SAMPLE elements is reduced to a fixed sample of its flat positions (seeded by its name), so that two builds can
+    be compared output for output; every file stays below 4 MiB."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            flat = t.reshape(-1)
+            pos = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            t = flat[torch.from_numpy(pos).to(flat.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.float().cpu().numpy())
+
+
 def emit(line):
     """Print the result as the LAST line of stdout: librccl logs its path through C stdio, which is block-buffered on a
     pipe and would otherwise be flushed after Python's output at exit."""
@@ -160,13 +181,13 @@ def main_finetune(a, world, rank, dev, use_dist):
     labels = model.label_convertor.str2tensor(words).to(dev)
 
     def step():
-        return ft.training_iteration(net, opt, images, labels, 1e-4)[0]
+        return ft.training_iteration(net, opt, images, labels, 1e-4)
 
     warm_summary = None                       # see main(): every launch timed in the last warm-up step, then one kind only
     for i in range(a.warmup):
         if not a.no_kernel_timer and i == a.warmup - 1:
             ops.TIMER = ops.KernelTimer()
-        loss = step()
+        loss, attn = step()
     if ops.TIMER is not None:
         torch.cuda.synchronize()
         warm_summary = ops.TIMER.summary()
@@ -178,7 +199,7 @@ def main_finetune(a, world, rank, dev, use_dist):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss = step()
+        loss, attn = step()
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
@@ -190,6 +211,8 @@ def main_finetune(a, world, rank, dev, use_dist):
     elapsed = t.item()
     final_loss = loss.item()
     assert final_loss == final_loss and abs(final_loss) < 1e4, f"non-finite loss {final_loss}"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"loss": loss.reshape(1), "attn": attn})      # what the step hands back (see main())
     census = rank_census(world, rank, dev, 25 * B)
     if rank == 0:
         ms = elapsed / a.steps * 1e3
@@ -271,6 +294,8 @@ def main_recognize(a, world, rank, dev, use_dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = t.item()
     assert tuple(probs.shape) == (B, 25, 92) and bool(torch.isfinite(probs).all())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"probs": probs})
     census = rank_census(world, rank, dev, 25 * B)
     if rank == 0:
         line = {"metric": "images/sec (32x128 crops) CCD text recognition, greedy decoding (25 steps)",
@@ -354,11 +379,16 @@ def main():
                     "branch (dino_vision.py:64-70; the batch then carries its characters in the images)")
     ap.add_argument("--graph", action="store_true", help="pretrain, 1 GPU: replay the step as ONE HIP graph "
                     "(pretrain.GraphedTrainingStep) - the small-batch regime, where the host's launches bound the step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the legs beyond the headline figure: the per-kind kernel table and "
+                    "`roofline` (HIP events in the last warm-up step and around the dominant kind) and the CPU oracle's `cpu_baseline`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="--full without the roofline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     a = ap.parse_args()
-    if os.environ.get("BENCH_NOTIMER") == "1":
+    if os.environ.get("BENCH_NOTIMER") == "1" or not a.full:
         a.no_kernel_timer = True
+    if not a.full:
+        a.no_cpu_baseline = True
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(a.gpus)               # `python bench.py --gpus N`: become the launcher of N ranks of this command
@@ -460,6 +490,16 @@ def main():
     elapsed = t.item()
     final_loss = loss.item()
     assert final_loss == final_loss and abs(final_loss) < 1e4, f"non-finite loss {final_loss}"
+    if a.dump_outputs and rank == 0:
+        # what the step hands back - the loss and its two terms - and the state it leaves that is fixed by the inputs up to rounding:
+        # the teacher's weights after the EMA and the DINO centre.  Not the student's gradients and weights: the fp32 atomic sums
+        # of a step add rounding noise to the gradients, and AdamW's early steps scale each element's gradient to about +-1, so an
+        # element whose exact gradient is zero (a convolution bias in front of a BatchNorm) moves by +-lr on the sign of that noise;
+        # over the warm-up and timed steps the student drifts from run to run by far more than rounding
+        outs = {"loss": loss.reshape(1)}
+        outs.update({"loss_" + k: v.reshape(1) for k, v in dino_loss.last_losses.items() if torch.is_tensor(v)})
+        outs.update({"teacher_weights": teacher.arena.flat, "center": dino_loss.center})
+        dump_outputs(a.dump_outputs, outs)
 
     # every rank: its selected-row count M (ranks hold different batches, so M differs), gathered through the collective library
     from ccd_amd import engine

@@ -56,6 +56,58 @@ def test_bench_refuses_more_gpus_than_present():
     assert r.returncode != 0 and "exposes" in r.stderr
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path):
+    """--dump-outputs: float32 files, a larger output reduced to the same positions in every run (two builds compare file by file)."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    big = torch.arange(bench.DUMP_SAMPLE + 5, dtype=torch.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": torch.ones(2, 3, dtype=torch.bfloat16)})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE,) and np.array_equal(a, b)
+    assert len(np.unique(a)) == bench.DUMP_SAMPLE and (np.diff(a) > 0).all()      # distinct positions, in order
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (2, 3) and (s == 1).all()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dump(tmp_path):
+    """A plain run prints the headline line without the --full legs, and --dump-outputs writes the last step's outputs."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BENCH_BACKEND", "BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    runs = []
+    for tag in ("a", "b"):     # the same arguments twice: the same inputs, the same outputs up to rounding
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--batch", "32", "--dump-outputs", str(out / tag)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in line, k
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and "roofline" not in line and "cpu_baseline" not in line
+        files = {f: np.load(out / tag / f) for f in os.listdir(out / tag)}
+        assert {"loss.npy", "loss_mask_loss.npy", "loss_Dino_loss.npy", "teacher_weights.npy", "center.npy"} == set(files)
+        assert sum(os.path.getsize(out / tag / f) for f in files) <= 64 << 20
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+        assert abs(float(files["loss.npy"][0]) - line["config"]["final_loss"]) < 1e-3
+        runs.append(files)
+    for f, a in runs[0].items():
+        b = runs[1][f].astype(np.float64)
+        rel = np.linalg.norm(b - a) / max(np.linalg.norm(a.astype(np.float64)), 1e-30)
+        assert rel < 1e-3, (f, rel)
+
+
 def test_bench_functions_use_only_names_they_can_see():
     """bench.py's finetune / recognize paths only run on a GPU box: a name that exists in one `main_*` function and was pasted into
     another (it happened: `graphed` in main_finetune) must fail HERE.  Every name a function loads is a local, an enclosing or

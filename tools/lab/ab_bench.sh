@@ -15,7 +15,7 @@ for r in $(seq 1 $rounds); do
     name=${v%%:*}; envs=""
     [ "$v" != "$name" ] && envs=${v#*:}
     out=gpurun_out/${tag}_${name}_$r
-    env $(echo "$envs" | tr ',' ' ') python bench.py --no-cpu-baseline "$@" 2> $out.err | tail -1 > $out.json
+    env $(echo "$envs" | tr ',' ' ') python bench.py --full --no-cpu-baseline "$@" 2> $out.err | tail -1 > $out.json
     python - $out.json <<'PY'
 import json, sys
 try:
