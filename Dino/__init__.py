@@ -1,6 +1,7 @@
 """`Dino.*` import paths of the reference (TongkunGuan/CCD) mapped onto the MI355X-native implementation in
 `ccd_amd`, so `from Dino.modules import vision_transformer as vits`, `from Dino.model.dino_vision import
-ABIDINOModel`, `from Dino.loss.Dino_loss import DINOLoss`, `from Dino.utils.utils import Config` keep working.
+ABIDINOModel`, `from Dino.loss.Dino_loss import DINOLoss`, `from Dino.utils.utils import Config`,
+`from Dino.utils.DBSCAN import label_cluster` keep working.
 The pretraining path and the finetune path (8f row 1: DINO_Finetune, NRTRDecoder, TFLoss,
 AttnConvertor) exist here."""
 import importlib
@@ -27,6 +28,7 @@ _ALIASES = {
     "Dino.dataset.datasetsupervised_kmeans": "ccd_amd.dataset.datasetsupervised_kmeans",
     "Dino.utils": "ccd_amd.utils",
     "Dino.utils.utils": "ccd_amd.utils.utils",
+    "Dino.utils.DBSCAN": "ccd_amd.utils.DBSCAN",
 }
 for _alias, _target in _ALIASES.items():
     _mod = importlib.import_module(_target)

@@ -70,6 +70,10 @@ SIGNATURES = {
     "ccd_region_pool_bwd": [P, P, P, P, P, P, P, I, I, P],
     "ccd_idmap_to_planes": [P, P, I, P],
     "ccd_planes_to_idmap": [P, P, I, P],
+    "ccd_dbscan_label": [P, P, I, P],
+    "ccd_region_boxes": [P, P, P, I, P],
+    "ccd_idmap_to_planes_u8": [P, P, I, P],
+    "ccd_boxes_to_planes_u8": [P, P, P, I, P],
     "ccd_l2norm_fwd": [P, P, P, I, P, I, I, P],
     "ccd_l2norm_bwd": [P, P, P, P, I, P, I, I, P],
     "ccd_weightnorm_fwd": [P, P, P, P, P, I, I, P],

@@ -18,6 +18,7 @@
 #include "kernels/gemm_tn384.h"
 #include "kernels/layernorm.h"
 #include "kernels/charmap.h"
+#include "kernels/cluster.h"
 #include "kernels/datapipe.h"
 #include "kernels/embed.h"
 #include "kernels/head.h"
@@ -276,8 +277,8 @@ static int ccd_launch_tn384_geom(ccd::GemmParams& p, int Mc, float* ws, long ws_
 
 extern "C" {
 
-int ccd_abi_version(void) { return 12; }   // 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
-const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi12"; }
+int ccd_abi_version(void) { return 13; }   // 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
+const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi13"; }
 int ccd_policy_set(const char* key, int value) {
     CCD_CHECK(key, CCD_EINVAL);
     for (const CcdPolicyKey& k : ccd_policy_keys)
@@ -1014,6 +1015,39 @@ int ccd_planes_to_idmap(const float* planes, uint8_t* idmap, int images, void* s
     const long n = (long)images * ccd::CM_PIX;
     CCD_LAUNCH(ccd::planes_to_idmap_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, planes, idmap,
                (long)images);
+    return ccd_rt_last_error();
+}
+
+// ------------------------------------------------------------------------------- Dino/utils/DBSCAN.py clusterers
+int ccd_dbscan_label(const float* mask, uint8_t* idmap, int images, void* stream) {
+    CCD_CHECK(images >= 0, CCD_EINVAL);
+    if (images == 0) return CCD_OK;                 // (an empty tensor may carry a null pointer)
+    CCD_CHECK(mask && idmap, CCD_EINVAL);
+    CCD_LAUNCH(ccd::dbscan_label_kernel, dim3(images), dim3(256), 0, stream, mask, idmap, images);
+    return ccd_rt_last_error();
+}
+int ccd_region_boxes(const float* mask, int* boxes, int* count, int images, void* stream) {
+    CCD_CHECK(images >= 0, CCD_EINVAL);
+    if (images == 0) return CCD_OK;
+    CCD_CHECK(mask && boxes && count, CCD_EINVAL);
+    CCD_LAUNCH(ccd::region_boxes_kernel, dim3(images), dim3(256), 0, stream, mask, boxes, count, images);
+    return ccd_rt_last_error();
+}
+int ccd_idmap_to_planes_u8(const uint8_t* idmap, uint8_t* planes, int images, void* stream) {
+    CCD_CHECK(images >= 0, CCD_EINVAL);
+    if (images == 0) return CCD_OK;
+    CCD_CHECK(idmap && planes && CCD_ALIGNED16(idmap) && CCD_ALIGNED16(planes), CCD_EINVAL);
+    CCD_CHECK((long)images * ccd::CM_PLANES <= 0x7fffffffL, CCD_ESHAPE);
+    CCD_LAUNCH(ccd::idmap_to_planes_u8_kernel, dim3((unsigned)(images * ccd::CM_PLANES)), dim3(256), 0, stream, idmap, planes);
+    return ccd_rt_last_error();
+}
+int ccd_boxes_to_planes_u8(const int* boxes, const int* count, uint8_t* planes, int images, void* stream) {
+    CCD_CHECK(images >= 0, CCD_EINVAL);
+    if (images == 0) return CCD_OK;
+    CCD_CHECK(boxes && count && planes && CCD_ALIGNED16(planes), CCD_EINVAL);
+    CCD_CHECK((long)images * ccd::CM_PLANES <= 0x7fffffffL, CCD_ESHAPE);
+    CCD_LAUNCH(ccd::boxes_to_planes_u8_kernel, dim3((unsigned)(images * ccd::CM_PLANES)), dim3(256), 0, stream, boxes, count,
+               planes);
     return ccd_rt_last_error();
 }
 

@@ -17,6 +17,50 @@ namespace ccd {
 constexpr int CM_H = 32, CM_W = 128, CM_PIX = CM_H * CM_W, CM_PLANES = 26, CM_MIN_AREA = 30;
 constexpr unsigned char CM_BG = 255;
 
+// ---- 8-connected components of the pixels with label[i] >= 0 (label[i] = i on entry, -1 = not a pixel of the set) --------
+// On return every member pixel holds its component's root: the raster index of the component's first pixel (== skimage /
+// scipy numbering order).  Hook (min over the 8 neighbours onto the current root) + full path compression, to a fixed point.
+// Called by all 256 threads of the workgroup; `changed` is a __shared__ int.
+__device__ __forceinline__ void cm_components(int* label, int* changed) {
+    const int t = threadIdx.x;
+    for (;;) {
+        if (t == 0) *changed = 0;
+        __syncthreads();
+        // hook: pull the smallest neighbouring label onto this pixel's current root
+        for (int i = t; i < CM_PIX; i += 256) {
+            const int li = label[i];
+            if (li < 0) continue;
+            const int y = i >> 7, x = i & 127;
+            int best = li;
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const int yy = y + dy, xx = x + dx;
+                    if (yy < 0 || yy >= CM_H || xx < 0 || xx >= CM_W) continue;
+                    const int ln = label[yy * CM_W + xx];
+                    if (ln >= 0 && ln < best) best = ln;
+                }
+            if (best < li) {
+                atomicMin(&label[li], best);
+                atomicMin(&label[i], best);
+                *changed = 1;
+            }
+        }
+        __syncthreads();
+        // compress: point every pixel at its current root
+        for (int i = t; i < CM_PIX; i += 256) {
+            int l = label[i];
+            if (l < 0) continue;
+            while (label[l] != l) l = label[l];
+            label[i] = l;
+        }
+        __syncthreads();
+        if (!*changed) break;
+        __syncthreads();
+    }
+}
+
 // ---- 8-connected component labelling of one 32x128 mask per workgroup (256 threads, 16 pixels each) --------
 // label = raster index of the component's first pixel (== skimage/scipy numbering order); components are kept
 // in that order while area >= 30, at most 26; planes are then ordered by mean column (exact rational compare,
@@ -39,42 +83,7 @@ __global__ __launch_bounds__(256) void ccl_label_kernel(const float* __restrict_
         colsum[i] = 0;
     }
     __syncthreads();
-    for (;;) {
-        if (t == 0) changed = 0;
-        __syncthreads();
-        // hook: pull the smallest neighbouring label onto this pixel's current root
-        for (int i = t; i < CM_PIX; i += 256) {
-            const int li = label[i];
-            if (li < 0) continue;
-            const int y = i >> 7, x = i & 127;
-            int best = li;
-#pragma unroll
-            for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-                for (int dx = -1; dx <= 1; ++dx) {
-                    const int yy = y + dy, xx = x + dx;
-                    if (yy < 0 || yy >= CM_H || xx < 0 || xx >= CM_W) continue;
-                    const int ln = label[yy * CM_W + xx];
-                    if (ln >= 0 && ln < best) best = ln;
-                }
-            if (best < li) {
-                atomicMin(&label[li], best);
-                atomicMin(&label[i], best);
-                changed = 1;
-            }
-        }
-        __syncthreads();
-        // compress: point every pixel at its current root
-        for (int i = t; i < CM_PIX; i += 256) {
-            int l = label[i];
-            if (l < 0) continue;
-            while (label[l] != l) l = label[l];
-            label[i] = l;
-        }
-        __syncthreads();
-        if (!changed) break;
-        __syncthreads();
-    }
+    cm_components(label, &changed);
     for (int i = t; i < CM_PIX; i += 256) {
         const int l = label[i];
         if (l >= 0) {

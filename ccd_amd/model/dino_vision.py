@@ -14,6 +14,12 @@ import torch.nn as nn
 
 from .. import engine, ops
 from ..modules.vision_transformer import ArenaModule
+from ..utils.DBSCAN import DBSCAN_cluster, label_cluster
+
+# the reference's module-level clusterers (dino_vision.py:18-19); constructing them does not touch the GPU.  ABIDINOModel itself
+# keeps its character regions on the device as id maps (ops.ccl_label) and does not go through these.
+dbscan = DBSCAN_cluster(eps=1.5, min_samples=4)
+label = label_cluster()
 
 
 class ClusterMaps:

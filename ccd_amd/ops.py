@@ -644,6 +644,44 @@ def planes_to_idmap(planes):
     return out
 
 
+# ------------------------------------------------------------------------------------------ Dino/utils/DBSCAN.py clusterers
+def dbscan_label(mask):
+    """DBSCAN_cluster: mask [B,32,128] fp32 (foreground = x > 0.1f) -> uint8 id map [B,32,128] (255 = none)."""
+    assert mask.dtype == F32 and mask.is_contiguous() and tuple(mask.shape[1:]) == (32, 128)
+    out = torch.empty(mask.shape, dtype=U8, device=mask.device)
+    _call("ccd_dbscan_label", _lib.ptr(mask), _lib.ptr(out), mask.shape[0])
+    return out
+
+
+def region_boxes(mask):
+    """region_cluster: mask [B,32,128] fp32 (nonzero = foreground) -> (boxes int32 [B,26,4] as ymin, xmin, ymax, xmax with
+    half-open stops, count int32 [B]); slots >= count are zero."""
+    assert mask.dtype == F32 and mask.is_contiguous() and tuple(mask.shape[1:]) == (32, 128)
+    boxes = torch.empty((mask.shape[0], 26, 4), dtype=I32, device=mask.device)
+    count = torch.empty((mask.shape[0],), dtype=I32, device=mask.device)
+    _call("ccd_region_boxes", _lib.ptr(mask), _lib.ptr(boxes), _lib.ptr(count), mask.shape[0])
+    return boxes, count
+
+
+def idmap_to_planes_u8(idmap):
+    """uint8 id map [B,32,128], 16-byte aligned (the kernel reads 16 pixels per load) -> the reference's uint8 planes
+    [B,26,32,128]."""
+    assert idmap.dtype == U8 and idmap.is_contiguous() and tuple(idmap.shape[1:]) == (32, 128)
+    assert idmap.data_ptr() % 16 == 0, "idmap_to_planes_u8: the id map must start on a 16-byte boundary (pass a fresh or cloned tensor)"
+    out = torch.empty((idmap.shape[0], 26, 32, 128), dtype=U8, device=idmap.device)
+    _call("ccd_idmap_to_planes_u8", _lib.ptr(idmap), _lib.ptr(out), idmap.shape[0])
+    return out
+
+
+def boxes_to_planes_u8(boxes, count):
+    """region_boxes' (boxes [B,26,4], count [B]) int32 -> the reference's uint8 planes [B,26,32,128] (filled boxes)."""
+    assert boxes.dtype == I32 and boxes.is_contiguous() and boxes.dim() == 3 and tuple(boxes.shape[1:]) == (26, 4)
+    assert count.dtype == I32 and count.is_contiguous() and tuple(count.shape) == (boxes.shape[0],)
+    out = torch.empty((boxes.shape[0], 26, 32, 128), dtype=U8, device=boxes.device)
+    _call("ccd_boxes_to_planes_u8", _lib.ptr(boxes), _lib.ptr(count), _lib.ptr(out), boxes.shape[0])
+    return out
+
+
 # ------------------------------------------------------------------------------------------ DINO head pieces
 def l2norm_fwd(x, y, inv, d_rows=None, rows_mul=1):
     _call("ccd_l2norm_fwd", _lib.ptr(x), _lib.ptr(y), _lib.ptr(inv), x.shape[0], _lib.ptr(d_rows), rows_mul, x.shape[1])

@@ -308,6 +308,23 @@ int ccd_region_pool_bwd(const ccd_bf16* d_rows, const uint8_t* tok_plane, const 
 int ccd_idmap_to_planes(const uint8_t* idmap, float* planes, int images, void* stream);
 int ccd_planes_to_idmap(const float* planes, uint8_t* idmap, int images, void* stream);
 
+/* ---------------------------------------------------------------- the public clusterers of Dino/utils/DBSCAN.py
+ * One workgroup per 32x128 mask, images masks per launch; images == 0 is a no-op.  Outputs are bit-exact against the
+ * reference wherever its own order is defined (mean-column ties: lower cluster number first).
+ * DBSCAN_cluster.forward, Dino/utils/DBSCAN.py:14-59 (sklearn DBSCAN(eps=1.5, min_samples=4) on the pixels with mask > 0.1,
+ * restated on the grid: core = >= 3 foreground 8-neighbours, clusters = 8-connected core components, border pixels join the
+ * lowest-numbered neighbouring cluster; clusters of < 30 pixels dropped, the 26 with the smallest mean column kept, in that
+ * order): mask [images,32,128] fp32 -> idmap uint8 [images,32,128] (plane index, 255 = none)                          */
+int ccd_dbscan_label(const float* mask, uint8_t* idmap, int images, void* stream);
+/* region_cluster.forward, Dino/utils/DBSCAN.py:110-141 (8-connected components of mask != 0 + their bounding boxes, stable
+ * sort by xmin + xmax, first 26, boxes of area < 100 skipped): mask [images,32,128] fp32 -> boxes int32 [images,26,4]
+ * (ymin, xmin, ymax, xmax; half-open stops; slots >= count zero), count int32 [images]                               */
+int ccd_region_boxes(const float* mask, int* boxes, int* count, int images, void* stream);
+/* the reference's uint8 [26,32,128] planes per image (DBSCAN.py:25,56,78,127): from an id map (DBSCAN_cluster,
+ * label_cluster) or from boxes + count (region_cluster, planes may overlap); idmap and planes 16-byte aligned       */
+int ccd_idmap_to_planes_u8(const uint8_t* idmap, uint8_t* planes, int images, void* stream);
+int ccd_boxes_to_planes_u8(const int* boxes, const int* count, uint8_t* planes, int images, void* stream);
+
 /* ---------------------------------------------------------------- DINOHead pieces, vit.py:313,326 */
 int ccd_l2norm_fwd(const ccd_bf16* x, ccd_bf16* y, float* inv, int max_rows, const int* d_rows, int rows_mul, int D,
                    void* stream);

@@ -6,11 +6,12 @@ with the stub third-party modules of tools/oracle_stubs/ and its pretraining ite
 is re-enacted by this harness; nothing from the reference is copied - only its numerical outputs for our
 seeded synthetic inputs (ccd_amd/synthetic.py) are recorded.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py [--only ccl|tiny|small|sched]
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py [--only ccl|cluster|tiny|small|sched]
 
 Fixtures (all small):
   sched.npz        cosine_iter_scheduler / teacher-temp schedule arrays           (modules/utils.py:200-210)
   ccl_cases.npz    adversarial masks -> label_cluster outputs as uint8 id maps     (utils/DBSCAN.py:61-103)
+  cluster_cases.npz  masks -> DBSCAN_cluster / label_cluster / region_cluster planes (packbits)  (utils/DBSCAN.py:10-141)
   tiny_step.npz    3-block E=192 model, B=2: full tensors of every stage + grads (tiny8_step.npz: the same at B=8)
   arch_step.npz    BASELINE config #4's two architectures (vit_base = 512 / 8 heads, the 768 / 12 shape): one iteration each, B = 4
   small_step.npz   CCD_pretrain_ViT_small hyper-parameters, B=8, 2 iterations: losses, index maps,
@@ -182,6 +183,159 @@ def gen_ccl():
                         idmaps=np.stack(idmaps), has_tie=np.array(has_tie))
     print("ccl_cases.npz written:", dict(zip(names, has_tie)))
 
+
+
+# --------------------------------------------------------------------------------------------------
+def cluster_cases():
+    """Masks for the three clusterers of Dino/utils/DBSCAN.py (DBSCAN_cluster, label_cluster, region_cluster)."""
+    H, W = 32, 128
+    rs = np.random.RandomState(11)
+    f01 = np.float32(0.1)
+    cases = {}
+    cases["empty"] = np.zeros((H, W), np.float32)
+    cases["full"] = np.ones((H, W), np.float32)
+    # nonzero, but no pixel > 0.1: the reference's DBSCAN gets no points and takes its exception path (zero planes)
+    m = np.zeros((H, W), np.float32)
+    m[4:20, 10:40] = 0.05; m[6:26, 60:90] = f01
+    cases["below_threshold"] = m
+    # blocks just above / exactly at / just below float32(0.1) (DBSCAN keeps only the first)
+    m = np.zeros((H, W), np.float32)
+    m[4:12, 5:15] = np.nextafter(f01, np.float32(1)); m[4:12, 30:40] = f01; m[4:12, 55:65] = np.nextafter(f01, np.float32(0))
+    m[16:28, 80:100] = 0.7; m[18:26, 84:96] = f01                 # a core block with a hole of exactly 0.1
+    cases["threshold_edges"] = m
+    # 1-px lines: no pixel has 3 foreground neighbours -> DBSCAN sees only noise
+    m = np.zeros((H, W), np.float32)
+    m[3, 2:120] = 1; m[6:31, 5] = 1
+    for k in range(25):
+        m[6 + k, 20 + k] = 1; m[6 + k, 80 - k] = 1
+    cases["lines_1px"] = m
+    # a non-core pixel between two clusters' corners joins the lower-numbered one (both orientations)
+    m = np.zeros((H, W), np.float32)
+    m[5:11, 10:16] = 1; m[11, 16] = 1; m[12:18, 17:23] = 1        # upper-left cluster first
+    m[5:11, 60:66] = 1; m[11, 59] = 1; m[12:18, 53:59] = 1        # upper-right cluster first
+    cases["border_two_clusters"] = m
+    # the raster-first pixel of the lower cluster's region is a border pixel of the upper-right cluster (found first)
+    m = np.zeros((H, W), np.float32)
+    m[0:5, 27:35] = 1; m[5, 26] = 1; m[6:12, 20:26] = 1
+    m[14:20, 70:76] = 1; m[13, 69] = 1                              # a corner spur: a border pixel above its own core
+    cases["border_first_pixel"] = m
+    # DBSCAN clusters of 29 / 30 / 31 pixels counting border pixels (corner-diagonal pixels are border pixels)
+    m = np.zeros((H, W), np.float32)
+    m[2:7, 2:7] = 1; m[1, 1] = m[1, 7] = m[7, 1] = m[7, 7] = 1     # 25 core + 4 border = 29
+    m[2:7, 20:26] = 1                                               # 30 core
+    m[2:7, 40:46] = 1; m[7, 46] = 1                                 # 30 core + 1 border = 31
+    m[12:14, 2:15] = 1; m[11, 1] = m[11, 15] = m[14, 1] = 1         # 26 core + 3 border = 29
+    m[12:14, 30:43] = 1; m[11, 29] = m[11, 43] = m[14, 29] = m[14, 43] = 1   # 26 core + 4 border = 30
+    m[12:14, 60:74] = 1; m[11, 59] = m[11, 74] = m[14, 59] = 1      # 28 core + 3 border = 31
+    m[20:22, 90:104] = 1; m[24, 92] = 1                             # 28 core + 1 noise pixel
+    cases["dbscan_sizes_29_30_31"] = m
+    # 72 qualifying 3x10 blocks, every one with its own mean column: the 26 leftmost != the first 26 in raster order
+    m = np.zeros((H, W), np.float32)
+    for r in range(8):
+        for c in range(9):
+            m[4 * r:4 * r + 3, 13 * c + r:13 * c + r + 10] = 1
+    cases["many_staggered"] = m
+    # 88 blocks on a regular grid (mean-column ties inside every column)
+    m = np.zeros((H, W), np.float32)
+    for r in range(8):
+        for c in range(11):
+            m[4 * r:4 * r + 3, 11 * c:11 * c + 10] = 1
+    cases["many_grid"] = m
+    # specks on the left use up region slots among the first 26; only 6 of the big boxes on the right get planes
+    m = np.zeros((H, W), np.float32)
+    for k in range(20):
+        m[(k * 3) % 31, 2 * (k // 3)] = 1
+    for k in range(10):
+        m[2:30, 30 + 9 * k:36 + 9 * k] = 1
+    cases["specks_use_slots"] = m
+    # a dense field of isolated pixels: ~1 000 components, all specks
+    yy, xx = np.mgrid[0:H, 0:W]
+    cases["speck_lattice"] = ((yy % 2 == 0) & (xx % 2 == 0)).astype(np.float32)
+    m = cases["speck_lattice"].copy(); m[8:24, 40:90] = 1
+    cases["speck_lattice_block"] = m
+    # overlapping boxes: an L shape and a block inside its bounding box
+    m = np.zeros((H, W), np.float32)
+    m[2:30, 10:12] = 1; m[28:30, 10:60] = 1; m[5:16, 20:36] = 1
+    m[4:12, 80:120] = 1; m[14:30, 70:74] = 1; m[26:30, 70:100] = 1
+    cases["overlapping_boxes"] = m
+    # bounding-box areas 99 / 100 / 101 (outlines: the box area differs from the pixel count)
+    m = np.zeros((H, W), np.float32)
+    for (y0, x0, h, w) in ((2, 2, 9, 11), (2, 20, 10, 10), (2, 40, 9, 12), (30, 10, 1, 101), (15, 2, 11, 9), (15, 20, 4, 25),
+                           (15, 50, 3, 33), (15, 90, 3, 34)):
+        m[y0, x0:x0 + w] = 1; m[y0 + h - 1, x0:x0 + w] = 1; m[y0:y0 + h, x0] = 1; m[y0:y0 + h, x0 + w - 1] = 1
+    cases["box_area_99_100"] = m
+    # equal xmin + xmax between boxes that both make a plane: the stable sort keeps label order (bit-exact).  In every pair the
+    # box later in label order lies further left (or the pair is stacked), so the opposite tie order gives different planes.
+    m = np.zeros((H, W), np.float32)
+    m[2:12, 40:51] = 1; m[16:30, 35:56] = 1                         # key 91: 10 x 11 first, then 14 x 21 further left
+    m[2:14, 70:80] = 1; m[18:30, 65:85] = 1                         # key 150
+    m[2:12, 100:112] = 1; m[16:28, 100:112] = 1                     # key 212, stacked
+    cases["region_key_tie"] = m
+    # a tie across the 26-slot cut: 25 specks take slots 0..24, of the two tied boxes only the one first in label order is kept
+    m = np.zeros((H, W), np.float32)
+    m[0:32:2, 0] = 1; m[0:18:2, 2] = 1                              # 16 + 9 specks, keys 1 and 5
+    m[2:12, 20:31] = 1; m[16:30, 15:36] = 1                         # key 51: the upper box keeps slot 25, the wider lower one is cut
+    m[4:28, 90:110] = 1                                             # key 200: beyond the cut
+    cases["region_tie_cut"] = m
+    # equal mean columns (flagged: the reference's np.argsort leaves the order open)
+    m = np.zeros((H, W), np.float32)
+    m[2:9, 10:20] = 1; m[20:27, 10:20] = 1; m[2:9, 40:50] = 1; m[12:30, 43:47] = 1
+    cases["mean_col_tie"] = m
+    # text-like masks of the synthetic pipeline
+    _, masks, _ = make_text_like_batch(6, seed=21)
+    for i in range(masks.shape[0]):
+        cases[f"text_like_{i}"] = masks[i].numpy().astype(np.float32)
+    # random binary masks at several densities, dilated specks, and float masks around the DBSCAN threshold
+    for p in (0.1, 0.3, 0.5, 0.7):
+        cases[f"random_p{int(p * 100)}"] = (rs.uniform(size=(H, W)) < p).astype(np.float32)
+    for p in (0.02, 0.05):
+        s = rs.uniform(size=(H, W)) < p
+        d = s.copy()
+        d[1:] |= s[:-1]; d[:, 1:] |= s[:, :-1]; d[1:, 1:] |= s[:-1, :-1]
+        cases[f"dilated_specks_p{int(p * 100)}"] = d.astype(np.float32)
+    cases["random_float"] = (rs.uniform(size=(H, W)) * 0.25).astype(np.float32)
+    blobs = np.zeros((H, W), np.float32)
+    for _ in range(12):
+        y0, x0 = rs.randint(0, 26), rs.randint(0, 120)
+        blobs[y0:y0 + rs.randint(3, 9), x0:x0 + rs.randint(3, 9)] = rs.choice([0.05, 0.1, 0.3, 1.0])
+    cases["blocks_mixed_values"] = blobs
+    return cases
+
+
+def _mean_col_tie(ids, min_area=30, first=None):
+    """Do two qualifying clusters of a (row-major) id array share a mean column?  ids: -1 = none."""
+    means = []
+    for c in np.unique(ids[ids >= 0]):
+        xs = np.nonzero(ids == c)[1]
+        if xs.size >= min_area:
+            means.append(xs.mean())
+            if first is not None and len(means) >= first:
+                break
+    return len(set(means)) != len(means)
+
+
+def gen_cluster():
+    from Dino.utils.DBSCAN import DBSCAN_cluster, label_cluster, region_cluster
+    from scipy import ndimage
+    from sklearn.cluster import DBSCAN
+    clusterers = (DBSCAN_cluster(eps=1.5, min_samples=4), label_cluster(), region_cluster())
+    names, masks, planes, has_tie = [], [], [[], [], []], []
+    for name, m in cluster_cases().items():
+        names.append(name); masks.append(m)
+        for k, f in enumerate(clusterers):
+            out = f(m)
+            assert out.dtype == np.uint8 and out.shape == (26, 32, 128)
+            planes[k].append(np.packbits(out, axis=-1))
+        ys, xs = np.nonzero(m > 0.1)
+        db = np.full(m.shape, -1)
+        if ys.size:
+            db[ys, xs] = DBSCAN(eps=1.5, min_samples=4).fit_predict(np.stack([ys, xs], 1))
+        cl = ndimage.label(m != 0, structure=np.ones((3, 3)))[0] - 1
+        has_tie.append([_mean_col_tie(db), _mean_col_tie(cl, first=26), False])      # region_cluster's sort is stable
+    np.savez_compressed(os.path.join(GOLD, "cluster_cases.npz"), names=np.array(names), masks=np.stack(masks),
+                        dbscan=np.stack(planes[0]), label=np.stack(planes[1]), region=np.stack(planes[2]),
+                        has_tie=np.array(has_tie))
+    print("cluster_cases.npz written:", {n: t for n, t in zip(names, has_tie) if any(t)})
 
 # --------------------------------------------------------------------------------------------------
 def build_reference_pair(arch_kwargs, head_kwargs, seg_channel, seed, drop_path_rate, tiny):
@@ -799,7 +953,7 @@ if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     os.chdir("/root/reference")  # Config() and friends use relative paths; we never write here
     torch.set_num_threads(8)
-    todo = [a.only] if a.only else ["sched", "ccl", "tiny", "small", "small3", "arch", "keys", "finetune", "kmeans", "eval"]
+    todo = [a.only] if a.only else ["sched", "ccl", "cluster", "tiny", "small", "small3", "arch", "keys", "finetune", "kmeans", "eval"]
     for t in todo:
-        {"sched": gen_sched, "ccl": gen_ccl, "tiny": gen_tiny, "arch": gen_arch, "small": gen_small, "small3": gen_small3, "keys": gen_keys,
+        {"sched": gen_sched, "ccl": gen_ccl, "cluster": gen_cluster, "tiny": gen_tiny, "arch": gen_arch, "small": gen_small, "small3": gen_small3, "keys": gen_keys,
          "finetune": gen_finetune, "kmeans": gen_kmeans, "eval": gen_eval, "small_noise": gen_small_noise}[t]()
