@@ -74,6 +74,12 @@ SIGNATURES = {
     "ccd_region_boxes": [P, P, P, I, P],
     "ccd_idmap_to_planes_u8": [P, P, I, P],
     "ccd_boxes_to_planes_u8": [P, P, P, I, P],
+    "ccd_ssim_ws_doubles": [I, I, I, I],
+    "ccd_ssim_fwd": [P, L, L, P, L, L, P, L, L, I, I, I, I, I, P, P, P],
+    "ccd_ssim_reduce": [P, I, I, I, I, P, P, P],
+    "ccd_ssim_bwd": [P, L, L, P, L, L, P, L, L, I, I, I, I, I, P, P, P, P, P, P],
+    "ccd_psnr_ws_doubles": [I, I, I, I],
+    "ccd_psnr_fwd": [P, L, L, P, L, L, I, I, I, I, P, P, P, P],
     "ccd_l2norm_fwd": [P, P, P, I, P, I, I, P],
     "ccd_l2norm_bwd": [P, P, P, P, I, P, I, I, P],
     "ccd_weightnorm_fwd": [P, P, P, P, P, I, I, P],
@@ -116,7 +122,8 @@ SIGNATURES = {
     "ccd_tf_loss_bwd": [P, L, I, P, I, I, I, P, P, P, P, L, P],
     "ccd_greedy_step": [P, L, I, I, P, I, I, P, I, P],
 }
-_RESTYPES = {"ccd_build_info": C.c_char_p, "ccd_attention_bwd_ws_floats": L, "ccd_gemm_tn_pair_ws_floats": L, "ccd_head_loss_ws_floats": L}
+_RESTYPES = {"ccd_build_info": C.c_char_p, "ccd_attention_bwd_ws_floats": L, "ccd_gemm_tn_pair_ws_floats": L, "ccd_head_loss_ws_floats": L,
+             "ccd_ssim_ws_doubles": L, "ccd_psnr_ws_doubles": L}
 
 
 def bind(lib: C.CDLL) -> C.CDLL:

@@ -19,6 +19,7 @@
 #include "kernels/layernorm.h"
 #include "kernels/charmap.h"
 #include "kernels/cluster.h"
+#include "kernels/ssim.h"
 #include "kernels/datapipe.h"
 #include "kernels/embed.h"
 #include "kernels/head.h"
@@ -277,8 +278,8 @@ static int ccd_launch_tn384_geom(ccd::GemmParams& p, int Mc, float* ws, long ws_
 
 extern "C" {
 
-int ccd_abi_version(void) { return 13; }   // 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
-const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi13"; }
+int ccd_abi_version(void) { return 14; }   // 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
+const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi14"; }
 int ccd_policy_set(const char* key, int value) {
     CCD_CHECK(key, CCD_EINVAL);
     for (const CcdPolicyKey& k : ccd_policy_keys)
@@ -1050,6 +1051,126 @@ int ccd_boxes_to_planes_u8(const int* boxes, const int* count, uint8_t* planes, 
                planes);
     return ccd_rt_last_error();
 }
+
+// ------------------------------------------------------------------------------- Dino/metric/eval_superpixel.py metrics
+static bool ccd_ssim_geometry(int images, int channels, int H, int W, int* tiles_x, int* tiles, long* planes) {
+    if (images < 0 || channels < 1 || H < 1 || W < 1) return false;
+    *tiles_x = (W + ccd::SS_TW - 1) / ccd::SS_TW;
+    *tiles = ((H + ccd::SS_FWD_TH - 1) / ccd::SS_FWD_TH) * *tiles_x;
+    *planes = (long)images * channels;
+    return *planes * (long)*tiles * 2 <= 0x7fffffffL;                // (the backward's 8-row tiles: twice as many)
+}
+// the three inputs' pointers + strides, checked: rows of W contiguous fp32, non-negative N / C strides; *vec = all 16-byte loadable
+static bool ccd_ssim_planes(const float* x1, long n1, long c1, const float* x2, long n2, long c2, const float* x3, long n3, long c3,
+                            int W, ccd::SsimPlanes* p, int* vec) {
+    const float* xs[3] = {x1, x2, x3};
+    const long ns[3] = {n1, n2, n3}, cs[3] = {c1, c2, c3};
+    int v = W % 4 == 0;
+    for (int i = 0; i < 3; ++i) {
+        p->x[i] = xs[i];
+        p->sn[i] = ns[i];
+        p->sc[i] = cs[i];
+        if (i < 2 && !xs[i]) return false;
+        if (!xs[i]) continue;
+        if (ns[i] < 0 || cs[i] < 0) return false;
+        v = v && CCD_ALIGNED16(xs[i]) && ns[i] % 4 == 0 && cs[i] % 4 == 0;
+    }
+    *vec = v;
+    return true;
+}
+static void ccd_ssim_taps(int window, const float* taps, ccd::SsimTaps* tp) {
+    for (int j = 0; j < 2 * ccd::SS_MAX_R + 1; ++j) tp->g[j] = j < window ? taps[j] : 0.0f;
+}
+#define CCD_SSIM_R_SWITCH(R_, LAUNCH)                                                                                   \
+    switch (R_) {                                                                                                       \
+        case 0: LAUNCH(0); break; case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break;         \
+        case 4: LAUNCH(4); break; case 5: LAUNCH(5); break; case 6: LAUNCH(6); break; case 7: LAUNCH(7); break;         \
+        default: return CCD_ESHAPE;                                                                                     \
+    }
+
+long ccd_ssim_ws_doubles(int images, int channels, int H, int W) {
+    int tiles_x, tiles;
+    long planes;
+    if (!ccd_ssim_geometry(images, channels, H, W, &tiles_x, &tiles, &planes)) return -1;
+    return planes * tiles;
+}
+int ccd_ssim_fwd(const float* x1, long n1, long c1, const float* x2, long n2, long c2, const float* x3, long n3, long c3, int images,
+                 int channels, int H, int W, int window, const float* taps, double* partials, void* stream) {
+    int tiles_x, tiles, vec;
+    long planes;
+    CCD_CHECK(ccd_ssim_geometry(images, channels, H, W, &tiles_x, &tiles, &planes), CCD_ESHAPE);
+    CCD_CHECK(window >= 1 && window <= 2 * ccd::SS_MAX_R + 1 && window % 2 == 1, CCD_ESHAPE);
+    if (images == 0) return CCD_OK;
+    ccd::SsimPlanes p;
+    ccd::SsimTaps tp;
+    CCD_CHECK(taps && partials && ccd_ssim_planes(x1, n1, c1, x2, n2, c2, x3, n3, c3, W, &p, &vec), CCD_EINVAL);
+    ccd_ssim_taps(window, taps, &tp);
+    const dim3 grid((unsigned)(planes * tiles)), block(ccd::SS_THREADS);
+#define CCD_SSIM_FWD(R) \
+    if (x3) CCD_LAUNCH((ccd::ssim_fwd_kernel<3, R>), grid, block, 0, stream, p, channels, H, W, tiles_x, tiles, tp, vec, partials); \
+    else CCD_LAUNCH((ccd::ssim_fwd_kernel<2, R>), grid, block, 0, stream, p, channels, H, W, tiles_x, tiles, tp, vec, partials)
+    CCD_SSIM_R_SWITCH(window / 2, CCD_SSIM_FWD)
+#undef CCD_SSIM_FWD
+    return ccd_rt_last_error();
+}
+int ccd_ssim_reduce(const double* partials, int images, int channels, int H, int W, float* per_image, float* mean, void* stream) {
+    int tiles_x, tiles;
+    long planes;
+    CCD_CHECK(ccd_ssim_geometry(images, channels, H, W, &tiles_x, &tiles, &planes), CCD_ESHAPE);
+    if (images == 0) return CCD_OK;
+    CCD_CHECK(partials && per_image, CCD_EINVAL);
+    const double count = (double)channels * H * W;
+    CCD_LAUNCH(ccd::ssim_reduce_kernel, dim3(1), dim3(ccd::SS_THREADS), 0, stream, partials, images, channels * tiles, count, per_image,
+               mean);
+    return ccd_rt_last_error();
+}
+int ccd_ssim_bwd(const float* x1, long n1, long c1, const float* x2, long n2, long c2, const float* x3, long n3, long c3, int images,
+                 int channels, int H, int W, int window, const float* taps, const float* gscale, float* dx1, float* dx2, float* dx3,
+                 void* stream) {
+    int tiles_x, tiles, vec;
+    long planes;
+    CCD_CHECK(ccd_ssim_geometry(images, channels, H, W, &tiles_x, &tiles, &planes), CCD_ESHAPE);
+    CCD_CHECK(window >= 1 && window <= 2 * ccd::SS_MAX_R + 1 && window % 2 == 1, CCD_ESHAPE);
+    if (images == 0) return CCD_OK;
+    ccd::SsimPlanes p;
+    ccd::SsimTaps tp;
+    CCD_CHECK(taps && gscale && ccd_ssim_planes(x1, n1, c1, x2, n2, c2, x3, n3, c3, W, &p, &vec), CCD_EINVAL);
+    CCD_CHECK(!dx3 || x3, CCD_EINVAL);
+    if (!dx1 && !dx2 && !dx3) return CCD_OK;
+    ccd_ssim_taps(window, taps, &tp);
+    const int th = x3 ? ccd::SsimBwdGeom<3, 0>::TH : ccd::SsimBwdGeom<2, 0>::TH;
+    const int btiles = ((H + th - 1) / th) * tiles_x;
+    const dim3 grid((unsigned)(planes * btiles)), block(ccd::SS_THREADS);
+#define CCD_SSIM_BWD(R) \
+    if (x3) CCD_LAUNCH((ccd::ssim_bwd_kernel<3, R>), grid, block, 0, stream, p, channels, H, W, tiles_x, btiles, tp, vec, gscale, dx1, \
+                       dx2, dx3); \
+    else CCD_LAUNCH((ccd::ssim_bwd_kernel<2, R>), grid, block, 0, stream, p, channels, H, W, tiles_x, btiles, tp, vec, gscale, dx1, \
+                    dx2, dx3)
+    CCD_SSIM_R_SWITCH(window / 2, CCD_SSIM_BWD)
+#undef CCD_SSIM_BWD
+    return ccd_rt_last_error();
+}
+long ccd_psnr_ws_doubles(int images, int channels, int H, int W) {
+    if (images < 0 || channels < 1 || channels > 3 || H < 1 || W < 1 || (long)H * W > 0x7fffffffL - ccd::PSNR_CHUNK) return -1;
+    const long chunks = ((long)H * W + ccd::PSNR_CHUNK - 1) / ccd::PSNR_CHUNK;
+    const long n = (long)images * channels * chunks;
+    return n <= 0x7fffffffL ? n : -1;
+}
+int ccd_psnr_fwd(const float* a, long an, long ac, const float* b, long bn, long bc, int images, int channels, int H, int W,
+                 double* partials, double* mse, float* psnr, void* stream) {
+    const long nparts = ccd_psnr_ws_doubles(images, channels, H, W);
+    CCD_CHECK(nparts >= 0, CCD_ESHAPE);
+    if (images == 0) return CCD_OK;
+    CCD_CHECK(a && b && partials && mse && psnr && an >= 0 && ac >= 0 && bn >= 0 && bc >= 0, CCD_EINVAL);
+    const int HW = H * W, chunks = (HW + ccd::PSNR_CHUNK - 1) / ccd::PSNR_CHUNK;
+    const int vec = HW % 4 == 0 && CCD_ALIGNED16(a) && CCD_ALIGNED16(b) && an % 4 == 0 && ac % 4 == 0 && bn % 4 == 0 && bc % 4 == 0;
+    CCD_LAUNCH(ccd::psnr_partial_kernel, dim3((unsigned)nparts), dim3(ccd::SS_THREADS), 0, stream, a, an, ac, b, bn, bc, channels, HW,
+               chunks, vec, partials);
+    CCD_LAUNCH(ccd::psnr_final_kernel, dim3(1), dim3(ccd::SS_THREADS), 0, stream, (const double*)partials, (int)nparts,
+               (double)images * channels * HW, mse, psnr);
+    return ccd_rt_last_error();
+}
+#undef CCD_SSIM_R_SWITCH
 
 // ------------------------------------------------------------------------------- DINO head pieces
 int ccd_l2norm_fwd(const ccd_bf16* x, ccd_bf16* y, float* inv, int max_rows, const int* d_rows, int rows_mul, int D,

@@ -3,6 +3,7 @@ current stream; nothing here computes on the host."""
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch
 
@@ -680,6 +681,134 @@ def boxes_to_planes_u8(boxes, count):
     out = torch.empty((boxes.shape[0], 26, 32, 128), dtype=U8, device=boxes.device)
     _call("ccd_boxes_to_planes_u8", _lib.ptr(boxes), _lib.ptr(count), _lib.ptr(out), boxes.shape[0])
     return out
+
+
+# ------------------------------------------------------------------------------------------ Dino/metric/eval_superpixel.py metrics
+F64 = torch.float64
+SSIM_MAX_WINDOW = 15
+
+
+def _plane_strides(x):
+    """(N stride, C stride) of an fp32 [N, C, H, W] tensor whose rows are contiguous with stride W (what the kernels read)."""
+    assert x.dtype == F32 and x.dim() == 4
+    assert x.stride(3) == 1 or x.shape[3] == 1, "rows must be contiguous"
+    assert x.stride(2) == x.shape[3] or x.shape[2] == 1, "rows must follow each other with stride W"
+    return x.stride(0), x.stride(1)
+
+
+def _ssim_inputs(imgs):
+    """ctypes arguments (x, n stride, c stride) x 3 for 2 or 3 same-shape inputs; a missing third input is NULL."""
+    assert len(imgs) in (2, 3) and all(tuple(x.shape) == tuple(imgs[0].shape) for x in imgs)
+    args = []
+    for i in range(3):
+        if i < len(imgs):
+            args += [_lib.ptr(imgs[i]), *_plane_strides(imgs[i])]
+        else:
+            args += [None, 0, 0]
+    return args
+
+
+def _taps_arg(window, taps):
+    assert window % 2 == 1 and 1 <= window <= SSIM_MAX_WINDOW and len(taps) == window
+    return (ctypes.c_float * window)(*taps)
+
+
+def ssim_fwd(imgs, window, taps, size_average):
+    """SSIM (2 inputs) / TRI_SSIM (3 inputs) of fp32 [N, C, H, W] images -> (per-image mean fp32 [N], batch mean fp32 0-dim or None).
+    taps: the window's 1-D Gaussian (host floats)."""
+    N, C, H, W = imgs[0].shape
+    dev = imgs[0].device
+    per = torch.empty((N,), dtype=F32, device=dev)
+    mean = torch.empty((), dtype=F32, device=dev) if size_average else None
+    if N == 0:
+        return per, (mean.fill_(float("nan")) if size_average else None)
+    nws = _lib.get().ccd_ssim_ws_doubles(N, C, H, W)
+    if nws < 0:
+        raise ValueError(f"ssim: unsupported shape {[N, C, H, W]}")
+    ws = torch.empty((nws,), dtype=F64, device=dev)
+    t = _taps_arg(window, taps)
+    _call("ccd_ssim_fwd", *_ssim_inputs(imgs), N, C, H, W, window, ctypes.addressof(t), _lib.ptr(ws))
+    _call("ccd_ssim_reduce", _lib.ptr(ws), N, C, H, W, _lib.ptr(per), _lib.ptr(mean))
+    return per, mean
+
+
+def ssim_bwd(imgs, window, taps, gscale, need):
+    """Gradients of sum_n gscale[n] * (sum of image n's map) w.r.t. the inputs with need[i]: contiguous fp32 [N, C, H, W] or None."""
+    N, C, H, W = imgs[0].shape
+    assert gscale.dtype == F32 and gscale.is_contiguous() and tuple(gscale.shape) == (N,)
+    dx = [torch.empty((N, C, H, W), dtype=F32, device=x.device) if need[i] else None for i, x in enumerate(imgs)]
+    dx += [None] * (3 - len(dx))
+    if N and any(d is not None for d in dx):
+        t = _taps_arg(window, taps)
+        _call("ccd_ssim_bwd", *_ssim_inputs(imgs), N, C, H, W, window, ctypes.addressof(t), _lib.ptr(gscale),
+              _lib.ptr(dx[0]), _lib.ptr(dx[1]), _lib.ptr(dx[2]))
+    return dx[:len(imgs)]
+
+
+def psnr_fwd(a, b):
+    """calculate_psnr's sums on channels 0..min(C, 3)-1 of fp32 [N, C, H, W] a, b -> (psnr fp32 0-dim, mse fp64 0-dim), on the device."""
+    assert tuple(a.shape) == tuple(b.shape)
+    N, C, H, W = a.shape
+    ch = min(C, 3)
+    psnr = torch.empty((), dtype=F32, device=a.device)
+    mse = torch.empty((), dtype=F64, device=a.device)
+    if N == 0:
+        return psnr.fill_(float("nan")), mse.fill_(float("nan"))
+    nws = _lib.get().ccd_psnr_ws_doubles(N, ch, H, W)
+    if nws < 0:
+        raise ValueError(f"calculate_psnr: unsupported shape {[N, C, H, W]}")
+    ws = torch.empty((nws,), dtype=F64, device=a.device)
+    _call("ccd_psnr_fwd", _lib.ptr(a), *_plane_strides(a), _lib.ptr(b), *_plane_strides(b), N, ch, H, W, _lib.ptr(ws),
+          _lib.ptr(mse), _lib.ptr(psnr))
+    return psnr, mse
+
+
+class SsimFn(torch.autograd.Function):
+    """apply(window, taps, size_average, img1, img2[, img3]) -> mean (0-dim) or per-image means [N]; backward on the kernels."""
+
+    @staticmethod
+    def forward(ctx, window, taps, size_average, *imgs):
+        per, mean = ssim_fwd(imgs, window, taps, size_average)
+        ctx.save_for_backward(*imgs)
+        ctx.window, ctx.taps, ctx.size_average = window, taps, size_average
+        return mean if size_average else per
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        imgs = ctx.saved_tensors
+        N, C, H, W = imgs[0].shape
+        if ctx.size_average:
+            gscale = (grad.float() / float(N * C * H * W)).expand(N).contiguous()
+        else:
+            gscale = (grad.float() / float(C * H * W)).contiguous()
+        dx = ssim_bwd(imgs, ctx.window, ctx.taps, gscale, ctx.needs_input_grad[3:])
+        return (None, None, None, *dx)
+
+
+class PsnrFn(torch.autograd.Function):
+    """apply(a, b) -> (psnr 0-dim fp32, mse 0-dim fp64, not differentiable).  d psnr / d a = -(20 / ln 10) 255^2 (a - b) / (mse count)
+    on the first min(C, 3) channels, zero on the others; d / d b = its negative (elementwise, not a hot path)."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        psnr, mse = psnr_fwd(a, b)
+        ctx.mark_non_differentiable(mse)
+        ctx.save_for_backward(a, b, mse)
+        return psnr, mse
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad, _grad_mse):
+        a, b, mse = ctx.saved_tensors
+        N, C, H, W = a.shape
+        ch = min(C, 3)
+        k = grad.double() * (-(20.0 / math.log(10.0)) * 255.0 ** 2) / (mse * float(N * ch * H * W))
+        d = torch.zeros(a.shape, dtype=F32, device=a.device)
+        d[:, :ch] = (k * (a[:, :ch].double() - b[:, :ch].double())).float()
+        da = d if ctx.needs_input_grad[0] else None
+        db = -d if ctx.needs_input_grad[1] else None
+        return da, db
 
 
 # ------------------------------------------------------------------------------------------ DINO head pieces

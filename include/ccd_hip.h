@@ -325,6 +325,36 @@ int ccd_region_boxes(const float* mask, int* boxes, int* count, int images, void
 int ccd_idmap_to_planes_u8(const uint8_t* idmap, uint8_t* planes, int images, void* stream);
 int ccd_boxes_to_planes_u8(const int* boxes, const int* count, uint8_t* planes, int images, void* stream);
 
+/* ---------------------------------------------------------------- the super-resolution metrics of Dino/metric/eval_superpixel.py
+ * Inputs are fp32 [images, channels, H, W] with contiguous rows (row stride W); n* / c* are the element strides of the image and
+ * channel dimensions, so a channel slice such as the [:, :3] view of an RGB + mask batch is read in place.  16-byte loads are used
+ * when every input is 16-byte aligned with W, n* and c* multiples of 4, scalar loads otherwise.  window: odd, 1..15 (CCD_ESHAPE
+ * otherwise); taps: HOST memory, the window's 1-D Gaussian (eval_superpixel.py:17-20, symmetric), applied as two separable passes
+ * with zero padding window / 2 (F.conv2d's padding).  images == 0 is a no-op.  No float atomics: results are bitwise repeatable
+ * and an image's values do not depend on the rest of the batch. */
+/* doubles of ccd_ssim_fwd's partials (one per (plane, 16x32 tile)); -1 on a bad shape */
+long ccd_ssim_ws_doubles(int images, int channels, int H, int W);
+/* _ssim / _tri_ssim, eval_superpixel.py:29-49,91-120 without the final mean: x3 == NULL -> SSIM of (x1, x2) (5 moments),
+ * else TRI_SSIM of (x1, x2, x3) (9 moments, no factor 2).  partials[ccd_ssim_ws_doubles] fp64: the sum of the map over each tile */
+int ccd_ssim_fwd(const float* x1, long n1, long c1, const float* x2, long n2, long c2, const float* x3, long n3, long c3, int images,
+                 int channels, int H, int W, int window, const float* taps, double* partials, void* stream);
+/* partials -> per_image fp32 [images] (the mean over channels x H x W, size_average=False) and, if mean != NULL, fp32 [1] the mean
+ * over the batch (size_average=True); one workgroup, fixed order */
+int ccd_ssim_reduce(const double* partials, int images, int channels, int H, int W, float* per_image, float* mean, void* stream);
+/* gradients of sum_n gscale[n] * sum over image n of the map (gscale fp32 [images] on the device: the upstream gradient over the
+ * count of the mean) w.r.t. each input whose dx* is non-NULL: fp32 contiguous [images, channels, H, W], overwritten.  One launch;
+ * the moments are recomputed, dS/d(moment) is blurred back with the same window (its adjoint) */
+int ccd_ssim_bwd(const float* x1, long n1, long c1, const float* x2, long n2, long c2, const float* x3, long n3, long c3, int images,
+                 int channels, int H, int W, int window, const float* taps, const float* gscale, float* dx1, float* dx2, float* dx3,
+                 void* stream);
+/* doubles of ccd_psnr_fwd's partials; -1 on a bad shape */
+long ccd_psnr_ws_doubles(int images, int channels, int H, int W);
+/* calculate_psnr, eval_superpixel.py:8-14, on the first `channels` (1..3: the caller's min(C, 3)) channels of a and b: mse fp64 [1] =
+ * the mean of (255 a - 255 b)^2 (products and difference rounded to fp32, square and sum in fp64), psnr fp32 [1] =
+ * 20 log10(255 / sqrt(mse)) (+inf for mse == 0, where the reference returns float('inf'): the caller's test) */
+int ccd_psnr_fwd(const float* a, long an, long ac, const float* b, long bn, long bc, int images, int channels, int H, int W,
+                 double* partials, double* mse, float* psnr, void* stream);
+
 /* ---------------------------------------------------------------- DINOHead pieces, vit.py:313,326 */
 int ccd_l2norm_fwd(const ccd_bf16* x, ccd_bf16* y, float* inv, int max_rows, const int* d_rows, int rows_mul, int D,
                    void* stream);

@@ -6,12 +6,14 @@ with the stub third-party modules of tools/oracle_stubs/ and its pretraining ite
 is re-enacted by this harness; nothing from the reference is copied - only its numerical outputs for our
 seeded synthetic inputs (ccd_amd/synthetic.py) are recorded.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py [--only ccl|cluster|tiny|small|sched]
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py [--only ccl|cluster|superpixel|tiny|small|sched]
 
 Fixtures (all small):
   sched.npz        cosine_iter_scheduler / teacher-temp schedule arrays           (modules/utils.py:200-210)
   ccl_cases.npz    adversarial masks -> label_cluster outputs as uint8 id maps     (utils/DBSCAN.py:61-103)
   cluster_cases.npz  masks -> DBSCAN_cluster / label_cluster / region_cluster planes (packbits)  (utils/DBSCAN.py:10-141)
+  superpixel_cases.npz  8-bit images -> ssim / SSIM / TRI_SSIM / calculate_psnr values, their input gradients and the
+                   gaussian / create_window values  (metric/eval_superpixel.py)
   tiny_step.npz    3-block E=192 model, B=2: full tensors of every stage + grads (tiny8_step.npz: the same at B=8)
   arch_step.npz    BASELINE config #4's two architectures (vit_base = 512 / 8 heads, the 768 / 12 shape): one iteration each, B = 4
   small_step.npz   CCD_pretrain_ViT_small hyper-parameters, B=8, 2 iterations: losses, index maps,
@@ -946,6 +948,94 @@ def gen_kmeans():
     print(f"kmeans_masks.npz written: {len(imgs)} images ({dropped} dropped: reference output depends on its random restarts)")
 
 
+# --------------------------------------------------------------------------------------------------
+def _savez_reproducible(path, arrays):
+    """np.savez_compressed with a fixed zip timestamp, so that rerunning the generator reproduces the file byte for byte."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as zf:
+        for key, val in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(val), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            zf.writestr(info, buf.getvalue())
+
+
+def superpixel_cases():
+    """name -> ((x1, x2, x3) uint8 [N, C, H, W] (the images are u8 / 255 in fp32), window size, gradients to record).
+    Text-like views of ccd_amd.synthetic (flat ground + strokes) with noisy 'super-resolved' copies, uniform noise with a correlated
+    copy, and planes smaller than the window."""
+    g = torch.Generator().manual_seed(2024)
+
+    def q(x):
+        return np.clip(np.rint(x.numpy().astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
+
+    views, _, _ = make_text_like_batch(1, seed=12)
+    v = views.float().reshape(-1, 3, 32, 128)[:2]
+    lo = v.flatten(1).min(1).values.view(-1, 1, 1, 1)
+    hi = v.flatten(1).max(1).values.view(-1, 1, 1, 1)
+    t1 = (v - lo) / (hi - lo)
+    text = tuple(q(x) for x in (t1, (t1 + 0.08 * torch.randn(t1.shape, generator=g)).clamp(0, 1),
+                                (t1 + 0.15 * torch.randn(t1.shape, generator=g)).clamp(0, 1)))
+
+    def noise(shape):
+        a = torch.rand(shape, generator=g)
+        return tuple(q(x) for x in (a, (a + 0.1 * torch.randn(shape, generator=g)).clamp(0, 1), torch.rand(shape, generator=g)))
+
+    low = noise((2, 4, 16, 64))
+    return {
+        "text_ws11": (text, 11, ("ssim",)),
+        "text_ws7": (text, 7, ()),
+        "text_ws3": (text, 3, ()),
+        "lowres_ws11": (low, 11, ("ssim", "tri")),
+        "lowres_ws7": (low, 7, ("ssim",)),
+        "lowres_ws3": (low, 3, ("ssim",)),
+        "tiny_ws11": (noise((1, 1, 7, 13)), 11, ("ssim", "tri")),
+        "odd_ws15": (noise((1, 2, 9, 21)), 15, ("ssim", "tri")),
+    }
+
+
+def gen_superpixel():
+    from Dino.metric.eval_superpixel import SSIM, TRI_SSIM, calculate_psnr, create_window, gaussian, ssim
+    out = {}
+    names = []
+    for name, (u8, ws, grads) in superpixel_cases().items():
+        names.append(name)
+        x = [torch.from_numpy(u).float() / 255.0 for u in u8]
+        rec = {f"x{i + 1}_u8": u for i, u in enumerate(u8)}
+        rec["ws"] = np.int32(ws)
+        with torch.no_grad():
+            rec["ssim_mean"] = ssim(x[0], x[1], ws).numpy()
+            rec["ssim_img"] = ssim(x[0], x[1], ws, size_average=False).numpy()
+            rec["SSIM_mean"] = SSIM(ws)(x[0], x[1]).numpy()                       # the module: channels [:3] only
+            rec["SSIM_img"] = SSIM(ws, size_average=False)(x[0], x[1]).numpy()
+            rec["tri_mean"] = TRI_SSIM(ws)(x[0], x[1], x[2]).numpy()
+            rec["tri_img"] = TRI_SSIM(ws, size_average=False)(x[0], x[1], x[2]).numpy()
+            rec["psnr"] = np.float32(calculate_psnr(x[0], x[1]))
+            same = calculate_psnr(x[0], x[0].clone())
+            assert same == float("inf")
+            rec["psnr_same"] = np.float32(same)
+        if "ssim" in grads:
+            a, b = (t.clone().requires_grad_(True) for t in x[:2])
+            ssim(a, b, ws).backward()
+            rec["g_ssim_1"], rec["g_ssim_2"] = a.grad.numpy(), b.grad.numpy()
+        if "tri" in grads:
+            a, b, c = (t.clone().requires_grad_(True) for t in x)
+            TRI_SSIM(ws)(a, b, c).backward()
+            rec["g_tri_1"], rec["g_tri_2"], rec["g_tri_3"] = a.grad.numpy(), b.grad.numpy(), c.grad.numpy()
+        out.update({f"{name}/{k}": np.asarray(v) for k, v in rec.items()})
+    sizes = (1, 3, 7, 11, 15)
+    for ws in sizes:
+        out[f"gaussian/{ws}"] = gaussian(ws, 1.5).numpy()
+        out[f"window/{ws}"] = create_window(ws, 3).numpy()
+    out["names"] = np.array(names)
+    out["window_sizes"] = np.array(sizes, dtype=np.int32)
+    path = os.path.join(GOLD, "superpixel_cases.npz")
+    _savez_reproducible(path, out)
+    print(f"superpixel_cases.npz written: {len(names)} cases, {os.path.getsize(path)} bytes")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
@@ -953,7 +1043,7 @@ if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     os.chdir("/root/reference")  # Config() and friends use relative paths; we never write here
     torch.set_num_threads(8)
-    todo = [a.only] if a.only else ["sched", "ccl", "cluster", "tiny", "small", "small3", "arch", "keys", "finetune", "kmeans", "eval"]
+    todo = [a.only] if a.only else ["sched", "ccl", "cluster", "tiny", "small", "small3", "arch", "keys", "finetune", "kmeans", "eval", "superpixel"]
     for t in todo:
         {"sched": gen_sched, "ccl": gen_ccl, "cluster": gen_cluster, "tiny": gen_tiny, "arch": gen_arch, "small": gen_small, "small3": gen_small3, "keys": gen_keys,
-         "finetune": gen_finetune, "kmeans": gen_kmeans, "eval": gen_eval, "small_noise": gen_small_noise}[t]()
+         "finetune": gen_finetune, "kmeans": gen_kmeans, "eval": gen_eval, "small_noise": gen_small_noise, "superpixel": gen_superpixel}[t]()
