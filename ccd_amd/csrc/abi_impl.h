@@ -13,6 +13,7 @@
 #include "kernels/mlp_bwd.h"
 #include "kernels/rowproj.h"
 #include "kernels/attention_fwd.h"
+#include "kernels/attention_probs.h"
 #include "kernels/attention_bwd.h"
 #include "kernels/attention_bwd1.h"
 #include "kernels/gemm_tn384.h"
@@ -278,8 +279,8 @@ static int ccd_launch_tn384_geom(ccd::GemmParams& p, int Mc, float* ws, long ws_
 
 extern "C" {
 
-int ccd_abi_version(void) { return 14; }   // 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
-const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi14"; }
+int ccd_abi_version(void) { return 15; }   // 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
+const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi15"; }
 int ccd_policy_set(const char* key, int value) {
     CCD_CHECK(key, CCD_EINVAL);
     for (const CcdPolicyKey& k : ccd_policy_keys)
@@ -793,6 +794,18 @@ int ccd_attention_fwd(const ccd_bf16* qkv, ccd_bf16* out, float* lse, int views,
     // staging already hides under the other's products; removed again, profiles/r04_attn_onepass_lab.jsonl.)
     CCD_LAUNCH(ccd::attention_fwd_kernel, dim3(views * heads), dim3(256), ccd::ATT_SMEM_BYTES, stream, qkv, out, lse,
                heads, scale);
+    return ccd_rt_last_error();
+}
+
+int ccd_attention_probs(const ccd_bf16* qkv, float* probs, int views, int heads, float scale, void* stream) {
+    CCD_CHECK(qkv && probs && CCD_ALIGNED16(qkv) && CCD_ALIGNED16(probs), CCD_EINVAL);
+    if (views == 0) return CCD_OK;
+    CCD_CHECK(views > 0 && heads > 0, CCD_EINVAL);
+    // the backbone's widths: E = 128 (test architecture), 192, 384, 512, 768 with head_dim 64
+    if (heads != 2 && heads != 3 && heads != 6 && heads != 8 && heads != 12) return CCD_ESHAPE;
+    CCD_CHECK((long)views * heads * 2 <= 0x7fffffffL, CCD_EINVAL);
+    CCD_LAUNCH(ccd::attention_probs_kernel, dim3(views * heads * 2), dim3(256), ccd::ATTP_SMEM_BYTES, stream, qkv, probs, heads,
+               scale);
     return ccd_rt_last_error();
 }
 

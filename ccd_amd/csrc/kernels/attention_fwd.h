@@ -9,8 +9,8 @@
 // The MFMA k-slot <-> key assignment of P^T is whatever the S^T accumulator layout gives
 // (lanes < 32: keys {0-3, 8-11} of each 16-key group, lanes >= 32: keys {4-7, 12-15}); V^T is written to LDS
 // with the same permutation, so no cross-lane data movement is needed between the two products.
-// The [256,256] attention matrix is never materialised (it is only consumed by get_last_selfattention,
-// vision_transformer.py:92/253-261, which is off the pretraining path).
+// The [256,256] attention matrix is never materialised here: get_last_selfattention (vision_transformer.py:92/253-261, off the
+// pretraining path) takes it from attention_probs.h.
 // Saves LSE[view, head, q] = max*scale + log(sum) for the backward pass.
 #pragma once
 

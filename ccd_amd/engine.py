@@ -154,8 +154,10 @@ class _BlockCtx:
                  "ds1", "ds2")
 
 
-def backbone_forward(arena, pre, spec: VitSpec, img, resample, save, training, need_taps=True):
-    """img [N,3,32,128] fp32 -> (tokens bf16 [N*256,E], [tap bf16 [N*256,E]] * len(taps), ctx or None)."""
+def backbone_forward(arena, pre, spec: VitSpec, img, resample, save, training, need_taps=True, keep=None):
+    """img [N,3,32,128] fp32 -> (tokens bf16 [N*256,E], [tap bf16 [N*256,E]] * len(taps), ctx or None).
+    keep (backbone_inspect): a dict {"n": n, "attn": bool, "x": []} that receives in "x" the fp32 residual stream after each of the
+    last n blocks and, with "attn", in "qkv" the last block's bf16 qkv rows."""
     E, N = spec.E, img.shape[0]
     R = N * 256
     dev = img.device
@@ -246,6 +248,10 @@ def backbone_forward(arena, pre, spec: VitSpec, img, resample, save, training, n
                                       bias=arena.w(b + "mlp.fc1.bias"), store_u=save)
             x = ops.gemm_nt(c.gact, arena.wb(b + "mlp.fc2.weight"), epilogue=ops.EPI_RESID,
                             bias=arena.w(b + "mlp.fc2.bias"), resid=c.x_mid, rowscale=c.ds2, rows_per_sample=256)
+        if keep is not None and i >= spec.depth - keep["n"]:
+            keep["x"].append(x)
+            if i == spec.depth - 1 and keep["attn"]:
+                keep["qkv"] = c.qkv
         if not save:
             c.y1 = c.qkv = c.att = c.y2 = c.u = c.gact = None
         ctxs.append(c if save else None)
@@ -263,6 +269,25 @@ def backbone_forward(arena, pre, spec: VitSpec, img, resample, save, training, n
         tokens, mu, rs = pending
     ctx = (ctxs, tap_ctx, (x, mu, rs), img) if save else None
     return tokens, taps, ctx
+
+
+def backbone_inspect(module, img, n=1, attention=False):
+    """The inference pass behind get_intermediate_layers / get_last_selfattention (vision_transformer.py:253-271): the blocks run as
+    in backbone_forward with nothing saved, no DropPath (the seed stream is not touched) and no taps, 1 <= n <= depth.
+    -> (streams, normed, probs):
+      streams  the fp32 residual stream [N*256,E] after each of the last n blocks, in block order;
+      normed   norm(stream) bf16 [N*256,E] of the same blocks - ops.ln_fwd for the earlier ones, the fused epilogue's output for the
+               last, i.e. forward's tokens;
+      probs    with `attention`: the last block's attention probabilities fp32 [N,heads,256,256] (ops.attention_probs on its qkv),
+               else None."""
+    arena, pre, spec = module.ensure_arena(), module.arena_prefix, module.spec
+    E, N = spec.E, img.shape[0]
+    keep = {"n": n, "attn": attention, "x": []}
+    tokens, _, _ = backbone_forward(arena, pre, spec, img, module.resample, False, False, need_taps=False, keep=keep)
+    normed = [ops.ln_fwd(x, arena.w(pre + "norm.weight"), arena.w(pre + "norm.bias"), spec.eps)[0] for x in keep["x"][:-1]]
+    normed.append(tokens)
+    probs = ops.attention_probs(keep["qkv"].view(N, 256, 3 * E), spec.heads, (E // spec.heads) ** -0.5) if attention else None
+    return keep["x"], normed, probs
 
 
 class _SideStream:

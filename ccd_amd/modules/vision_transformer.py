@@ -13,7 +13,7 @@ from functools import partial
 import torch
 import torch.nn as nn
 
-from .. import _lib, engine
+from .. import _lib, engine, ops
 from ..arena import ParamArena
 from .utils import trunc_normal_
 
@@ -121,6 +121,51 @@ class VisionTransformer(ArenaModule):
     def forward(self, x):
         tokens, *taps = self.tokens_and_taps(x)
         return tokens, [self.to_2D(t) for t in taps]
+
+    # ---- inspection (vision_transformer.py:182-201, 225-236, 253-271): inference passes outside autograd, no DropPath in either mode
+    def _image(self, x):
+        dev = next(self.parameters()).device
+        if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (3, 32, 128) or x.device != dev:
+            raise ValueError(f"expected fp32 images [N, 3, 32, 128] on {dev}, got "
+                             f"{(x.dtype, tuple(x.shape), x.device) if torch.is_tensor(x) else type(x).__name__}")
+        return x.contiguous()
+
+    def interpolate_pos_encoding(self, x, w, h):
+        """The bicubically resampled position table fp32 [1, 256, E] for (w, h) = (32, 128), the only input size (x: the patch
+        tokens, only their shape is read)."""
+        E = self.spec.E
+        if (w, h) != (32, 128) or not torch.is_tensor(x) or x.dim() != 3 or x.shape[1] != 256 or x.shape[-1] != E:
+            raise ValueError(f"interpolate_pos_encoding covers tokens [N, 256, {E}] of 32 x 128 images, got "
+                             f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__} and (w, h) = {(w, h)}")
+        arena = self.ensure_arena()
+        out = torch.empty((256, E), dtype=torch.float32, device=self.resample.device)
+        ops.small_matmul(self.resample, arena.w(self.arena_prefix + "pos_embed").view(-1, E), out)
+        return out.view(1, 256, E)
+
+    def prepare_tokens(self, x):
+        """Patch embedding + position encoding, fp32 [N, 256, E] (pos_drop is the identity: the constructor refuses drop_rate)."""
+        img = self._image(x)
+        arena, pre = self.ensure_arena(), self.arena_prefix
+        pos = self.interpolate_pos_encoding(img.new_empty((0, 256, self.spec.E)), 32, 128).view(256, -1)
+        out = ops.patch_embed_fwd(img, arena.w(pre + "patch_embed.proj.weight"), arena.w(pre + "patch_embed.proj.bias"), pos)
+        return out.view(img.shape[0], 256, -1)
+
+    def get_last_selfattention(self, x):
+        """(x_last fp32 [N, 256, E], attn fp32 [N, heads, 256, 256]): the last block's output and its attention probabilities - the
+        reference's Block.forward(return_attention=True) tuple (upstream DINO returns attn alone)."""
+        img = self._image(x)
+        streams, _, probs = engine.backbone_inspect(self, img, 1, attention=True)
+        return streams[-1].view(img.shape[0], 256, -1), probs
+
+    def get_intermediate_layers(self, x, n=1):
+        """[norm(x_i)] for the last min(max(n, 0), depth) blocks, in block order: bf16 [N, 256, E] like forward's tokens (the last one
+        IS forward(x)[0])."""
+        img = self._image(x)
+        n = min(max(int(n), 0), self.spec.depth)
+        if n == 0:
+            return []
+        _, normed, _ = engine.backbone_inspect(self, img, n)
+        return [t.view(img.shape[0], 256, -1) for t in normed]
 
 
 def vit_tiny(patch_size=16, **kwargs):

@@ -436,6 +436,22 @@ def attention_fwd(qkv, heads, scale):
     return out, lse
 
 
+def attention_probs(qkv, heads, scale):
+    """qkv [views,256,3*E] bf16 -> the attention probabilities softmax(q k^T * scale), fp32 [views,heads,256,256] (inspection:
+    get_last_selfattention; the training path never materialises them)."""
+    _chk(qkv, BF16, "qkv")
+    if qkv.dim() != 3 or qkv.shape[1] != 256 or qkv.shape[2] != 3 * 64 * heads or not qkv.is_contiguous():
+        raise ValueError(f"attention_probs: qkv must be a contiguous [views, 256, 3 * 64 * heads] tensor, got {tuple(qkv.shape)} "
+                         f"with heads={heads}")
+    views, T = qkv.shape[0], qkv.shape[1]
+    probs = torch.empty((views, heads, T, T), dtype=F32, device=qkv.device)
+    # per (view, head): S = Q K^T, 2 * 256 * 256 * 64 flop; q and k read once, P written once
+    with _Span("attention_probs", views * heads * 2.0 * T * T * 64, views * heads * (2.0 * T * 64 * 2 + 4.0 * T * T)):
+        _lib.check(_lib.get().ccd_attention_probs(_lib.ptr(qkv), _lib.ptr(probs), views, heads, float(scale), _lib.stream()),
+                   "attention_probs")
+    return probs
+
+
 def attention_bwd(qkv, out, d_out, lse, heads, scale, d_bias=None, dout_colsum=None, dout_colsum_mat=None):
     """-> d_qkv bf16 [views,256,3E].  d_bias (fp32 [3E], optional): += the qkv-bias gradient (column sums of d_qkv) without a
     pass over d_qkv - q part inside the dQ kernel, k part identically 0, v part = colsum(d_out) = `dout_colsum` [E], or

@@ -209,6 +209,11 @@ int ccd_ln_bwd_g16(const ccd_bf16* dy, const float* x, const float* mean, const 
  * qkv [views, 256, 3, heads, 64] bf16 (the layout Attention.forward reshapes to), out [views, 256, heads*64]  */
 int ccd_attention_fwd(const ccd_bf16* qkv, ccd_bf16* out, float* lse, int views, int heads, float scale,
                       void* stream);
+/* The attention probabilities themselves (ABI 15): probs [views, heads, 256, 256] fp32 = softmax(q k^T * scale) per row, what
+ * Attention.forward returns as `attn` (vit.py:85-86, 92) and get_last_selfattention hands out (vit.py:253-260).  Inspection only:
+ * the training path never materialises them.  The kernel computes its own row max / sum (no LSE).  heads in {2, 3, 6, 8, 12}
+ * (E = 128, 192, 384, 512, 768) - CCD_ESHAPE otherwise.  No atomics: bitwise repeatable, each view independent of the others. */
+int ccd_attention_probs(const ccd_bf16* qkv, float* probs, int views, int heads, float scale, void* stream);
 /* d_qkv_bias (nullable, fp32 [3 * heads * 64], ACCUMULATED): the gradient of the qkv bias (vit.py:75 `qkv_bias`; what autograd's
  * Linear backward computes as grad_output.sum(0) over d_qkv) without a pass over d_qkv:
  *   q part  column sums of the fp32 dQ tiles, inside the dQ kernel; needs bias_ws = ccd_attention_bwd_ws_floats(views, heads)

@@ -20,6 +20,7 @@ Fixtures (all small):
                    sampled logits, per-parameter grad norms / post-step checksums
   small3_step.npz  the same model with perturbed head biases: 3 consecutive iterations + one at epoch 30 (predicted masks)
   finetune_step.npz  DINO_Finetune (vit_tiny/2 layers, vit_small/6 layers): 2 AdamW iterations + greedy decoding
+  selfattn_cases.npz  vit_small with perturbed qkv weights: interpolate_pos_encoding, get_last_selfattention, get_intermediate_layers
 """
 import argparse
 import os
@@ -1036,6 +1037,44 @@ def gen_superpixel():
     print(f"superpixel_cases.npz written: {len(names)} cases, {os.path.getsize(path)} bytes")
 
 
+# every attn.qkv.weight += scale * N(0, 1), one seeded generator, parameter order (tests/selfattn_ref.py: perturb_qkv).  At the plain init
+# every attention row is ~1/256 and a wrong key order would pass unnoticed; at 0.06 the rows' maxima are 2 - 20x uniform and a key
+# permutation moves them by ~100 % (relative L2).  Rows with maxima >= 0.2 need logits whose bf16 rounding alone moves the last block's
+# probabilities by more than the 2e-2 gate (0.10: 3e-2, 0.15: 0.3, measured on a bf16 restatement): the gate decides the scale.
+QKV_PERTURB = dict(seed=4321, scale=0.06)
+SELFATTN_ROWS = np.array([0, 7, 31, 32, 45, 63, 64, 100, 127, 128, 150, 191, 200, 222, 240, 255])
+
+
+def gen_selfattn():
+    """vit_small(patch_size=4) at seed 0 with perturbed qkv weights, two text-like images: interpolate_pos_encoding (64 rows),
+    get_last_selfattention (x_last and attn on 16 query rows, every head and key) and get_intermediate_layers(n=4) on the same rows
+    -> selfattn_cases.npz."""
+    from Dino.modules import vision_transformer as rvits
+    torch.manual_seed(0)
+    model = rvits.vit_small(patch_size=4).eval()
+    g = torch.Generator().manual_seed(QKV_PERTURB["seed"])
+    with torch.no_grad():
+        for n, p in model.named_parameters():
+            if n.endswith("attn.qkv.weight"):
+                p.add_(QKV_PERTURB["scale"] * torch.randn(p.shape, generator=g))
+    images = make_text_like_batch(2, seed=7)[0][:, 0].contiguous()
+    rows = SELFATTN_ROWS
+    pos_rows = np.arange(0, 256, 4)
+    with torch.no_grad():
+        tokens = model.patch_embed(images)
+        pos = model.interpolate_pos_encoding(tokens, 32, 128)
+        x_last, attn = model.get_last_selfattention(images)
+        inter = model.get_intermediate_layers(images, n=4)
+    out = {"perturb": np.array([QKV_PERTURB["seed"], QKV_PERTURB["scale"]]), "images": images.numpy(), "rows": rows,
+           "pos_rows": pos_rows, "pos": pos[0, pos_rows].numpy(), "x_last": x_last[:, rows].numpy(),
+           "attn": attn[:, :, rows].numpy(), "inter": torch.stack([t[:, rows] for t in inter]).numpy()}
+    path = os.path.join(GOLD, "selfattn_cases.npz")
+    _savez_reproducible(path, out)
+    mx = attn[:, :, rows].max(-1).values
+    print(f"selfattn_cases.npz written: {os.path.getsize(path)} bytes; attn row maxima median {float(mx.median()):.4f}, "
+          f"max {float(mx.max()):.4f}")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
@@ -1043,7 +1082,9 @@ if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     os.chdir("/root/reference")  # Config() and friends use relative paths; we never write here
     torch.set_num_threads(8)
-    todo = [a.only] if a.only else ["sched", "ccl", "cluster", "tiny", "small", "small3", "arch", "keys", "finetune", "kmeans", "eval", "superpixel"]
+    todo = [a.only] if a.only else ["sched", "ccl", "cluster", "tiny", "small", "small3", "arch", "keys", "finetune", "kmeans", "eval", "superpixel",
+                                    "selfattn"]
     for t in todo:
         {"sched": gen_sched, "ccl": gen_ccl, "cluster": gen_cluster, "tiny": gen_tiny, "arch": gen_arch, "small": gen_small, "small3": gen_small3, "keys": gen_keys,
-         "finetune": gen_finetune, "kmeans": gen_kmeans, "eval": gen_eval, "small_noise": gen_small_noise, "superpixel": gen_superpixel}[t]()
+         "finetune": gen_finetune, "kmeans": gen_kmeans, "eval": gen_eval, "small_noise": gen_small_noise, "superpixel": gen_superpixel,
+         "selfattn": gen_selfattn}[t]()
