@@ -96,6 +96,9 @@ SIGNATURES = {
     "ccd_seg_loss": [P, P, P, I, F, P, P, P],
     "ccd_seg_sumsq": [P, P, P, P, I, P, P],
     "ccd_adamw": [P, P, P, P, P, P, P, P, I, P, P, F, F, F, F, P],
+    "ccd_seg_moments": [P, P, P, P, P, I, P, P],
+    "ccd_sgd_momentum": [P, P, P, P, P, P, P, I, P, P, F, F, P],
+    "ccd_lars": [P, P, P, P, P, P, P, I, P, P, F, F, F, P],
     "ccd_clip_scale": [P, P, P, P, I, P, F, P],
     "ccd_ema": [P, P, P, L, F, F, P, P],
     "ccd_conv_gemm": [P, L, P, P, L, I, I, P, L, P, P, P, P],

@@ -279,8 +279,8 @@ static int ccd_launch_tn384_geom(ccd::GemmParams& p, int Mc, float* ws, long ws_
 
 extern "C" {
 
-int ccd_abi_version(void) { return 15; }   // 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
-const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi15"; }
+int ccd_abi_version(void) { return 16; }   // 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
+const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi16"; }
 int ccd_policy_set(const char* key, int value) {
     CCD_CHECK(key, CCD_EINVAL);
     for (const CcdPolicyKey& k : ccd_policy_keys)
@@ -1359,6 +1359,31 @@ int ccd_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq
     static_assert(sizeof(ccd_seg_hyper) == sizeof(ccd::SegHyper), "hyper layout");
     CCD_LAUNCH(ccd::adamw_kernel, dim3(nchunks), dim3(256), 0, stream, param, grad, exp_avg, exp_avg_sq, mirror, chunk_seg,
                chunk_begin, chunk_len, reinterpret_cast<const ccd::SegHyper*>(hyper), norm2, clip, beta1, beta2, eps);
+    return ccd_rt_last_error();
+}
+int ccd_seg_moments(const float* grad, const float* param, const int* chunk_seg, const long* chunk_begin, const int* chunk_len,
+                    int nchunks, float* moments, void* stream) {
+    CCD_CHECK(grad && param && chunk_seg && chunk_begin && chunk_len && moments && nchunks > 0, CCD_EINVAL);
+    const int cpb = 32;                                     // 128 KiB of gradients + 128 KiB of parameters per workgroup
+    CCD_LAUNCH(ccd::seg_moments_kernel, dim3((nchunks + cpb - 1) / cpb), dim3(256), 0, stream, grad, param, chunk_seg, chunk_begin,
+               chunk_len, moments, nchunks, cpb);
+    return ccd_rt_last_error();
+}
+int ccd_sgd_momentum(float* param, const float* grad, float* buf, ccd_bf16* mirror, const int* chunk_seg,
+                     const long* chunk_begin, const int* chunk_len, int nchunks, const ccd_seg_mom_hyper* hyper,
+                     const float* norm2, float clip, float momentum, void* stream) {
+    CCD_CHECK(param && grad && buf && chunk_seg && chunk_begin && chunk_len && hyper && norm2 && nchunks > 0, CCD_EINVAL);
+    static_assert(sizeof(ccd_seg_mom_hyper) == sizeof(ccd::SegMomHyper), "hyper layout");
+    CCD_LAUNCH(ccd::momentum_kernel<false>, dim3(nchunks), dim3(256), 0, stream, param, grad, buf, mirror, chunk_seg, chunk_begin,
+               chunk_len, reinterpret_cast<const ccd::SegMomHyper*>(hyper), norm2, clip, momentum, 0.0f);
+    return ccd_rt_last_error();
+}
+int ccd_lars(float* param, const float* grad, float* mu, ccd_bf16* mirror, const int* chunk_seg, const long* chunk_begin,
+             const int* chunk_len, int nchunks, const ccd_seg_mom_hyper* hyper, const float* moments, float clip,
+             float momentum, float eta, void* stream) {
+    CCD_CHECK(param && grad && mu && chunk_seg && chunk_begin && chunk_len && hyper && moments && nchunks > 0, CCD_EINVAL);
+    CCD_LAUNCH(ccd::momentum_kernel<true>, dim3(nchunks), dim3(256), 0, stream, param, grad, mu, mirror, chunk_seg, chunk_begin,
+               chunk_len, reinterpret_cast<const ccd::SegMomHyper*>(hyper), moments, clip, momentum, eta);
     return ccd_rt_last_error();
 }
 int ccd_clip_scale(float* grad, const int* chunk_seg, const long* chunk_begin, const int* chunk_len, int nchunks,

@@ -949,6 +949,28 @@ def adamw(param, grad, exp_avg, exp_avg_sq, mirror, chunk_seg, chunk_begin, chun
           _lib.ptr(norm2), float(clip), float(beta1), float(beta2), float(eps))
 
 
+def seg_moments(grad, param, chunk_seg, chunk_begin, chunk_len, moments):
+    """moments [segments, 3] fp32 += per-tensor {sum g^2, sum p^2, sum g p} (zeroed by the caller)."""
+    assert moments.dtype == torch.float32 and moments.is_contiguous() and moments.shape[-1] == 3
+    _call("ccd_seg_moments", _lib.ptr(grad), _lib.ptr(param), _lib.ptr(chunk_seg), _lib.ptr(chunk_begin), _lib.ptr(chunk_len),
+          chunk_seg.numel(), _lib.ptr(moments))
+
+
+def sgd_momentum(param, grad, buf, mirror, chunk_seg, chunk_begin, chunk_len, hyper, norm2, clip, momentum=0.9):
+    """hyper [segments, 4] fp32 on the device: lr, weight decay, (unused), active."""
+    _call("ccd_sgd_momentum", _lib.ptr(param), _lib.ptr(grad), _lib.ptr(buf), _lib.ptr(mirror), _lib.ptr(chunk_seg),
+          _lib.ptr(chunk_begin), _lib.ptr(chunk_len), chunk_seg.numel(), _lib.ptr(hyper), _lib.ptr(norm2), float(clip),
+          float(momentum))
+
+
+def lars(param, grad, mu, mirror, chunk_seg, chunk_begin, chunk_len, hyper, moments, clip, momentum=0.9, eta=0.001):
+    """hyper [segments, 4] fp32 on the device: lr, weight decay, adapt (ndim != 1), active; moments: seg_moments' table."""
+    assert moments.shape[-1] == 3 and moments.is_contiguous()
+    _call("ccd_lars", _lib.ptr(param), _lib.ptr(grad), _lib.ptr(mu), _lib.ptr(mirror), _lib.ptr(chunk_seg),
+          _lib.ptr(chunk_begin), _lib.ptr(chunk_len), chunk_seg.numel(), _lib.ptr(hyper), _lib.ptr(moments), float(clip),
+          float(momentum), float(eta))
+
+
 def clip_scale(grad, chunk_seg, chunk_begin, chunk_len, norm2, clip):
     _call("ccd_clip_scale", _lib.ptr(grad), _lib.ptr(chunk_seg), _lib.ptr(chunk_begin), _lib.ptr(chunk_len),
           chunk_seg.numel(), _lib.ptr(norm2), float(clip))

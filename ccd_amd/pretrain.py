@@ -12,7 +12,7 @@ from .loss.Dino_loss import DINOLoss
 from .model.dino_vision import ABIDINOModel
 from .modules import vision_transformer as vits
 from .modules.segmentor import SegHead
-from .optim import FusedClipAdamW, ema_update
+from .optim import FusedClipAdamW, FusedClipLARS, FusedClipSGD, ema_update
 
 
 def build_networks(arch="vit_small", patch_size=4, out_dim=65536, drop_path_rate=0.1, norm_last_layer=False,
@@ -42,9 +42,14 @@ def build_networks(arch="vit_small", patch_size=4, out_dim=65536, drop_path_rate
     return student, teacher
 
 
-def make_optimizer(student_module, clip_grad=3.0):
+OPTIMIZERS = {"adamw": FusedClipAdamW, "sgd": FusedClipSGD, "lars": FusedClipLARS}      # the YAML's `optimizer` (train.py:131-137)
+
+
+def make_optimizer(student_module, clip_grad=3.0, name="adamw"):
+    if name not in OPTIMIZERS:
+        raise NotImplementedError(f"optimizer '{name}': the fused optimizers are {sorted(OPTIMIZERS)}")
     arena = student_module.ensure_arena()
-    opt = FusedClipAdamW(arena, clip_grad=clip_grad)
+    opt = OPTIMIZERS[name](arena, clip_grad=clip_grad)
     opt.mark_unused(student_module.unused_parameter_names())
     return opt
 
@@ -149,7 +154,7 @@ def training_iteration(student, teacher, dino_loss: DINOLoss, optimizer: FusedCl
     loss = _forward_backward(student, teacher, dino_loss, optimizer, images, masks, metrics, epoch, check_finite)
     if epoch < freeze_last_layer:
         s_mod.arena.skip_substrings.add("last_layer")        # cancel_gradients_last_layer (modules/utils.py:144-149)
-    optimizer.step()                                         # per-tensor clip + AdamW, fused
+    optimizer.step()                                         # per-tensor clip + AdamW / SGD / LARS, fused
     ema_update(s_mod.arena, t_mod.arena, float(momentum))
     return loss.detach()
 

@@ -415,6 +415,22 @@ int ccd_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq
               const int* chunk_seg, const long* chunk_begin, const int* chunk_len, int nchunks,
               const ccd_seg_hyper* hyper, const float* norm2, float clip, float beta1, float beta2, float eps,
               void* stream);
+/* torch.optim.SGD(momentum) and the reference's LARS (Dino/modules/utils.py:564-602) behind the same per-tensor clip, over the same
+ * chunk tables (ABI 16).  One table row per tensor, read when the kernel runs: lr, the tensor's weight decay, adapt (LARS: 1 = the
+ * tensor has ndim != 1, so weight decay and the trust ratio apply) and active (0 = no gradient this iteration: nothing is touched).
+ *   d = c g + wd p  (c = the clip coefficient);  LARS, adapt: d *= eta |p| / |d| unless either norm is 0;  LARS, 1-D: d = c g
+ *   buf = momentum buf + d;  p -= lr buf;  mirror = bf16(p)
+ * ccd_seg_moments: moments[3 s + {0, 1, 2}] += {sum g^2, sum p^2, sum g p} of tensor s (zero the table first), from which ccd_lars
+ * forms c and |c g + wd p|^2 = c^2 sum g^2 + 2 c wd sum g p + wd^2 sum p^2.  ccd_sgd_momentum reads ccd_seg_sumsq's norm2 table. */
+typedef struct ccd_seg_mom_hyper { float lr, wd, adapt, active; } ccd_seg_mom_hyper;
+int ccd_seg_moments(const float* grad, const float* param, const int* chunk_seg, const long* chunk_begin, const int* chunk_len,
+                    int nchunks, float* moments, void* stream);
+int ccd_sgd_momentum(float* param, const float* grad, float* buf, ccd_bf16* mirror, const int* chunk_seg,
+                     const long* chunk_begin, const int* chunk_len, int nchunks, const ccd_seg_mom_hyper* hyper,
+                     const float* norm2, float clip, float momentum, void* stream);
+int ccd_lars(float* param, const float* grad, float* mu, ccd_bf16* mirror, const int* chunk_seg, const long* chunk_begin,
+             const int* chunk_len, int nchunks, const ccd_seg_mom_hyper* hyper, const float* moments, float clip,
+             float momentum, float eta, void* stream);
 int ccd_clip_scale(float* grad, const int* chunk_seg, const long* chunk_begin, const int* chunk_len, int nchunks,
                    const float* norm2, float clip, void* stream);
 /* d_m (optional, device, 2 floats {m, 1 - m}): read at run time instead of the two launch arguments (HIP-graph replays of the step) */

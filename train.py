@@ -160,12 +160,10 @@ def train(config):
     print(f"training epochs is {config.epochs}")
     dino_loss = DINOLoss(config.out_dim, config.crops_number, config.warmup_teacher_temp, config.teacher_temp,
                          config.warmup_teacher_temp_epochs, config.epochs).cuda()
-    if config.optimizer != "adamw":
-        raise NotImplementedError("the shipped pretraining configs use adamw; only the fused AdamW is implemented")
     if config.use_fp16:
         raise NotImplementedError("use_fp16 is False in every shipped config; this implementation runs bf16 MFMA "
                                   "operands with fp32 master weights and needs no loss scaler")
-    optimizer = pretrain.make_optimizer(student.module, clip_grad=config.clip_grad or 0.0)
+    optimizer = pretrain.make_optimizer(student.module, clip_grad=config.clip_grad or 0.0, name=config.optimizer)
 
     niter = config.training_epochs * len(loader)
     lr_schedule = utils.cosine_iter_scheduler(config.lr * global_bs / 256., config.min_lr, niter,
