@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -16,127 +17,89 @@ LIB_PATH = os.environ.get("CCD_HIP_LIB") or os.path.join(_HERE, "libccd_hip.so")
 _handle = None            # ctypes.CDLL once loaded
 _stream_override = None   # tests of the ABI may pin the stream argument
 
-P = C.c_void_p
-I = C.c_int
-L = C.c_long
-F = C.c_float
-U64 = C.c_uint64
+HEADER_PATH = os.path.join(_HERE, "..", "include", "ccd_hip.h")
 
-# name -> argtypes (restype is always int unless listed in _RESTYPES); mirrors include/ccd_hip.h
-SIGNATURES = {
-    "ccd_abi_version": [],
-    "ccd_build_info": [],
-    "ccd_policy_set": [C.c_char_p, I],
-    "ccd_policy_get": [C.c_char_p, P],
-    "ccd_gemm_nt": [P, L, P, L, I, I, I, I, P, L, P, L, P, P, L, P, I, P, L, F, I, P, I, P, P],
-    "ccd_gemm_nt_resid_ln": [P, L, P, L, I, I, I, P, L, P, P, L, P, I, P, P, F, P, L, P, P, P],
-    "ccd_gemm_tn": [P, L, P, L, I, I, I, I, P, L, F, I, P, I, P],
-    "ccd_gemm_tn_colsum": [P, L, P, L, I, I, I, P, L, P, I, P],
-    "ccd_gemm_tn_pair": [P, L, P, L, I, I, P, L, P, L, P, L, I, I, P, L, I, P],
-    "ccd_gemm_tn_pair_ws": [P, L, P, L, I, I, P, L, P, L, P, L, I, I, P, L, I, P, L, P],
-    "ccd_gemm_tn_pair_ws_floats": [I, I, I, I],
-    "ccd_gemm_nt_lnbwd": [P, L, P, L, I, I, I, P, L, P, P, P, P, L, I, P, P, P, L, P, I, P, P],
-    "ccd_gemm_nt_lnbwd_g16": [P, L, P, L, I, I, I, P, L, P, P, P, P, L, I, P, P, P, L, P, I, P, P],
-    "ccd_gemm_nt_lnbwd_tap_g16": [P, L, P, L, I, I, I, P, L, P, P, P, P, L, I, P, P, P, L, P, I, P, P, L, P, P, P, P],
-    "ccd_proj_mlp_fused": [P, L, P, L, P, P, L, P, P, P, P, L, P, L, P, P, P, L, P, P, L, P, P, I, P, L, P, P, F, P, L, P, P, P, L, P, P, P, L,
-                           I, I, I, P],
-    "ccd_proj_mlp_fused_gact": [P, L, P, L, P, P, L, P, P, P, P, L, P, L, P, P, P, L, P, P, L, P, P, I, P, L, P, P, F, P, L, P, P, P, L, P, L,
-                                P, P, P, L, I, I, I, P],
-    "ccd_mlp_bwd_fused": [P, L, P, L, P, L, P, L, P, L, P, P, L, P, P, P, P, L, I, P, P, P, L, P, I, P, I, I, I, P],
-    "ccd_mlp_fused": [P, L, P, L, P, P, L, P, P, L, P, I, P, L, P, P, F, P, L, P, P, P, L, P, L, I, I, I, P],
-    "ccd_ln_fwd": [P, P, P, P, P, P, I, I, F, P],
-    "ccd_ln_bwd": [P, P, P, P, P, P, I, P, P, P, P, I, P, I, I, P],
-    "ccd_ln_bwd_g16": [P, P, P, P, P, P, I, P, P, P, P, I, P, I, I, P],
-    "ccd_attention_fwd": [P, P, P, I, I, F, P],
-    "ccd_attention_probs": [P, P, I, I, F, P],
-    "ccd_attention_bwd": [P, P, P, P, P, P, I, I, F, P, P, P, P, L, P],
-    "ccd_attention_bwd_ws_floats": [I, I],
-    "ccd_patch_embed_fwd": [P, P, P, P, P, I, I, P],
-    "ccd_patch_embed_bwd": [P, P, P, P, P, P, P, I, I, P],
-    "ccd_patch_embed_bwd_g16": [P, P, P, P, P, P, I, I, P],
-    "ccd_small_matmul_f32": [P, P, P, I, I, I, I, I, P],
-    "ccd_colsum_bf16": [P, L, I, I, P, I, P, P],
-    "ccd_mirror_bf16": [P, I, I, P],
-    "ccd_cast_bf16": [P, P, L, P],
-    "ccd_scale_cast_rows": [P, P, P, I, L, I, P],
-    "ccd_ccl_label": [P, P, I, P],
-    "ccd_mask_to_idmap": [P, P, I, P],
-    "ccd_seg_to_mask": [P, P, I, P],
-    "ccd_kmeans2_mask": [P, P, P, P, I, P],
-    "ccd_augment_views": [P, P, P, P, P, I, I, I, P, P, P, I, P, I, P],
-    "ccd_warp_idmap": [P, P, I, P, I, P],
-    "ccd_region_stats": [P, P, P, P, I, P],
-    "ccd_select_scan": [P, I, P, P, P, P, P],
-    "ccd_region_pool_fwd": [P, P, P, P, P, P, P, I, I, P],
-    "ccd_region_pool_bwd": [P, P, P, P, P, P, P, I, I, P],
-    "ccd_idmap_to_planes": [P, P, I, P],
-    "ccd_planes_to_idmap": [P, P, I, P],
-    "ccd_dbscan_label": [P, P, I, P],
-    "ccd_region_boxes": [P, P, P, I, P],
-    "ccd_idmap_to_planes_u8": [P, P, I, P],
-    "ccd_boxes_to_planes_u8": [P, P, P, I, P],
-    "ccd_ssim_ws_doubles": [I, I, I, I],
-    "ccd_ssim_fwd": [P, L, L, P, L, L, P, L, L, I, I, I, I, I, P, P, P],
-    "ccd_ssim_reduce": [P, I, I, I, I, P, P, P],
-    "ccd_ssim_bwd": [P, L, L, P, L, L, P, L, L, I, I, I, I, I, P, P, P, P, P, P],
-    "ccd_psnr_ws_doubles": [I, I, I, I],
-    "ccd_psnr_fwd": [P, L, L, P, L, L, I, I, I, I, P, P, P, P],
-    "ccd_l2norm_fwd": [P, P, P, I, P, I, I, P],
-    "ccd_l2norm_bwd": [P, P, P, P, I, P, I, I, P],
-    "ccd_weightnorm_fwd": [P, P, P, P, P, I, I, P],
-    "ccd_weightnorm_bwd": [P, P, P, P, P, P, I, I, P],
-    "ccd_dino_loss_fwd": [P, P, P, I, P, I, F, F, P, P, P],
-    "ccd_dino_loss_bwd": [P, P, P, I, P, I, F, F, P, F, P, P, P],
-    "ccd_head_loss_ws_floats": [I, I],
-    "ccd_head_loss_fwd": [P, L, P, L, P, L, P, L, P, I, I, P, I, F, F, P, P, P, P],
-    "ccd_head_loss_bwd": [P, L, P, L, P, L, P, L, P, I, I, P, I, F, F, P, F, P, P, L, P],
-    "ccd_colsum_f32": [P, I, P, I, I, P, P],
-    "ccd_matvec_bf16": [P, L, P, I, I, P, P],
-    "ccd_center_ema": [P, P, I, P, I, F, P],
-    "ccd_seg_loss": [P, P, P, I, F, P, P, P],
-    "ccd_seg_sumsq": [P, P, P, P, I, P, P],
-    "ccd_adamw": [P, P, P, P, P, P, P, P, I, P, P, F, F, F, F, P],
-    "ccd_seg_moments": [P, P, P, P, P, I, P, P],
-    "ccd_sgd_momentum": [P, P, P, P, P, P, P, I, P, P, F, F, P],
-    "ccd_lars": [P, P, P, P, P, P, P, I, P, P, F, F, F, P],
-    "ccd_clip_scale": [P, P, P, P, I, P, F, P],
-    "ccd_ema": [P, P, P, L, F, F, P, P],
-    "ccd_conv_gemm": [P, L, P, P, L, I, I, P, L, P, P, P, P],
-    "ccd_conv_wgrad": [P, L, I, P, L, P, L, P, L, P],
-    "ccd_im2col": [P, L, P, L, P, P],
-    "ccd_bn_finalize": [P, F, F, F, P, P, P, I, P],
-    "ccd_bn_relu_fwd": [P, L, P, P, P, P, L, L, I, P],
-    "ccd_bn_relu_bwd_reduce": [P, L, P, L, P, P, P, P, L, I, P],
-    "ccd_bn_relu_bwd_apply": [P, L, P, L, P, P, P, P, F, P, P, P, P, L, L, I, P],
-    "ccd_cls_gather_fwd": [P, L, P, P, I, I, I, P],
-    "ccd_cls_grad_cols": [P, P, I, I, I, P],
-    "ccd_cls_tail_fwd": [P, L, P, P, P, P, P, P, I, I, I, I, P],
-    "ccd_cls_tail_bwd_reduce": [P, P, L, P, P, P, P, P, P, I, I, I, I, P],
-    "ccd_cls_tail_bwd_apply": [P, P, L, P, P, P, P, P, F, P, P, P, P, P, P, L, I, I, I, I, P],
-    "ccd_permute4": [P, P, P, P, P, I, P],
-    "ccd_permute4_multi": [P, I, I, P],
-    "ccd_bn_finalize_multi": [P, I, P],
-    "ccd_dropout": [P, I, P, P, I, L, U64, F, P],
-    "ccd_droppath_scales": [P, P, I, I, U64, P, P],
-    "ccd_dec_embed_fwd": [P, P, P, P, I, I, I, I, U64, F, P],
-    "ccd_dec_embed_bwd": [P, P, P, I, I, I, I, U64, F, P],
-    "ccd_dec_attn_fwd": [P, L, P, L, P, L, P, L, P, P, P, P, I, I, I, I, I, I, F, U64, F, P],
-    "ccd_dec_attn_bwd": [P, L, P, L, P, L, P, P, L, P, P, P, I, I, I, I, I, I, F, U64, F, P, L, P, L, P, L, P],
-    "ccd_tf_loss_fwd": [P, L, I, P, I, I, I, P, P, P],
-    "ccd_tf_loss_bwd": [P, L, I, P, I, I, I, P, P, P, P, L, P],
-    "ccd_greedy_step": [P, L, I, I, P, I, I, P, I, P],
-}
-_RESTYPES = {"ccd_build_info": C.c_char_p, "ccd_attention_bwd_ws_floats": L, "ccd_gemm_tn_pair_ws_floats": L, "ccd_head_loss_ws_floats": L,
-             "ccd_ssim_ws_doubles": L, "ccd_psnr_ws_doubles": L}
+_SCALARS = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "uint64_t": C.c_uint64, "const char*": C.c_char_p}
+_RETURNS = {"int": C.c_int, "long": C.c_long, "const char*": C.c_char_p}
+# element type of a pointer parameter -> the tensor dtypes it takes (None: untyped, any dtype)
+_ELEMENT_DTYPES = {"float": (torch.float32,), "ccd_bf16": (torch.bfloat16,), "uint16_t": (torch.float16,), "double": (torch.float64,),
+                   "int": (torch.int32,), "long": (torch.int64,), "int64_t": (torch.int64,), "uint64_t": (torch.int64, torch.uint64),
+                   "uint8_t": (torch.uint8,), "void": None}
+
+
+def _pointer_type(elem, dtypes):
+    """The argtype of an `elem*` parameter.  It takes None (NULL), an int (a raw address), a ctypes array / structure / pointer, or a
+    tensor: its data_ptr(), provided the dtype is the header's and the innermost dimension is dense."""
+    want = " or ".join(str(d)[6:] for d in dtypes) if dtypes else ""
+
+    def from_param(cls, v):
+        if isinstance(v, torch.Tensor):
+            if dtypes is not None and v.dtype not in dtypes:
+                raise TypeError(f"expects {want}, got {str(v.dtype)[6:]}")
+            if not v.is_contiguous() and v.stride(-1) != 1 and v.shape[-1] > 1:      # (one call for the usual, dense tensor)
+                raise ValueError("innermost dimension must be contiguous")
+            return C.c_void_p(v.data_ptr())
+        if v is None:
+            return None
+        return C.byref(v) if isinstance(v, C.Structure) else C.c_void_p.from_param(v)
+
+    return type(f"{elem}_p", (), {"elem": elem, "dtypes": dtypes, "from_param": classmethod(from_param)})
+
+
+def parse_header(text):
+    """name -> (restype, [(argtype, parameter name)]) of every ccd_* prototype of include/ccd_hip.h.  Anything the tables above do not
+    know is an error here, at import: a guessed argument type would corrupt a stride or a pointer on the device."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$|extern\s+\"C\"\s*\{", " ", text, flags=re.M)
+    pointers = dict(_ELEMENT_DTYPES)
+    for name in re.findall(r"typedef\s+struct[^{;]*\{[^}]*\}\s*(\w+)\s*;", text):
+        pointers[name] = None                                    # descriptor structs: host or device memory, no dtype
+    text = re.sub(r"typedef\s+struct[^{;]*\{[^}]*\}\s*\w+\s*;|typedef[^;{]*;", " ", text)
+    pointers = {elem + "*": _pointer_type(elem, dtypes) for elem, dtypes in pointers.items()}
+
+    def ctype(decl, table, where):
+        decl = re.sub(r"\s*\*", "*", " ".join(decl.split()))
+        if decl not in table and decl.removeprefix("const ") not in table:
+            raise ImportError(f"ccd_amd: include/ccd_hip.h: no ctypes mapping for '{decl}' in {where}")
+        return table[decl] if decl in table else table[decl.removeprefix("const ")]
+
+    protos = {}
+    for stmt in text.replace("}", " ").split(";"):               # (the brace that closes extern "C")
+        if not stmt.strip():
+            continue
+        m = re.fullmatch(r"\s*([\w\s\*]+?)\s*\b(ccd_\w+)\s*\(([^()]*)\)\s*", stmt)
+        if m is None:
+            raise ImportError(f"ccd_amd: include/ccd_hip.h: cannot parse '{' '.join(stmt.split())}'")
+        ret, name, params = m.groups()
+        args = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            decl, pname = re.fullmatch(r"\s*(.*?)(\w+)\s*", p, flags=re.S).groups()
+            args.append((ctype(decl, {**_SCALARS, **pointers}, f"{name}({pname})"), pname))
+        protos[name] = (ctype(ret, _RETURNS, name), args)
+    return protos
+
+
+with open(HEADER_PATH) as _f:
+    PROTOTYPES = parse_header(_f.read())
+SIGNATURES = {name: [t for t, _ in args] for name, (_, args) in PROTOTYPES.items()}       # name -> argtypes
 
 
 def bind(lib: C.CDLL) -> C.CDLL:
     """Attach argtypes/restypes; raises AttributeError if the library lacks a declared symbol."""
-    for name, argtypes in SIGNATURES.items():
+    for name, (restype, _) in PROTOTYPES.items():
         fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name, I)
+        fn.argtypes = SIGNATURES[name]
+        fn.restype = restype
     return lib
+
+
+def argument_error(name, err):
+    """ctypes.ArgumentError of a call of `name` -> the TypeError / ValueError a pointer type raised, naming the header's parameter."""
+    m = re.fullmatch(r"argument (\d+): (\w+): (.*)", str(err), flags=re.S)
+    kind = {"TypeError": TypeError, "ValueError": ValueError}.get(m.group(2)) if m else None
+    if kind is None:
+        return err
+    return kind(f"{name}: {PROTOTYPES[name][1][int(m.group(1)) - 1][1]} {m.group(3)}")
 
 
 def get() -> C.CDLL:

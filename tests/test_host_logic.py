@@ -14,6 +14,32 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 
+# argument kinds and return kind of include/ccd_hip.h, copied by hand (const dropped): what the header parser of ccd_amd/_lib.py must read
+PINNED_PROTOTYPES = {
+    "ccd_gemm_nt": ("int", "ccd_bf16* long ccd_bf16* long int int int int void* long void* long float* float* long float* int ccd_bf16* long "
+                           "float int int* int float* void*"),
+    "ccd_proj_mlp_fused_gact": ("int", "ccd_bf16* long ccd_bf16* long float* float* long "
+                                       "float* float* float* float* long ccd_bf16* "
+                                       "long float* float* ccd_bf16* long float* ccd_bf16* "
+                                       "long float* float* int float* long "
+                                       "float* float* float ccd_bf16* long float* "
+                                       "float* ccd_bf16* long ccd_bf16* long float* float* ccd_bf16* long "
+                                       "int int int void*"),
+    "ccd_dropout": ("int", "void* int float* void* int long uint64_t float void*"),
+    "ccd_droppath_scales": ("int", "float* float* int int uint64_t uint64_t* void*"),
+    "ccd_policy_get": ("int", "char* int*"),
+    "ccd_build_info": ("char*", ""),
+    "ccd_abi_version": ("int", ""),
+    "ccd_attention_bwd_ws_floats": ("long", "int int"),
+    "ccd_ssim_fwd": ("int", "float* long long float* long long float* long long int int int int int float* double* void*"),
+    "ccd_kmeans2_mask": ("int", "uint8_t* long* int* uint8_t* int void*"),
+    "ccd_dec_embed_fwd": ("int", "int64_t* float* float* float* int int int int uint64_t float void*"),
+    "ccd_augment_views": ("int", "uint8_t* float* float* float* uint8_t* int int int float* float* uint16_t* int float* int void*"),
+    "ccd_conv_gemm": ("int", "ccd_bf16* long ccd_conv_desc* ccd_bf16* long int int ccd_bf16* long float* float* float* void*"),
+    "ccd_adamw": ("int", "float* float* float* float* ccd_bf16* int* long* int* int ccd_seg_hyper* float* float float float float void*"),
+}
+
+
 def test_c_abi_library_exports_every_declared_symbol():
     from ccd_amd import _lib
     header = open(os.path.join(ROOT, "include", "ccd_hip.h")).read()
@@ -23,12 +49,42 @@ def test_c_abi_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_lib.LIB_PATH)            # loads without a GPU; no compute call is made here
     missing = [n for n in declared if not hasattr(lib, n)]
     assert not missing, missing
-    assert sorted(_lib.SIGNATURES) == declared, "ccd_amd/_lib.py signature table out of sync with include/ccd_hip.h"
+    # the table is parsed from the header: the parser must find exactly these prototypes, and read the pinned ones as written below
+    assert sorted(_lib.SIGNATURES) == declared == sorted(_lib.PROTOTYPES), "ccd_amd/_lib.py misses prototypes of include/ccd_hip.h"
+    scalars = {ctypes.c_int: "int", ctypes.c_long: "long", ctypes.c_float: "float", ctypes.c_uint64: "uint64_t",
+               ctypes.c_char_p: "char*"}
+    for name, (ret, args) in PINNED_PROTOTYPES.items():
+        restype, params = _lib.PROTOTYPES[name]
+        got = [scalars[t] if t in scalars else t.elem + "*" for t, _ in params]
+        assert got == args.split(), (name, got)
+        assert [t for t, _ in params] == _lib.SIGNATURES[name] and scalars[restype] == ret, name
+    assert [n for _, n in _lib.PROTOTYPES["ccd_gemm_nt"][1]] == (
+        "A lda B ldb M N K epilogue C ldc C2 ldc2 bias resid ldr rowscale rows_per_sample aux ldaux alpha m_fastest d_rows rows_mul colsum "
+        "stream").split()
     _lib.bind(lib)
+    assert lib.ccd_gemm_nt.argtypes == _lib.SIGNATURES["ccd_gemm_nt"] and lib.ccd_build_info.restype is ctypes.c_char_p
+    assert lib.ccd_attention_bwd_ws_floats.restype is ctypes.c_long and lib.ccd_policy_get.restype is ctypes.c_int
     # the library on disk was built from THESE sources (a stale in-tree .so would carry the previous number)
     src = open(os.path.join(ROOT, "ccd_amd", "csrc", "abi_impl.h")).read()
     want = int(re.search(r"int ccd_abi_version\(void\) \{ return (\d+); \}", src).group(1))
     assert want >= 11 and lib.ccd_abi_version() == want
+
+
+def test_header_parser_refuses_what_it_does_not_know():
+    """An unknown scalar, element or return type, or a statement that is no prototype, is an error that names it - never a guess."""
+    from ccd_amd import _lib
+    ok = _lib.parse_header("/* c */ typedef struct { int a; float* b; } ccd_job;\n"
+                           "long ccd_f(const ccd_job* jobs /* host */, const float* x, uint64_t seed, void* stream);\nint ccd_g(void);")
+    assert sorted(ok) == ["ccd_f", "ccd_g"] and ok["ccd_g"] == (ctypes.c_int, []) and ok["ccd_f"][0] is ctypes.c_long
+    assert [(t.elem, t.dtypes) if hasattr(t, "elem") else t for t, _ in ok["ccd_f"][1]] == [
+        ("ccd_job", None), ("float", (torch.float32,)), ctypes.c_uint64, ("void", None)]
+    assert [n for _, n in ok["ccd_f"][1]] == ["jobs", "x", "seed", "stream"]
+    for bad, named in (("int ccd_f(short n, void* stream);", "ccd_f(n)"), ("int ccd_f(const short* p);", "ccd_f(p)"),
+                       ("int ccd_f(unsigned n);", "ccd_f(n)"), ("int ccd_f(ccd_other* p);", "ccd_f(p)"),
+                       ("double ccd_f(int n);", "ccd_f"), ("float* ccd_f(int n);", "ccd_f"), ("int ccd_f(int n) { return n; }", "ccd_f")):
+        with pytest.raises(ImportError) as e:
+            _lib.parse_header(bad)
+        assert named in str(e.value), (bad, str(e.value))
 
 
 def test_product_has_no_cpu_fallback():
