@@ -1,7 +1,7 @@
 """`Dino.*` import paths of the reference (TongkunGuan/CCD) mapped onto the MI355X-native implementation in
 `ccd_amd`, so `from Dino.modules import vision_transformer as vits`, `from Dino.model.dino_vision import
 ABIDINOModel`, `from Dino.loss.Dino_loss import DINOLoss`, `from Dino.utils.utils import Config`,
-`from Dino.utils.DBSCAN import label_cluster`, `from Dino.metric.eval_superpixel import SSIM` keep working.
+`from Dino.utils.DBSCAN import label_cluster`, `from Dino.metric.eval_superpixel import SSIM`, `from Dino.metric.eval_IOU import fore_IU` keep working.
 The pretraining path and the finetune path (8f row 1: DINO_Finetune, NRTRDecoder, TFLoss,
 AttnConvertor) exist here."""
 import importlib
@@ -24,6 +24,7 @@ _ALIASES = {
     "Dino.metric": "ccd_amd.metric",
     "Dino.metric.eval_acc": "ccd_amd.metric.eval_acc",
     "Dino.metric.eval_superpixel": "ccd_amd.metric.eval_superpixel",
+    "Dino.metric.eval_IOU": "ccd_amd.metric.eval_IOU",
     "Dino.dataset": "ccd_amd.dataset",
     "Dino.dataset.dataset_pretrain": "ccd_amd.dataset.dataset_pretrain",
     "Dino.dataset.datasetsupervised_kmeans": "ccd_amd.dataset.datasetsupervised_kmeans",

@@ -21,6 +21,7 @@
 #include "kernels/charmap.h"
 #include "kernels/cluster.h"
 #include "kernels/ssim.h"
+#include "kernels/segmetric.h"
 #include "kernels/datapipe.h"
 #include "kernels/embed.h"
 #include "kernels/head.h"
@@ -277,9 +278,64 @@ static int ccd_launch_tn384_geom(ccd::GemmParams& p, int Mc, float* ws, long ws_
     return ccd_rt_last_error();
 }
 
+// ------------------------------------------------------------------------------- Dino/metric/eval_IOU.py metrics: launchers
+static_assert(CCD_SEG_CLASSES == ccd::SEG_CLASSES, "");
+static int ccd_seg_elem_bytes(int dtype) {
+    switch (dtype) {
+        case CCD_SEG_U8: return 1;
+        case CCD_SEG_I32: case CCD_SEG_F32: return 4;
+        case CCD_SEG_I64: return 8;
+        default: return 0;
+    }
+}
+// may P elements at a time be loaded from every image of a map?  (16-byte loads, or one 4-byte load for four uint8)
+static bool ccd_seg_vec_ok(const void* p, long stride, int images, int elem_bytes, int P) {
+    const long align = P * elem_bytes < 16 ? P * elem_bytes : 16;
+    return ((uintptr_t)p) % align == 0 && (images == 1 || (stride * elem_bytes) % align == 0);
+}
+// (the chunks start at multiples of SEG_CHUNK elements, which keeps an image's alignment)
+template <typename Src, typename TG, int P>
+static void ccd_seg_launch(const Src& ev, const void* gt, long gt_stride, int images, int pixels, int chunks, int* cm, int* status,
+                           void* stream) {
+    const ccd::SegMapSrc<TG> g = {static_cast<const TG*>(gt), gt_stride, ccd_seg_vec_ok(gt, gt_stride, images, (int)sizeof(TG), P) ? 1 : 0};
+    CCD_LAUNCH((ccd::seg_confusion_kernel<Src, TG, P>), dim3((unsigned)((long)images * chunks)), dim3(ccd::SEG_THREADS), 0, stream, ev,
+               g, pixels, chunks, cm, status);
+}
+template <typename Src>
+static int ccd_seg_launch_gt(const Src& ev, const void* gt, int gt_dtype, long gt_stride, int images, int pixels, int chunks, int* cm,
+                             int* status, void* stream) {
+    switch (gt_dtype) {
+        case CCD_SEG_U8: ccd_seg_launch<Src, unsigned char, 4>(ev, gt, gt_stride, images, pixels, chunks, cm, status, stream); break;
+        case CCD_SEG_I32: ccd_seg_launch<Src, int, 4>(ev, gt, gt_stride, images, pixels, chunks, cm, status, stream); break;
+        case CCD_SEG_I64: ccd_seg_launch<Src, long long, 4>(ev, gt, gt_stride, images, pixels, chunks, cm, status, stream); break;
+        case CCD_SEG_F32: ccd_seg_launch<Src, float, 4>(ev, gt, gt_stride, images, pixels, chunks, cm, status, stream); break;
+        default: return CCD_ESHAPE;
+    }
+    return ccd_rt_last_error();
+}
+template <typename TE>
+static int ccd_seg_launch_eval(const void* eval, long eval_stride, const void* gt, int gt_dtype, long gt_stride, int images, int pixels,
+                               int chunks, int* cm, int* status, void* stream) {
+    const ccd::SegMapSrc<TE> ev = {static_cast<const TE*>(eval), eval_stride, ccd_seg_vec_ok(eval, eval_stride, images, (int)sizeof(TE), 4) ? 1 : 0};
+    return ccd_seg_launch_gt(ev, gt, gt_dtype, gt_stride, images, pixels, chunks, cm, status, stream);
+}
+// shape checks shared by the two entry points; clears cm and status when the images are split over several workgroups
+static int ccd_seg_prepare(int images, long pixels, int* cm, int* status, int* chunks, void* stream) {
+    CCD_CHECK(pixels >= 1 && pixels < (1L << 31), CCD_ESHAPE);
+    const long c = (pixels + ccd::SEG_CHUNK - 1) / ccd::SEG_CHUNK;
+    CCD_CHECK((long)images * c <= 0x7fffffffL, CCD_ESHAPE);
+    *chunks = (int)c;
+    if (c > 1) {
+        int rc = ccd_rt_memset_async(cm, 0, (size_t)images * ccd::SEG_BINS * sizeof(int), stream);
+        if (rc == 0) rc = ccd_rt_memset_async(status, 0, (size_t)images * sizeof(int), stream);
+        return rc;
+    }
+    return CCD_OK;
+}
+
 extern "C" {
 
-int ccd_abi_version(void) { return 16; }   // 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
+int ccd_abi_version(void) { return 17; }   // 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
 const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi16"; }
 int ccd_policy_set(const char* key, int value) {
     CCD_CHECK(key, CCD_EINVAL);
@@ -1184,6 +1240,52 @@ int ccd_psnr_fwd(const float* a, long an, long ac, const float* b, long bn, long
     return ccd_rt_last_error();
 }
 #undef CCD_SSIM_R_SWITCH
+
+// ------------------------------------------------------------------------------- Dino/metric/eval_IOU.py metrics (launchers: above)
+int ccd_seg_confusion(const void* eval, int eval_dtype, long eval_stride, const void* gt, int gt_dtype, long gt_stride, int images,
+                      long pixels, int* cm, int* status, void* stream) {
+    CCD_CHECK(images >= 0, CCD_EINVAL);
+    if (images == 0) return CCD_OK;
+    CCD_CHECK(eval && gt && cm && status && eval_stride >= 0 && gt_stride >= 0, CCD_EINVAL);
+    CCD_CHECK(ccd_seg_elem_bytes(eval_dtype) && ccd_seg_elem_bytes(gt_dtype), CCD_ESHAPE);
+    int chunks;
+    const int rc = ccd_seg_prepare(images, pixels, cm, status, &chunks, stream);
+    if (rc != CCD_OK) return rc;
+    const int px = (int)pixels;
+    if (eval_dtype == CCD_SEG_U8 && gt_dtype == CCD_SEG_U8 && ccd_seg_vec_ok(eval, eval_stride, images, 1, 16) &&
+        ccd_seg_vec_ok(gt, gt_stride, images, 1, 16)) {                // two byte maps: 16 pixels per lane and load
+        const ccd::SegMapSrc<unsigned char> ev = {static_cast<const unsigned char*>(eval), eval_stride, 1};
+        ccd_seg_launch<ccd::SegMapSrc<unsigned char>, unsigned char, 16>(ev, gt, gt_stride, images, px, chunks, cm, status, stream);
+        return ccd_rt_last_error();
+    }
+    switch (eval_dtype) {
+        case CCD_SEG_U8: return ccd_seg_launch_eval<unsigned char>(eval, eval_stride, gt, gt_dtype, gt_stride, images, px, chunks, cm, status, stream);
+        case CCD_SEG_I32: return ccd_seg_launch_eval<int>(eval, eval_stride, gt, gt_dtype, gt_stride, images, px, chunks, cm, status, stream);
+        case CCD_SEG_I64: return ccd_seg_launch_eval<long long>(eval, eval_stride, gt, gt_dtype, gt_stride, images, px, chunks, cm, status, stream);
+        default: return ccd_seg_launch_eval<float>(eval, eval_stride, gt, gt_dtype, gt_stride, images, px, chunks, cm, status, stream);
+    }
+}
+int ccd_seg_confusion_logits(const float* logits, long image_stride, long channel_stride, int classes, const void* gt, int gt_dtype,
+                             long gt_stride, int images, long pixels, int* cm, int* status, void* stream) {
+    CCD_CHECK(images >= 0, CCD_EINVAL);
+    if (images == 0) return CCD_OK;
+    CCD_CHECK(logits && gt && cm && status && image_stride >= 0 && channel_stride >= 0 && gt_stride >= 0, CCD_EINVAL);
+    CCD_CHECK(ccd_seg_elem_bytes(gt_dtype) && classes >= 2 && classes <= ccd::SEG_CLASSES, CCD_ESHAPE);
+    int chunks;
+    const int rc = ccd_seg_prepare(images, pixels, cm, status, &chunks, stream);
+    if (rc != CCD_OK) return rc;
+    const int vec = ccd_seg_vec_ok(logits, image_stride, images, 4, 4) && (channel_stride * 4) % 16 == 0;
+    const ccd::SegLogitSrc ev = {logits, image_stride, channel_stride, classes, vec};
+    return ccd_seg_launch_gt(ev, gt, gt_dtype, gt_stride, images, (int)pixels, chunks, cm, status, stream);
+}
+int ccd_seg_scores(const int* cm, int* status, int images, double* scores, void* stream) {
+    CCD_CHECK(images >= 0, CCD_EINVAL);
+    if (images == 0) return CCD_OK;
+    CCD_CHECK(cm && status && scores, CCD_EINVAL);
+    CCD_LAUNCH(ccd::seg_scores_kernel, dim3((unsigned)((images + ccd::SEG_WAVES - 1) / ccd::SEG_WAVES)), dim3(ccd::SEG_THREADS), 0, stream,
+               cm, status, images, scores);
+    return ccd_rt_last_error();
+}
 
 // ------------------------------------------------------------------------------- DINO head pieces
 int ccd_l2norm_fwd(const ccd_bf16* x, ccd_bf16* y, float* inv, int max_rows, const int* d_rows, int rows_mul, int D,

@@ -691,6 +691,77 @@ def psnr_fwd(a, b):
     return psnr, mse
 
 
+# ------------------------------------------------------------------------------------------ Dino/metric/eval_IOU.py metrics
+SEG_CLASSES = 32             # labels are integers in [0, 32) (ccd_hip.h: CCD_SEG_CLASSES)
+SEG_CHUNK = 4096             # pixels of one image per workgroup (segmetric.h: SEG_CHUNK); larger images are split
+SEG_WAVE_PIXELS = (256, 1024)    # pixels a wavefront loads per step: 4 per lane, 16 per lane for two aligned uint8 maps
+SEG_SCORES = ("pixel_accuracy", "mean_accuracy", "mean_IU", "fore_IU", "frequency_weighted_IU")
+SEG_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.int64: 2, torch.float32: 3}      # ccd_hip.h: CCD_SEG_U8 ..
+
+
+def _seg_map(x, name):
+    """A label map [B, H, W] (or [B, pixels]) -> (tensor read in place, dtype code, image stride, pixels).  bool goes through a
+    uint8 view; the pixels of an image must be contiguous (a copy is made otherwise), the image stride is free."""
+    if x.dtype == torch.bool:
+        x = x.view(torch.uint8)
+    if x.dtype not in SEG_DTYPES:
+        raise TypeError(f"{name}: label maps are uint8, bool, int32, int64 or float32, got {str(x.dtype)[6:]}")
+    if x.dim() not in (2, 3):
+        raise ValueError(f"{name}: expects [B, H, W] label maps, got {list(x.shape)}")
+    pixels = x[0].numel() if x.shape[0] else math.prod(x.shape[1:])
+    if x.shape[0] and not x[0].is_contiguous():
+        x = x.contiguous()
+    return x, SEG_DTYPES[x.dtype], (x.stride(0) if x.shape[0] > 1 else pixels), pixels
+
+
+def _seg_outputs(images, dev):
+    return (torch.empty((images, SEG_CLASSES, SEG_CLASSES), dtype=I32, device=dev), torch.empty((images,), dtype=I32, device=dev))
+
+
+def seg_confusion(eval_segm, gt_segm):
+    """Label maps [B, H, W] -> (cm int32 [B, 32, 32] with cm[i, g, e] = pixels of gt label g and eval label e, status int32 [B]:
+    bit 0 = a label outside [0, 32) / not integral / NaN, not counted)."""
+    e, ecode, estride, pixels = _seg_map(eval_segm, "seg_confusion(eval)")
+    g, gcode, gstride, gpixels = _seg_map(gt_segm, "seg_confusion(gt)")
+    if e.shape[0] != g.shape[0] or pixels != gpixels:
+        raise ValueError(f"seg_confusion: the maps differ in shape: {list(eval_segm.shape)} and {list(gt_segm.shape)}")
+    cm, status = _seg_outputs(e.shape[0], e.device)
+    if e.shape[0]:
+        _call("ccd_seg_confusion", e, ecode, estride, g, gcode, gstride, e.shape[0], pixels, cm, status)
+    return cm, status
+
+
+def seg_confusion_logits(logits, gt_segm):
+    """The same with eval = argmax over the channels of fp32 logits [B, C, H, W] (2 <= C <= 32, first maximum), read in place:
+    image and channel strides are free, the pixels of a channel contiguous."""
+    if logits.dtype != F32:
+        raise TypeError(f"seg_confusion_logits: logits must be float32, got {str(logits.dtype)[6:]}")
+    if logits.dim() not in (3, 4) or not 2 <= logits.shape[1] <= SEG_CLASSES:
+        raise ValueError(f"seg_confusion_logits: expects [B, C, H, W] logits with 2 <= C <= {SEG_CLASSES}, got {list(logits.shape)}")
+    g, gcode, gstride, pixels = _seg_map(gt_segm, "seg_confusion_logits(gt)")
+    B, C = logits.shape[:2]
+    if B != g.shape[0] or math.prod(logits.shape[2:]) != pixels:
+        raise ValueError(f"seg_confusion_logits: logits {list(logits.shape)} do not match the gt maps {list(gt_segm.shape)}")
+    if B and not logits[0, 0].is_contiguous():
+        logits = logits.contiguous()
+    cm, status = _seg_outputs(B, logits.device)
+    if B:
+        _call("ccd_seg_confusion_logits", logits, logits.stride(0) if B > 1 else C * pixels, logits.stride(1), C, g, gcode, gstride, B,
+              pixels, cm, status)
+    return cm, status
+
+
+def seg_scores(cm, status):
+    """cm int32 [B, 32, 32], status int32 [B] (updated in place: bit 1 = fore_IU undefined) -> scores fp64 [B, 5] in the order of
+    SEG_SCORES; NaN where undefined."""
+    assert cm.dtype == I32 and cm.is_contiguous() and tuple(cm.shape[1:]) == (SEG_CLASSES, SEG_CLASSES)
+    assert status.dtype == I32 and status.is_contiguous() and tuple(status.shape) == (cm.shape[0],)
+    scores = torch.empty((cm.shape[0], len(SEG_SCORES)), dtype=F64, device=cm.device)
+    if cm.shape[0]:
+        _call("ccd_seg_scores", cm, status, cm.shape[0], scores)
+    return scores
+
+
 class SsimFn(torch.autograd.Function):
     """apply(window, taps, size_average, img1, img2[, img3]) -> mean (0-dim) or per-image means [N]; backward on the kernels."""
 

@@ -360,6 +360,35 @@ long ccd_psnr_ws_doubles(int images, int channels, int H, int W);
 int ccd_psnr_fwd(const float* a, long an, long ac, const float* b, long bn, long bc, int images, int channels, int H, int W,
                  double* partials, double* mse, float* psnr, void* stream);
 
+/* ---------------------------------------------------------------- the segmentation metrics of Dino/metric/eval_IOU.py
+ * Labels are integers in [0, CCD_SEG_CLASSES).  A label map is [images, pixels] with the pixels of an image contiguous and a free
+ * image stride in elements (>= 0), so x[:, 0] and out[:B] views are read in place; its element type is a dtype code: uint8, int32,
+ * int64 or fp32 holding integral values.  16-byte loads (4-byte loads for uint8 beside a wider map) are used where the base and
+ * the image stride are aligned for them, element loads otherwise.  The caller allocates everything; the calls clear what they
+ * write.  images == 0 is a no-op.  CCD_EINVAL: a missing pointer or a negative stride; CCD_ESHAPE: pixels < 1, pixels >= 2^31,
+ * an unknown dtype code, classes outside 2..32.  Counts are integers and integer adds commute: results are bitwise repeatable
+ * and an image's values do not depend on the rest of the batch. */
+#define CCD_SEG_CLASSES 32
+#define CCD_SEG_U8 0
+#define CCD_SEG_I32 1
+#define CCD_SEG_I64 2
+#define CCD_SEG_F32 3
+/* cm int32 [images, 32, 32]: cm[i, g, e] = the pixels of image i with gt label g and eval label e; status int32 [images]: bit 0 =
+ * the image has a label outside [0, 32), a non-integral value or a NaN (those pixels are not counted).  An image of at most 4096
+ * pixels is one workgroup; a larger one is split over several that add their non-zero bins with integer atomics. */
+int ccd_seg_confusion(const void* eval, int eval_dtype, long eval_stride, const void* gt, int gt_dtype, long gt_stride, int images,
+                      long pixels, int* cm, int* status, void* stream);
+/* the same with eval = the arg-max over `classes` (2..32) channels of fp32 logits [images, classes, pixels] (image and channel
+ * strides in elements, pixels contiguous); the first maximum wins as in torch.argmax (two classes: logit1 > logit0, which is
+ * ccd_seg_to_mask's rule); a NaN logit sets status bit 0.  The logits are read once, the prediction is never written. */
+int ccd_seg_confusion_logits(const float* logits, long image_stride, long channel_stride, int classes, const void* gt, int gt_dtype,
+                             long gt_stride, int images, long pixels, int* cm, int* status, void* stream);
+/* cm, status -> scores fp64 [images, 5] = pixel_accuracy, mean_accuracy, mean_IU, fore_IU, frequency_weighted_IU
+ * (eval_IOU.py:4-137; t_c / n_c / d_c = row sum / column sum / diagonal of cm, class sums in ascending class order in fp64).
+ * Sets status bit 1 where fore_IU is undefined (fewer than two classes in the union of the two maps): that column is NaN.  An
+ * image with status bit 0 gets five NaNs. */
+int ccd_seg_scores(const int* cm, int* status, int images, double* scores, void* stream);
+
 /* ---------------------------------------------------------------- DINOHead pieces, vit.py:313,326 */
 int ccd_l2norm_fwd(const ccd_bf16* x, ccd_bf16* y, float* inv, int max_rows, const int* d_rows, int rows_mul, int D,
                    void* stream);

@@ -6,7 +6,7 @@ with the stub third-party modules of tools/oracle_stubs/ and its pretraining ite
 is re-enacted by this harness; nothing from the reference is copied - only its numerical outputs for our
 seeded synthetic inputs (ccd_amd/synthetic.py) are recorded.
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py [--only ccl|cluster|superpixel|tiny|small|sched]
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py [--only ccl|cluster|superpixel|iou|tiny|small|sched]
 
 Fixtures (all small):
   sched.npz        cosine_iter_scheduler / teacher-temp schedule arrays           (modules/utils.py:200-210)
@@ -14,6 +14,7 @@ Fixtures (all small):
   cluster_cases.npz  masks -> DBSCAN_cluster / label_cluster / region_cluster planes (packbits)  (utils/DBSCAN.py:10-141)
   superpixel_cases.npz  8-bit images -> ssim / SSIM / TRI_SSIM / calculate_psnr values, their input gradients and the
                    gaussian / create_window values  (metric/eval_superpixel.py)
+  iou_cases.npz    uint8 label-map pairs -> the five segmentation scores, class lists and the module's public names  (metric/eval_IOU.py)
   tiny_step.npz    3-block E=192 model, B=2: full tensors of every stage + grads (tiny8_step.npz: the same at B=8)
   arch_step.npz    BASELINE config #4's two architectures (vit_base = 512 / 8 heads, the 768 / 12 shape): one iteration each, B = 4
   small_step.npz   CCD_pretrain_ViT_small hyper-parameters, B=8, 2 iterations: losses, index maps,
@@ -1075,6 +1076,79 @@ def gen_selfattn():
           f"max {float(mx.max()):.4f}")
 
 
+def iou_cases():
+    """name -> (eval, gt) uint8 [H, W] label maps for Dino/metric/eval_IOU.py."""
+    rs = np.random.RandomState(77)
+
+    def flipped(gt, share, classes):
+        redraw = rs.rand(*gt.shape) < share
+        return np.where(redraw, rs.randint(0, classes, size=gt.shape), gt).astype(np.uint8)
+
+    binary_gt = (rs.rand(32, 128) < 0.3).astype(np.uint8)
+    binary_ev = np.where(rs.rand(32, 128) < 0.1, 1 - binary_gt, binary_gt).astype(np.uint8)            # 10 % of the pixels flipped
+    _, masks, _ = make_text_like_batch(1, seed=5)
+    text_gt = (masks[0].numpy() > 0).astype(np.uint8)
+    text_ev = (np.roll(text_gt, 1, axis=1) & (rs.rand(32, 128) > 0.05)).astype(np.uint8)
+    three_gt = np.zeros((32, 128), np.uint8)
+    three_gt[8:24, 20:60] = 2                                                       # class 2: gt only
+    three_ev = np.zeros((32, 128), np.uint8)
+    three_ev[10:26, 24:70] = 1                                                      # class 1: eval only
+    many_gt = rs.randint(0, 27, size=(32, 128)).astype(np.uint8)
+    hi_gt = np.where(rs.rand(32, 128) < 0.4, 31, 0).astype(np.uint8)
+    single_ev, single_gt = np.zeros((32, 128), np.uint8), np.zeros((32, 128), np.uint8)
+    single_ev[17, 77] = single_gt[17, 77] = 1
+    cases = {
+        "binary_flip10": (binary_ev, binary_gt),
+        "text_like": (text_ev, text_gt),
+        "zeros_zeros": (np.zeros((32, 128), np.uint8), np.zeros((32, 128), np.uint8)),
+        "ones_zeros": (np.ones((32, 128), np.uint8), np.zeros((32, 128), np.uint8)),
+        "three_disjoint": (three_ev, three_gt),
+        "classes27": (flipped(many_gt, 0.2, 27), many_gt),
+        "labels_0_31": (np.where(rs.rand(32, 128) < 0.1, 31 - hi_gt, hi_gt).astype(np.uint8), hi_gt),
+        "single_pixel": (single_ev, single_gt),
+    }
+    for h, w in ((1, 1), (5, 7), (33, 130)):
+        gt = rs.randint(0, 3, size=(h, w)).astype(np.uint8)
+        cases[f"shape_{h}x{w}"] = (flipped(gt, 0.3, 3), gt)
+    return cases
+
+
+def gen_iou():
+    """The real Dino/metric/eval_IOU.py on the maps of iou_cases() -> iou_cases.npz: the five values (NaN + a flag where fore_IU raised
+    IndexError), the class lists of extract_classes / union_classes, and the module's public names with their parameter lists."""
+    import inspect
+    from Dino.metric import eval_IOU as R
+    fns = (R.pixel_accuracy, R.mean_accuracy, R.mean_IU, R.fore_IU, R.frequency_weighted_IU)
+    out, names = {}, []
+    for name, (ev, gt) in iou_cases().items():
+        names.append(name)
+        vals, raised = np.full(5, np.nan), False
+        for k, fn in enumerate(fns):
+            try:
+                vals[k] = fn(ev, gt)
+            except IndexError:
+                assert fn is R.fore_IU
+                raised = True
+        rec = {"eval": ev, "gt": gt, "scores": vals, "fore_raised": np.bool_(raised),
+               "eval_classes": R.extract_classes(ev)[0], "gt_classes": R.extract_classes(gt)[0], "union_classes": R.union_classes(ev, gt)[0],
+               "masks_sum": R.extract_masks(gt, *R.extract_classes(gt)).sum(axis=(1, 2))}
+        out.update({f"{name}/{k}": np.asarray(v) for k, v in rec.items()})
+    api = [f"{n}({', '.join(inspect.signature(o).parameters)})" for n, o in sorted(vars(R).items())
+           if not n.startswith("_") and (inspect.isfunction(o) or inspect.isclass(o)) and o.__module__ == R.__name__]
+    try:
+        R.check_size(np.zeros((2, 3)), np.zeros((2, 4)))
+        raise AssertionError("check_size accepted different shapes")
+    except R.EvalSegErr as e:
+        out["diffdim_message"] = np.array(str(e))
+    out["names"] = np.array(names)
+    out["api"] = np.array(api)
+    path = os.path.join(GOLD, "iou_cases.npz")
+    _savez_reproducible(path, out)
+    print(f"iou_cases.npz written: {len(names)} cases, {os.path.getsize(path)} bytes; api = {api}")
+    for n in names:
+        print(f"  {n}: {out[n + '/scores']} fore_raised={bool(out[n + '/fore_raised'])}")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
@@ -1083,8 +1157,8 @@ if __name__ == "__main__":
     os.chdir("/root/reference")  # Config() and friends use relative paths; we never write here
     torch.set_num_threads(8)
     todo = [a.only] if a.only else ["sched", "ccl", "cluster", "tiny", "small", "small3", "arch", "keys", "finetune", "kmeans", "eval", "superpixel",
-                                    "selfattn"]
+                                    "selfattn", "iou"]
     for t in todo:
         {"sched": gen_sched, "ccl": gen_ccl, "cluster": gen_cluster, "tiny": gen_tiny, "arch": gen_arch, "small": gen_small, "small3": gen_small3, "keys": gen_keys,
          "finetune": gen_finetune, "kmeans": gen_kmeans, "eval": gen_eval, "small_noise": gen_small_noise, "superpixel": gen_superpixel,
-         "selfattn": gen_selfattn}[t]()
+         "selfattn": gen_selfattn, "iou": gen_iou}[t]()
