@@ -118,6 +118,25 @@ class AttnConvertor:
         return torch.from_numpy(target)
 
     # ------------------------------------------------------------------ decode
+    def score_table(self):
+        """The classes as code points, for scoring on the device (ops.text_score): (raw, normalised) int32 [num_classes, width]
+        tables, row c = the code points of idx2char[c] as idx2str writes it / as TextAccuracy normalises it, padded with -1.  The
+        end and padding classes never reach a decoded string: their rows are empty.  None when max_seq_len steps of the longest
+        normalised row would not fit the kernel's columns (the caller scores on the host).  Built once."""
+        if not hasattr(self, "_score_table"):
+            from ..metric.eval_acc import normalise
+            from ..ops import TEXT_COLS
+            silent = {self.end_idx, self.padding_idx}
+            raw = ["" if c in silent else s for c, s in enumerate(self.idx2char)]
+            tables = []
+            for rows in (raw, [normalise(s) for s in raw]):
+                table = np.full((len(rows), max(1, max(map(len, rows)))), -1, dtype=np.int32)
+                for row, s in zip(table, rows):
+                    row[:len(s)] = np.frombuffer(s.encode("utf-32-le"), dtype="<u4")
+                tables.append(table)
+            self._score_table = tuple(tables) if self.max_seq_len * tables[1].shape[1] <= TEXT_COLS else None
+        return self._score_table
+
     @torch.no_grad()
     def tensor2idx(self, outputs, img_metas=None):
         """[N, T, C] class scores -> (class indices, softmax confidences) per sample: positions up to the first <EOS>,

@@ -9,15 +9,48 @@ Same surface and the same arithmetic as `Dino.metric.eval_acc.TextAccuracy` (ref
 * ccr: position-wise equal characters of the RAW strings over the raw ground-truth length (:53-56).
 The scoring is `update(gt_text, pt_text)`, separated from the model loop so that it can be checked against the reference's
 numbers without a model.  (`editdistance` is not in this image: the Levenshtein distance is computed here.)
+
+On a GPU `compute` scores on the device instead: `update_scores(scores, gt_text)` hands the decoder's output and the ground truth
+as code points (`encode_truth`) to ops.text_score / ops.text_accumulate - arg-max decoding, normalisation, edit distance and the
+sums in two launches per batch, no host synchronisation - and `result()` reads the six totals back in one copy.  The values are
+those of `update` on the decoded strings: the counts exactly, `ned` up to the order of its fp64 sum.  The device path needs
+`AttnConvertor.score_table()` (None when max_seq_len steps of the longest class do not fit the kernel: host path) and takes the
+first maximum of the scores themselves where `tensor2idx` takes the maximum of their softmax; the two differ only where two
+classes of a step are closer than the softmax resolves.
 """
 from __future__ import annotations
 
 import re
 import time
 
+import numpy as np
 import torch
 
+from .. import ops
+
 _KEEP = re.compile("[^A-Z^a-z^0-9^一-龥]")      # the reference's pattern, verbatim semantics: '^' itself is kept too
+
+
+def normalise(s: str) -> str:
+    """What a word is compared as: lower case, everything outside [a-z0-9^ + CJK] dropped (`update`)."""
+    return _KEEP.sub("", s.lower())
+
+
+def encode_truth(strings):
+    """['ab', 'c', ...] -> (code points int32 [B, L] zero-padded to the longest string (L >= 1), lengths int32 [B]): one encode of
+    the joined batch, no per-character Python."""
+    strings = list(strings)
+    lens = np.fromiter((len(s) for s in strings), dtype=np.int32, count=len(strings))
+    flat = np.frombuffer("".join(strings).encode("utf-32-le", "surrogatepass"), dtype="<u4").astype(np.int32)
+    codes = np.zeros((len(strings), max(1, int(lens.max(initial=0)))), dtype=np.int32)
+    codes[np.arange(codes.shape[1], dtype=np.int32)[None, :] < lens[:, None]] = flat
+    return codes, lens
+
+
+def _to_device(array, device):
+    """numpy -> device without a host synchronisation: through pinned memory, asynchronously (a CPU `device`: no copy)."""
+    t = torch.from_numpy(array)
+    return t.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else t
 
 
 def levenshtein(a: str, b: str) -> int:
@@ -42,6 +75,9 @@ class TextAccuracy:
         self._names = ["ccr", "cwr", "ted", "ned", "ted/w", "words", "time"]
         self.total_num_char = self.total_num_word = self.correct_num_char = self.correct_num_word = 0.0
         self.total_ed = self.total_ned = self.inference_time = 0.0
+        self._totals = None          # device path: int64 [6] on the device (ops.TEXT_TOTALS), read by result()
+        self._tables = None          # (convertor, device, raw table, normalised table) of the last update_scores
+        self._spans = []             # device path of compute(): (start, end) events around each batch
 
     def update(self, gt_text, pt_text):
         """Score one batch of (ground truth, prediction) strings."""
@@ -59,15 +95,59 @@ class TextAccuracy:
             self.correct_num_char += sum(1 for j in range(min(len(gt), len(pt))) if gt[j] == pt[j])
             self.total_num_char += len(gt)
 
+    def update_scores(self, scores, gt_text, convertor=None):
+        """Score one batch on the device: decoder scores fp32 [B, T, C] (a strided view is read in place) against the ground-truth
+        strings.  Nothing is read back; the totals stay on the device until result().  convertor: the model's AttnConvertor
+        (default: the one of the last call)."""
+        if self.case_sensitive:
+            raise NotImplementedError("TextAccuracy is defined for case_sensitive=False (eval_acc.py:40-46)")
+        dev = scores.device
+        if convertor is not None and (self._tables is None or self._tables[0] is not convertor or self._tables[1] != dev):
+            tables = convertor.score_table()
+            if tables is None:
+                raise ValueError("update_scores: max_seq_len steps of the convertor's longest class exceed ops.TEXT_COLS characters; "
+                                 "score on the host with update()")
+            self._tables = (convertor, dev) + tuple(_to_device(t, dev) for t in tables)
+        if self._tables is None:
+            raise ValueError("update_scores: pass the model's label convertor")
+        conv, _, raw, norm = self._tables
+        if self._totals is None:
+            self._totals = ops.text_totals(dev)
+        codes, lens = encode_truth(gt_text)
+        if len(lens) != scores.shape[0]:
+            raise ValueError(f"update_scores: {scores.shape[0]} samples but {len(lens)} ground-truth strings")
+        both = _to_device(np.concatenate([codes.ravel(), lens]), dev)         # one host-to-device copy for both
+        records = ops.text_score(scores, raw, norm, conv.end_idx, conv.padding_idx, both[:codes.size].view(codes.shape), both[codes.size:])
+        ops.text_accumulate(records, self._totals)
+        return records
+
     def result(self):
-        mets = [self.correct_num_char / self.total_num_char, self.correct_num_word / self.total_num_word, self.total_ed,
-                self.total_ned, self.total_ed / self.total_num_word, self.total_num_word, self.inference_time]
+        cc, tc, cw, words, ed, ned = self.correct_num_char, self.total_num_char, self.correct_num_word, self.total_num_word, \
+            self.total_ed, self.total_ned
+        if self._totals is not None:
+            host = self._totals.cpu()                                         # the one device-to-host copy
+            cc, tc, cw, words, ed = (a + float(b) for a, b in zip((cc, tc, cw, words, ed), host[:5].tolist()))
+            ned += host[5:].view(torch.float64).item()
+            self.inference_time += sum(e0.elapsed_time(e1) for e0, e1 in self._spans) * 1e-3
+            self._spans = []
+        mets = [cc / tc, cw / words, ed, ned, ed / words, words, self.inference_time]
         return dict(zip(self._names, mets))
 
     @torch.no_grad()
     def compute(self, model, dataloader):
         net = model.module if hasattr(model, "module") else model
         device = next(net.parameters()).device
+        convertor = net.label_convertor
+        if device.type == "cuda" and not self.case_sensitive and convertor.score_table() is not None:
+            for image_tensors, label_tensors in dataloader:
+                image_tensors = image_tensors.to(device)
+                span = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                span[0].record()
+                out_dec = model(image_tensors, text=None, return_loss=False, test_speed=False)
+                self.update_scores(out_dec.float(), list(label_tensors[0]), convertor)
+                span[1].record()
+                self._spans.append(span)                                      # read in result(), behind its copy
+            return self.result()
         for image_tensors, label_tensors in dataloader:
             image_tensors = image_tensors.to(device)
             start = time.time()

@@ -762,6 +762,45 @@ def seg_scores(cm, status):
     return scores
 
 
+# ------------------------------------------------------------------------------------------ Dino/metric/eval_acc.py scores
+TEXT_COLS = 128              # normalised prediction characters per sample (ccd_hip.h: CCD_TEXT_COLS): steps * norm_width <= 128
+TEXT_RECORD = ("distance", "equal_chars", "gt_chars", "word_correct")          # the int32 columns of a per-sample record
+TEXT_TOTALS = ("correct_char", "total_char", "correct_word", "words", "total_ed", "total_ned")     # int64 x 5, then fp64 bits
+
+
+def text_score(scores, table_raw, table_norm, end_idx, pad_idx, gt_codes, gt_len):
+    """Decoder scores fp32 [B, T, C] (any sample / step stride, e.g. probs[:, :done]) against the ground truth as int32 code points
+    [B, L] with lengths int32 [B] -> records int32 [B, 4] in the order of TEXT_RECORD.  table_raw / table_norm: int32 [C, width], the
+    code points of every class and of its normalised form, rows padded with -1 (AttnConvertor.score_table)."""
+    if scores.dim() != 3 or gt_codes.dim() != 2 or gt_codes.shape[0] != scores.shape[0] or tuple(gt_len.shape) != (scores.shape[0],):
+        raise ValueError(f"text_score: expects scores [B, T, C], gt [B, L] and gt_len [B], got {list(scores.shape)}, {list(gt_codes.shape)}, "
+                         f"{list(gt_len.shape)}")
+    B, T, C = scores.shape
+    for name, t in (("table_raw", table_raw), ("table_norm", table_norm)):
+        if t.dim() != 2 or t.shape[0] < C or not t.is_contiguous():      # (the decoder has no <PAD> output: one row more than C)
+            raise ValueError(f"text_score: {name} must be a contiguous [>= {C}, width] table, got {list(t.shape)}")
+    assert gt_len.is_contiguous()
+    records = torch.empty((B, len(TEXT_RECORD)), dtype=I32, device=scores.device)
+    if B:
+        _call("ccd_text_score", scores, scores.stride(0), scores.stride(1), B, T, C, table_raw, table_raw.shape[1], table_norm,
+              table_norm.shape[1], int(end_idx), int(pad_idx), gt_codes if gt_codes.shape[1] else None, gt_codes.stride(0),
+              gt_codes.shape[1], gt_len, records)
+    return records
+
+
+def text_totals(device):
+    """The accumulator of text_accumulate: int64 [6] zeros, in the order of TEXT_TOTALS (the last one holds an fp64)."""
+    return torch.zeros(len(TEXT_TOTALS), dtype=I64, device=device)
+
+
+def text_accumulate(records, totals):
+    """totals (text_totals) += the sums over records [B, 4], in a fixed order; no host synchronisation."""
+    assert records.dtype == I32 and records.is_contiguous() and records.dim() == 2 and records.shape[1] == len(TEXT_RECORD)
+    assert totals.dtype == I64 and totals.is_contiguous() and tuple(totals.shape) == (len(TEXT_TOTALS),)
+    if records.shape[0]:
+        _call("ccd_text_accumulate", records, records.shape[0], totals[:5], totals[5:].view(F64))
+
+
 class SsimFn(torch.autograd.Function):
     """apply(window, taps, size_average, img1, img2[, img3]) -> mean (0-dim) or per-image means [N]; backward on the kernels."""
 

@@ -389,6 +389,34 @@ int ccd_seg_confusion_logits(const float* logits, long image_stride, long channe
  * image with status bit 0 gets five NaNs. */
 int ccd_seg_scores(const int* cm, int* status, int images, double* scores, void* stream);
 
+/* ---------------------------------------------------------------- the recognition scores of Dino/metric/eval_acc.py (ABI 18)
+ * TextAccuracy's scoring loop (eval_acc.py:33-56) from the decoder's output, without the strings ever existing on the host.
+ * ccd_text_score, one wavefront per sample:
+ *   scores      fp32 [batch, steps, classes], classes contiguous, sample and step strides in elements (>= 0): greedy decoding's
+ *               probs[:, :done] view is read in place.  The class of a step is its first maximum; the prediction ends in front of
+ *               the first end_idx step and skips pad_idx steps (Dino/convertor/attn.py:133-154); a pad_idx outside [0, classes)
+ *               skips nothing (NRTRDecoder has no padding output: classes = num_classes - 1).
+ *   table_raw   int32 [>= classes, raw_width], table_norm int32 [>= classes, norm_width]: the code points a class stands for, as
+ *               idx2str writes them and after the metric's normalisation, each row padded with -1 (a row may be empty: the end and
+ *               padding classes; or hold several code points: `<UKN>`).  Widths 1..64; steps * norm_width <= CCD_TEXT_COLS.
+ *   gt          int32 [batch, gt_cols] code points of the ground truth (row stride gt_stride), gt_len int32 [batch] (clamped to
+ *               0..gt_cols); any length.  The ground truth is normalised on the device, code point by code point: A-Z -> a-z,
+ *               U+212A -> k, U+0130 -> i, [a-z0-9^] and U+4E00..U+9FA5 kept, everything else dropped - what
+ *               re.sub('[^A-Z^a-z^0-9^\u4e00-\u9fa5]', '', s.lower()) gives for every string.
+ *   records     int32 [batch, CCD_TEXT_RECORD] = {Levenshtein distance of the normalised strings, position-wise equal code points of
+ *               the raw strings over the shorter one, raw ground-truth length, 1 if the normalised strings are equal}.
+ * ccd_text_accumulate, one workgroup: totals int64 [5] += {equal characters, ground-truth characters, correct words, words, edit
+ * distance}, total_ned fp64 [1] += sum of distance / max(raw ground-truth length, 1), summed in a fixed order (no atomics: the same
+ * batches in the same order give the same bits); launches that share the totals must be ordered on one stream.
+ * batch == 0 is a no-op.  CCD_EINVAL: a missing pointer, a negative stride or size; CCD_ESHAPE: steps or classes < 1, a width outside
+ * 1..64, steps * norm_width > CCD_TEXT_COLS, end_idx outside [0, classes). */
+#define CCD_TEXT_COLS 128
+#define CCD_TEXT_RECORD 4
+int ccd_text_score(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, const int* table_raw,
+                   int raw_width, const int* table_norm, int norm_width, int end_idx, int pad_idx, const int* gt, long gt_stride,
+                   int gt_cols, const int* gt_len, int* records, void* stream);
+int ccd_text_accumulate(const int* records, int batch, long* totals, double* total_ned, void* stream);
+
 /* ---------------------------------------------------------------- DINOHead pieces, vit.py:313,326 */
 int ccd_l2norm_fwd(const ccd_bf16* x, ccd_bf16* y, float* inv, int max_rows, const int* d_rows, int rows_mul, int D,
                    void* stream);

@@ -9,7 +9,9 @@ with gradient averaging over RCCL (ccd_amd.parallel.DataParallel, SURVEY.md 8f r
 `module.` prefix either way, so `pretrain_checkpoint` (the teacher of a pretraining run, :190-198) and `checkpoint`
 ({net, optimizer, iteration}, :199-207, 382-388) load and save in the reference's layout.
 Data: `dataset.scheme: supervised` reads the labelled LMDB datasets (ccd_amd/dataset/dataset_pretrain.py), `synthetic` gives
-seeded labelled batches; benchmark evaluation is test.py (TextAccuracy, ccd_amd/metric/eval_acc.py).
+seeded labelled batches.  With `dataset.test.roots` set, every `training.eval_iters` iterations the benchmarks are scored as test.py
+scores them (TextAccuracy, ccd_amd/metric/eval_acc.py; reference :328-381): the report is appended to log_all_evaluation.txt and the
+best word-weighted total so far keeps `best_accuracy.pth`.
 """
 import argparse
 import logging
@@ -85,6 +87,24 @@ def word_accuracy(model, images, labels):
     return sum(int(a == b) for a, b in zip(idx, truth)) / max(1, len(truth))
 
 
+def evaluate_benchmarks(model, loaders, config, optimizer, iteration, out_dir, best_accuracy):
+    """One evaluation round of the reference's loop (train_finetune.py:328-381) -> (total accuracy, best accuracy so far)."""
+    from test import evaluate
+    logging.info("eval model")
+    report, results = evaluate(model, loaders, config)
+    model.train()
+    words = sum(r["words"] for r in results)
+    total = sum(r["cwr"] * r["words"] for r in results) / max(words, 1.0)
+    with open(os.path.join(out_dir, "log_all_evaluation.txt"), "a") as log:
+        log.write("-" * 80 + "\n" + f"iteration: {iteration} \n" + report + "\n")
+    logging.info(f"iteration: {iteration} \n{report}")
+    if total >= best_accuracy:                           # (>= as in the reference: a tie keeps the later checkpoint)
+        torch.save({"net": model.state_dict(), "optimizer": optimizer.state_dict(), "iteration": iteration},
+                   os.path.join(out_dir, "best_accuracy.pth"))
+        best_accuracy = total
+    return total, best_accuracy
+
+
 def main(config):
     world, rank = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -126,6 +146,11 @@ def main(config):
     os.makedirs(out_dir, exist_ok=True)
     total, it, t0, running, nrun = int(config.training_epochs * len(loader)), iter(loader), time.time(), None, 0
     augmenter = None
+    # benchmark evaluation: rank 0 scores dataset.test.roots, the other ranks wait for it (the evaluation is not sharded)
+    test_loaders, best_accuracy = None, 0.0
+    if config.dataset_test_roots:
+        from test import get_test_loaders
+        test_loaders = get_test_loaders(config) if rank == 0 else []
     while iteration < total:
         try:
             images, labels = next(it)
@@ -156,6 +181,11 @@ def main(config):
             acc = word_accuracy(model, images, labels)
             logging.info(f"iteration: {iteration} synthetic-batch word accuracy: {acc:0.3f} "
                          f"({(time.time() - t0):.0f} s elapsed)")
+            if test_loaders is not None:
+                if rank == 0:
+                    acc, best_accuracy = evaluate_benchmarks(model, test_loaders, config, optimizer, iteration, out_dir, best_accuracy)
+                if world > 1:
+                    dist.barrier()
             if config.writer is not None:
                 config.writer.add_scalar("metric/eval_acc", acc, iteration)
         if iteration % config.training_save_iters == 0 and rank == 0:
