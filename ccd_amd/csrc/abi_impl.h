@@ -27,6 +27,7 @@
 #include "kernels/embed.h"
 #include "kernels/head.h"
 #include "kernels/loss.h"
+#include "kernels/sinkhorn.h"
 #include "kernels/headloss.h"
 #include "kernels/optim.h"
 #include "kernels/conv.h"
@@ -336,7 +337,7 @@ static int ccd_seg_prepare(int images, long pixels, int* cm, int* status, int* c
 
 extern "C" {
 
-int ccd_abi_version(void) { return 18; }   // 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
+int ccd_abi_version(void) { return 19; }   // 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
 const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi16"; }
 int ccd_policy_set(const char* key, int value) {
     CCD_CHECK(key, CCD_EINVAL);
@@ -1458,6 +1459,89 @@ int ccd_center_ema(float* center, const float* batch_sum, int K, const int* d_m,
     CCD_CHECK(center && batch_sum && d_m && K > 0 && world > 0, CCD_EINVAL);
     CCD_LAUNCH(ccd::center_ema_kernel, dim3((K + 255) / 256), dim3(256), 0, stream, center, batch_sum, K, d_m, world,
                momentum);
+    return ccd_rt_last_error();
+}
+// ------------------------------------------------------------------------------- Sinkhorn-Knopp teacher assignment (sinkhorn.h)
+static_assert(CCD_SINKHORN_STRIP == ccd::SK_STRIP && CCD_SINKHORN_ROW_CHUNK == ccd::SK_ROW_CHUNK, "");
+#define CCD_ALIGNED4(p) ((((uintptr_t)(p)) & 3u) == 0)
+static ccd::SkScale ccd_sinkhorn_scale(float temp) {
+    const double inv = 1.0 / (double)temp;
+    ccd::SkScale sc;
+    sc.hi = (float)inv;
+    sc.lo = (float)(inv - (double)sc.hi);
+    return sc;
+}
+static int ccd_sinkhorn_shape(int K, int rows_mul, int max_rows, float temp) {
+    CCD_CHECK(K > 0 && rows_mul > 0 && max_rows > 0 && temp > 0.f && temp < 3.0e38f, CCD_ESHAPE);
+    CCD_CHECK((max_rows + ccd::SK_ROW_CHUNK - 1) / ccd::SK_ROW_CHUNK <= 65535, CCD_ESHAPE);      // (chunks are the grid's y)
+    return CCD_OK;
+}
+long ccd_sinkhorn_ws_floats(int max_rows, int K) {
+    if (max_rows <= 0 || K <= 0) return 0;
+    return 2L * ((max_rows + ccd::SK_ROW_CHUNK - 1) / ccd::SK_ROW_CHUNK) * K;
+}
+int ccd_sinkhorn_colpass(const float* logits, int K, const int* d_rows, int rows_mul, int max_rows, float temp, const float* log_alpha,
+                         float* ws, float* col_m, float* col_s, void* stream) {
+    CCD_CHECK(logits && d_rows && ws && col_m && col_s, CCD_EINVAL);
+    CCD_CHECK(CCD_ALIGNED4(logits) && CCD_ALIGNED4(log_alpha) && CCD_ALIGNED4(ws) && CCD_ALIGNED4(col_m) && CCD_ALIGNED4(col_s), CCD_EINVAL);
+    const int rs = ccd_sinkhorn_shape(K, rows_mul, max_rows, temp);
+    if (rs != CCD_OK) return rs;
+    const int chunks = (max_rows + ccd::SK_ROW_CHUNK - 1) / ccd::SK_ROW_CHUNK, strips = (K + ccd::SK_STRIP - 1) / ccd::SK_STRIP;
+    float* part_m = ws;
+    float* part_s = ws + (long)chunks * K;
+    const ccd::SkScale sc = ccd_sinkhorn_scale(temp);
+    if (K % 4 == 0 && CCD_ALIGNED16(logits) && CCD_ALIGNED16(ws))
+        CCD_LAUNCH((ccd::sinkhorn_colpass_kernel<true>), dim3(strips, chunks), dim3(ccd::SK_THREADS), 0, stream, logits, K, d_rows, rows_mul,
+                   max_rows, sc, log_alpha, part_m, part_s);
+    else
+        CCD_LAUNCH((ccd::sinkhorn_colpass_kernel<false>), dim3(strips, chunks), dim3(ccd::SK_THREADS), 0, stream, logits, K, d_rows, rows_mul,
+                   max_rows, sc, log_alpha, part_m, part_s);
+    CCD_LAUNCH(ccd::sinkhorn_colmerge_kernel, dim3((K + ccd::SK_THREADS - 1) / ccd::SK_THREADS), dim3(ccd::SK_THREADS), 0, stream,
+               (const float*)part_m, (const float*)part_s, K, d_rows, rows_mul, max_rows, col_m, col_s);
+    return ccd_rt_last_error();
+}
+int ccd_sinkhorn_rescale(float* col_m, float* col_s, const float* shift, int K, void* stream) {
+    CCD_CHECK(col_m && col_s && shift && CCD_ALIGNED4(col_m) && CCD_ALIGNED4(col_s) && CCD_ALIGNED4(shift), CCD_EINVAL);
+    CCD_CHECK(K > 0, CCD_ESHAPE);
+    CCD_LAUNCH(ccd::sinkhorn_rescale_kernel, dim3((K + ccd::SK_THREADS - 1) / ccd::SK_THREADS), dim3(ccd::SK_THREADS), 0, stream, col_m, col_s,
+               shift, K);
+    return ccd_rt_last_error();
+}
+int ccd_sinkhorn_finish(const float* col_m, const float* col_s, int K, float temp, float* log_beta, float* c, void* stream) {
+    CCD_CHECK(col_m && col_s && (log_beta || c), CCD_EINVAL);
+    CCD_CHECK(CCD_ALIGNED4(col_m) && CCD_ALIGNED4(col_s) && CCD_ALIGNED4(log_beta) && CCD_ALIGNED4(c), CCD_EINVAL);
+    CCD_CHECK(K > 0 && temp > 0.f && temp < 3.0e38f, CCD_ESHAPE);
+    CCD_LAUNCH(ccd::sinkhorn_finish_kernel, dim3(1), dim3(ccd::SK_FIN_THREADS), 0, stream, col_m, col_s, K, temp, log_beta, c);
+    return ccd_rt_last_error();
+}
+int ccd_sinkhorn_rowpass(const float* logits, int K, const int* d_rows, int rows_mul, int max_rows, float temp, const float* log_beta,
+                         float* log_alpha, void* stream) {
+    CCD_CHECK(logits && d_rows && log_beta && log_alpha, CCD_EINVAL);
+    CCD_CHECK(CCD_ALIGNED4(logits) && CCD_ALIGNED4(log_beta) && CCD_ALIGNED4(log_alpha), CCD_EINVAL);
+    const int rs = ccd_sinkhorn_shape(K, rows_mul, max_rows, temp);
+    if (rs != CCD_OK) return rs;
+    const ccd::SkScale sc = ccd_sinkhorn_scale(temp);
+    if (K % 4 == 0 && CCD_ALIGNED16(logits) && CCD_ALIGNED16(log_beta))
+        CCD_LAUNCH((ccd::sinkhorn_rowpass_kernel<true>), dim3(max_rows), dim3(ccd::SK_THREADS), 0, stream, logits, K, d_rows, rows_mul, max_rows,
+                   sc, log_beta, log_alpha);
+    else
+        CCD_LAUNCH((ccd::sinkhorn_rowpass_kernel<false>), dim3(max_rows), dim3(ccd::SK_THREADS), 0, stream, logits, K, d_rows, rows_mul, max_rows,
+                   sc, log_beta, log_alpha);
+    return ccd_rt_last_error();
+}
+int ccd_sinkhorn_assign(const float* logits, int K, const int* d_rows, int rows_mul, int max_rows, float temp, const float* log_beta,
+                        float* q, void* stream) {
+    CCD_CHECK(logits && d_rows && log_beta && q, CCD_EINVAL);
+    CCD_CHECK(CCD_ALIGNED4(logits) && CCD_ALIGNED4(log_beta) && CCD_ALIGNED4(q), CCD_EINVAL);
+    const int rs = ccd_sinkhorn_shape(K, rows_mul, max_rows, temp);
+    if (rs != CCD_OK) return rs;
+    const ccd::SkScale sc = ccd_sinkhorn_scale(temp);
+    if (K % 4 == 0 && CCD_ALIGNED16(logits) && CCD_ALIGNED16(log_beta) && CCD_ALIGNED16(q))
+        CCD_LAUNCH((ccd::sinkhorn_assign_kernel<true>), dim3(max_rows), dim3(ccd::SK_THREADS), 0, stream, logits, K, d_rows, rows_mul, max_rows,
+                   sc, log_beta, q);
+    else
+        CCD_LAUNCH((ccd::sinkhorn_assign_kernel<false>), dim3(max_rows), dim3(ccd::SK_THREADS), 0, stream, logits, K, d_rows, rows_mul, max_rows,
+                   sc, log_beta, q);
     return ccd_rt_last_error();
 }
 int ccd_seg_loss(const float* logits, const float* mask_a, const uint8_t* idmap_b, int half, float grad_scale,

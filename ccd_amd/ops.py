@@ -940,6 +940,67 @@ def center_ema(center, batch_sum, d_m, world, momentum):
     _call("ccd_center_ema", center, batch_sum, center.numel(), d_m, int(world), float(momentum))
 
 
+SINKHORN_STRIP = 1024        # columns per workgroup of the Sinkhorn column pass (sinkhorn.h: SK_STRIP)
+SINKHORN_ROW_CHUNK = 128     # rows per workgroup of that pass (SK_ROW_CHUNK); the chunks' partial sums are folded in ascending order
+
+
+def _sinkhorn_log_beta(logits, d_total, temp, n_iterations, rows_mul, c):
+    """The Sinkhorn-Knopp iteration of Dino_loss.py:157-184 in the log domain (include/ccd_hip.h: ccd_sinkhorn_*): n_iterations
+    column passes and n_iterations - 1 row passes over `logits`.  -> log beta [K], gauged to mean 0; `c` [K] (or None) receives
+    -temp * log beta.
+    In a process group the column state is all-reduced (MAX of the shifts, SUM of the re-based sums), as the reference all-reduces
+    its prototype sums; ranks may hold different numbers of rows.  Nothing here reads a value back from the device."""
+    import torch.distributed as dist
+    if int(n_iterations) < 1:
+        raise ValueError("sinkhorn: n_iterations must be at least 1")
+    if logits.dim() != 2 or logits.dtype != F32 or not logits.is_contiguous():
+        raise ValueError("sinkhorn: logits must be a dense [rows, K] fp32 matrix")
+    max_rows, K = logits.shape
+    dev, temp = logits.device, float(temp)
+    ws = torch.empty(int(_lib.get().ccd_sinkhorn_ws_floats(max_rows, K)), dtype=F32, device=dev)
+    col_m, col_s = torch.empty(K, dtype=F32, device=dev), torch.empty(K, dtype=F32, device=dev)
+    log_beta, log_alpha = torch.empty(K, dtype=F32, device=dev), torch.empty(max_rows, dtype=F32, device=dev)
+    shared = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+    passes = 2 * int(n_iterations) - 1
+    with _Span("sinkhorn_potentials", 0.0, 4.0 * passes * max_rows * K):
+        for it in range(int(n_iterations)):
+            _call("ccd_sinkhorn_colpass", logits, K, d_total, int(rows_mul), max_rows, temp, log_alpha if it else None, ws, col_m, col_s)
+            if shared:
+                shift = col_m.clone()
+                dist.all_reduce(shift, op=dist.ReduceOp.MAX)
+                _call("ccd_sinkhorn_rescale", col_m, col_s, shift, K)
+                dist.all_reduce(col_s)
+            last = it == int(n_iterations) - 1
+            _call("ccd_sinkhorn_finish", col_m, col_s, K, temp, log_beta, c if last else None)
+            if not last:
+                _call("ccd_sinkhorn_rowpass", logits, K, d_total, int(rows_mul), max_rows, temp, log_beta, log_alpha)
+    return log_beta
+
+
+def sinkhorn_potentials(logits, d_total, temp, n_iterations=3, rows_mul=2, out=None):
+    """c [K] fp32 with softmax((logits - c) / temp) == DINOLoss.sinkhorn_knopp_teacher(logits, temp, n_iterations) of the reference on
+    the first rows_mul * d_total[0] rows (d_total: int32 device scalar), mean(c) == 0: what the loss kernels take in place of the
+    centre.  `logits`: [max_rows, K] fp32, or an engine.LazyLogits (materialised once by its tensor())."""
+    from .engine import logits_tensor
+    logits = logits_tensor(logits)
+    if out is None:
+        out = torch.empty(logits.shape[1], dtype=F32, device=logits.device)
+    if out.dtype != F32 or out.numel() != logits.shape[1] or not out.is_contiguous():
+        raise ValueError("sinkhorn_potentials: out must be a dense fp32 tensor of K elements")
+    _sinkhorn_log_beta(logits, d_total, temp, n_iterations, rows_mul, out.view(-1))
+    return out
+
+
+def sinkhorn_assign(logits, d_total, temp, n_iterations=3, rows_mul=2):
+    """The assignment itself, [max_rows, K] fp32 (rows past rows_mul * d_total[0] are zero): sinkhorn_potentials + one row softmax."""
+    from .engine import logits_tensor
+    logits = logits_tensor(logits)
+    log_beta = _sinkhorn_log_beta(logits, d_total, temp, n_iterations, rows_mul, None)
+    q = torch.zeros_like(logits)
+    _call("ccd_sinkhorn_assign", logits, logits.shape[1], d_total, int(rows_mul), logits.shape[0], float(temp), log_beta, q)
+    return q
+
+
 def seg_loss(logits, mask_a, idmap_b, grad_scale, loss_out, d_logits=None):
     half = mask_a.shape[0]
     assert logits.shape[0] == 2 * half and logits.is_contiguous()

@@ -54,6 +54,15 @@ def make_optimizer(student_module, clip_grad=3.0, name="adamw"):
     return opt
 
 
+def make_dino_loss(config, nepochs):
+    """DINOLoss of train.py:116-124 from the YAML.  `teacher_centering` ("center", the default, or "sinkhorn_knopp") and
+    `sinkhorn_iterations` (3) are this implementation's keys for the assignment the reference keeps behind a commented call
+    (Dino_loss.py:88); a config without them builds what the reference builds."""
+    return DINOLoss(config.out_dim, config.crops_number, config.warmup_teacher_temp, config.teacher_temp,
+                    config.warmup_teacher_temp_epochs, nepochs, teacher_centering=config.teacher_centering or "center",
+                    sinkhorn_iterations=config.sinkhorn_iterations or 3)
+
+
 def _set_schedule(optimizer, lr, wd):
     for i, g in enumerate(optimizer.param_groups):
         g["lr"] = float(lr)

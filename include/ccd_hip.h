@@ -460,6 +460,35 @@ int ccd_colsum_f32(const float* x, int K, const int* d_rows, int rows_mul, int m
 int ccd_matvec_bf16(const ccd_bf16* w, long ldw, const float* v, int K, int D, float* out, void* stream);
 int ccd_center_ema(float* center, const float* batch_sum, int K, const int* d_m, int world, float momentum,
                    void* stream);
+/* DINOLoss.sinkhorn_knopp_teacher, Dino_loss.py:157-184 (ABI 19): the SwAV / DINOv2 equal-partition assignment of the teacher logits
+ * [max_rows, K] fp32, dense row-major, live rows = rows_mul * d_rows[0] (device side; rows past them are never read).  What the
+ * reference returns is softmax_k(t[r, k] / temp + log beta_k) with beta its accumulated prototype scaling; these entries iterate the
+ * two scalings in the log domain (x = t / temp, every sum shifted by its maximum: no finite x overflows) and hand the loss kernels
+ *   c[k] = -temp * log beta[k],  gauged to mean_k c = 0,
+ * which ccd_dino_loss_fwd / _bwd and ccd_head_loss_fwd / _bwd take in place of `center`: softmax((t - c) / temp) IS the assignment.
+ * One iteration = colpass -> [all-reduce] -> finish -> rowpass; the last iteration stops at finish (the loss's own softmax scales
+ * the rows), so n iterations read the matrix 2n - 1 times.
+ *   colpass  col_m[k], col_s[k]: sum_r exp(x[r,k] + log_alpha[r]) = col_s[k] * exp(col_m[k])  (log_alpha NULL: uniform, the first pass).
+ *            Strips of CCD_SINKHORN_STRIP columns x chunks of CCD_SINKHORN_ROW_CHUNK rows; the chunks' partial (max, sum) pairs go
+ *            through `ws` (ccd_sinkhorn_ws_floats(max_rows, K) floats) and are folded in ascending order: bit-reproducible, no atomics.
+ *   rescale  col_s[k] *= exp(col_m[k] - shift[k]), col_m[k] = shift[k]: between ranks, shift = all_reduce(MAX) of col_m, then
+ *            all_reduce(SUM) of col_s (the reference's all_reduce of the prototype sums, :174-175); ranks may hold different row counts.
+ *   finish   log_beta[k] = -(col_m[k] + log col_s[k]) - mean_k(...), c[k] = -temp * log_beta[k]; either output may be NULL.
+ *   rowpass  log_alpha[r] = -log sum_k exp(x[r,k] + log_beta[k])                                     (live rows only)
+ *   assign   q[r,k] = softmax_k(x[r,k] + log_beta[k]), the [max_rows, K] assignment itself            (live rows only)
+ * Any K >= 1 and any 4-byte aligned pointers; K % 4 == 0 with 16-byte aligned matrices takes 16-byte loads.  CCD_ESHAPE: K, rows_mul,
+ * max_rows or temp not positive, max_rows > 65535 * CCD_SINKHORN_ROW_CHUNK. */
+#define CCD_SINKHORN_STRIP 1024
+#define CCD_SINKHORN_ROW_CHUNK 128
+long ccd_sinkhorn_ws_floats(int max_rows, int K);
+int ccd_sinkhorn_colpass(const float* logits, int K, const int* d_rows, int rows_mul, int max_rows, float temp, const float* log_alpha,
+                         float* ws, float* col_m, float* col_s, void* stream);
+int ccd_sinkhorn_rescale(float* col_m, float* col_s, const float* shift, int K, void* stream);
+int ccd_sinkhorn_finish(const float* col_m, const float* col_s, int K, float temp, float* log_beta, float* c, void* stream);
+int ccd_sinkhorn_rowpass(const float* logits, int K, const int* d_rows, int rows_mul, int max_rows, float temp, const float* log_beta,
+                         float* log_alpha, void* stream);
+int ccd_sinkhorn_assign(const float* logits, int K, const int* d_rows, int rows_mul, int max_rows, float temp, const float* log_beta,
+                        float* q, void* stream);
 /* softmax -> cross_entropy (double softmax) of the seg logits [2*half,2,32,128]; d_logits may be NULL */
 int ccd_seg_loss(const float* logits, const float* mask_a, const uint8_t* idmap_b, int half, float grad_scale,
                  float* loss_out, float* d_logits, void* stream);

@@ -158,8 +158,7 @@ def train(config):
     global_bs = config.batch_size_per_gpu * world
     config.epochs = int(config.training_epochs * len(loader) * global_bs / config.imgnet_based) + 1
     print(f"training epochs is {config.epochs}")
-    dino_loss = DINOLoss(config.out_dim, config.crops_number, config.warmup_teacher_temp, config.teacher_temp,
-                         config.warmup_teacher_temp_epochs, config.epochs).cuda()
+    dino_loss = pretrain.make_dino_loss(config, config.epochs).cuda()
     if config.use_fp16:
         raise NotImplementedError("use_fp16 is False in every shipped config; this implementation runs bf16 MFMA "
                                   "operands with fp32 master weights and needs no loss scaler")
