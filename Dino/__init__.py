@@ -3,7 +3,7 @@
 ABIDINOModel`, `from Dino.loss.Dino_loss import DINOLoss`, `from Dino.utils.utils import Config`,
 `from Dino.utils.DBSCAN import label_cluster`, `from Dino.metric.eval_superpixel import SSIM`, `from Dino.metric.eval_IOU import fore_IU` keep working.
 The pretraining path and the finetune path (8f row 1: DINO_Finetune, NRTRDecoder, TFLoss,
-AttnConvertor) exist here."""
+AttnConvertor) exist here, and beside the latter a CTC head the reference lacks (CTCDecoder, CTCLoss, CTCConvertor)."""
 import importlib
 import sys
 
@@ -17,10 +17,13 @@ _ALIASES = {
     "Dino.loss": "ccd_amd.loss",
     "Dino.loss.Dino_loss": "ccd_amd.loss.Dino_loss",
     "Dino.loss.ce_loss": "ccd_amd.loss.ce_loss",
+    "Dino.loss.ctc_loss": "ccd_amd.loss.ctc_loss",
     "Dino.decoder": "ccd_amd.decoder",
     "Dino.decoder.nrtr_decoder": "ccd_amd.decoder.nrtr_decoder",
+    "Dino.decoder.ctc_decoder": "ccd_amd.decoder.ctc_decoder",
     "Dino.convertor": "ccd_amd.convertor",
     "Dino.convertor.attn": "ccd_amd.convertor.attn",
+    "Dino.convertor.ctc": "ccd_amd.convertor.ctc",
     "Dino.metric": "ccd_amd.metric",
     "Dino.metric.eval_acc": "ccd_amd.metric.eval_acc",
     "Dino.metric.eval_superpixel": "ccd_amd.metric.eval_superpixel",

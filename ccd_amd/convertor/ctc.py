@@ -1,0 +1,121 @@
+"""Label codec of the CTC recognition head: words <-> class indices <-> zero-padded target tensors.
+
+Class layout: `<BLK>` (the CTC blank) is class 0, the alphabet occupies 1..n, `<UKN>` (when enabled) is last: DICT90 gives 92
+classes.  A target row is the word's classes followed by zeros, cut to `max_seq_len` - a valid label is never 0, so the length of a
+row is its count of leading non-zero entries (what ccd_ctc_loss_fwd reads on the device).  Decoding is the greedy CTC rule: the
+arg-max class of every frame (first maximum), repeats collapsed, blanks dropped.  The reference has no CTC head; the surface follows
+AttnConvertor's so that DINO_Finetune, TextAccuracy, train_finetune.py and test.py take either.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .attn import ALPHABETS, _NO_CLASS, _read_alphabet_file
+
+
+def is_ctc(convertor):
+    """True for the codec of the CTC head (targets are zero-padded classes, decoding is the greedy CTC rule)."""
+    return isinstance(convertor, CTCConvertor)
+
+
+class CTCConvertor:
+    """CTCConvertor(dict_type='DICT90', with_unknown=True, max_seq_len=25, lower=False) - see the module docstring."""
+
+    dicts = {name: tuple(chars) for name, chars in ALPHABETS.items()}
+
+    def __init__(self, dict_type="DICT90", dict_file=None, dict_list=None, with_unknown=True, max_seq_len=25, lower=False, **_ignored):
+        if dict_file is not None:
+            alphabet = _read_alphabet_file(dict_file)
+        elif dict_list is not None:
+            alphabet = list(dict_list)
+        elif dict_type in ALPHABETS:
+            alphabet = list(ALPHABETS[dict_type])
+        else:
+            raise NotImplementedError(f"unknown dictionary type {dict_type!r} (have {sorted(ALPHABETS)})")
+        if len(set(alphabet)) != len(alphabet):
+            raise AssertionError("dictionary holds a character twice")
+        self.with_unknown, self.max_seq_len, self.lower = bool(with_unknown), int(max_seq_len), bool(lower)
+        self.blank_idx = 0
+        self.idx2char = ["<BLK>"] + alphabet
+        self.unknown_idx = None
+        if self.with_unknown:
+            self.idx2char.append("<UKN>")
+            self.unknown_idx = len(self.idx2char) - 1
+        self.char2idx = {c: i for i, c in enumerate(self.idx2char)}
+        points = [ord(c) for c in alphabet if len(c) == 1]
+        self._lut = np.full(max(points) + 1 if points else 1, _NO_CLASS, dtype=np.int64)
+        for cls, c in enumerate(alphabet, start=1):
+            if len(c) == 1:
+                self._lut[ord(c)] = cls
+
+    def num_classes(self):
+        return len(self.idx2char)
+
+    # ------------------------------------------------------------------ encode
+    def _classes_of(self, word):
+        if self.lower:
+            word = word.lower()
+        points = np.frombuffer(word.encode("utf-32-le"), dtype="<u4").astype(np.int64)
+        inside = points < self._lut.size
+        cls = np.where(inside, self._lut[np.minimum(points, self._lut.size - 1)], _NO_CLASS)
+        missing = cls == _NO_CLASS
+        if missing.any():
+            if self.unknown_idx is None:
+                bad = word[int(np.argmax(missing))]
+                raise KeyError(f"character {bad!r} is not in the dictionary (pass with_unknown=True or a custom dict_file)")
+            cls = np.where(missing, self.unknown_idx, cls)
+        return cls
+
+    def str2idx(self, strings):
+        if not isinstance(strings, list):
+            raise TypeError("str2idx expects a list of strings")
+        return [self._classes_of(w).tolist() for w in strings]
+
+    def idx2str(self, indexes):
+        if not isinstance(indexes, list):
+            raise TypeError("idx2str expects a list of index lists")
+        table = self.idx2char
+        return ["".join(table[i] for i in row) for row in indexes]
+
+    def str2tensor(self, strings):
+        """['hello', ...] -> int64 [N, max_seq_len]: the word's classes, zero-padded (longer words cut)."""
+        if not isinstance(strings, list) or not all(isinstance(w, str) for w in strings):
+            raise TypeError("str2tensor expects a list of strings")
+        target = np.zeros((len(strings), self.max_seq_len), dtype=np.int64)
+        for row, word in zip(target, strings):
+            cls = self._classes_of(word)[:self.max_seq_len]
+            row[:cls.size] = cls
+        return torch.from_numpy(target)
+
+    # ------------------------------------------------------------------ decode
+    def score_table(self, steps=32):
+        """The classes as code points for ops.text_score_ctc, as AttnConvertor.score_table: (raw, normalised) int32 [num_classes,
+        width], rows padded with -1, the blank's row empty.  None when `steps` frames of the longest normalised row would not fit the
+        kernel's columns.  The tables are built once."""
+        if not hasattr(self, "_tables"):
+            from ..metric.eval_acc import normalise
+            raw = ["" if c == self.blank_idx else s for c, s in enumerate(self.idx2char)]
+            tables = []
+            for rows in (raw, [normalise(s) for s in raw]):
+                table = np.full((len(rows), max(1, max(map(len, rows)))), -1, dtype=np.int32)
+                for row, s in zip(table, rows):
+                    row[:len(s)] = np.frombuffer(s.encode("utf-32-le"), dtype="<u4")
+                tables.append(table)
+            self._tables = tuple(tables)
+        from ..ops import TEXT_COLS
+        return self._tables if steps * self._tables[1].shape[1] <= TEXT_COLS else None
+
+    @torch.no_grad()
+    def tensor2idx(self, outputs, img_metas=None):
+        """[N, T, C] frame scores (logits or probabilities) -> (class indices, confidences) per sample by the greedy rule; the
+        confidence of a character is the softmax probability (of `outputs` as given) of the first frame of its run."""
+        probs = outputs.float().softmax(dim=-1)
+        conf, cls = probs.max(dim=-1)                                        # [N, T]; the first maximum
+        cls_np, conf_np = cls.cpu().numpy(), conf.cpu().numpy()
+        new_run = np.ones_like(cls_np, dtype=bool)
+        new_run[:, 1:] = cls_np[:, 1:] != cls_np[:, :-1]
+        keep = new_run & (cls_np != self.blank_idx)
+        indexes = [cls_np[i][keep[i]].tolist() for i in range(cls_np.shape[0])]
+        scores = [conf_np[i][keep[i]].tolist() for i in range(cls_np.shape[0])]
+        return indexes, scores

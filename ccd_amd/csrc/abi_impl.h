@@ -23,6 +23,7 @@
 #include "kernels/ssim.h"
 #include "kernels/segmetric.h"
 #include "kernels/textscore.h"
+#include "kernels/ctc.h"
 #include "kernels/datapipe.h"
 #include "kernels/embed.h"
 #include "kernels/head.h"
@@ -337,7 +338,7 @@ static int ccd_seg_prepare(int images, long pixels, int* cm, int* status, int* c
 
 extern "C" {
 
-int ccd_abi_version(void) { return 19; }   // 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
+int ccd_abi_version(void) { return 20; }   // 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
 const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi16"; }
 int ccd_policy_set(const char* key, int value) {
     CCD_CHECK(key, CCD_EINVAL);
@@ -1302,8 +1303,23 @@ int ccd_text_score(const float* scores, long sample_stride, long step_stride, in
               norm_width <= ccd::TS_MAX_WIDTH, CCD_ESHAPE);
     CCD_CHECK((long)steps * norm_width <= ccd::TS_COLS, CCD_ESHAPE);          // the longest normalised prediction: two columns per lane
     CCD_CHECK(end_idx >= 0 && end_idx < classes, CCD_ESHAPE);      // (a pad_idx no step can take skips nothing: a decoder without a padding output)
-    CCD_LAUNCH(ccd::text_score_kernel, dim3((unsigned)((batch + ccd::TS_WAVES - 1) / ccd::TS_WAVES)), dim3(ccd::TS_THREADS), 0, stream, scores,
+    CCD_LAUNCH(ccd::text_score_kernel<false>, dim3((unsigned)((batch + ccd::TS_WAVES - 1) / ccd::TS_WAVES)), dim3(ccd::TS_THREADS), 0, stream, scores,
                sample_stride, step_stride, batch, steps, classes, table_raw, raw_width, table_norm, norm_width, end_idx, pad_idx, gt,
+               gt_stride, gt_cols, gt_len, records);
+    return ccd_rt_last_error();
+}
+int ccd_text_score_ctc(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, const int* table_raw,
+                       int raw_width, const int* table_norm, int norm_width, const int* gt, long gt_stride, int gt_cols, const int* gt_len,
+                       int* records, void* stream) {
+    CCD_CHECK(batch >= 0, CCD_EINVAL);
+    if (batch == 0) return CCD_OK;
+    CCD_CHECK(scores && table_raw && table_norm && gt_len && records && (gt || gt_cols == 0), CCD_EINVAL);
+    CCD_CHECK(sample_stride >= 0 && step_stride >= 0 && gt_stride >= 0 && gt_cols >= 0, CCD_EINVAL);
+    CCD_CHECK(steps >= 1 && classes >= 1 && raw_width >= 1 && raw_width <= ccd::TS_MAX_WIDTH && norm_width >= 1 &&
+              norm_width <= ccd::TS_MAX_WIDTH, CCD_ESHAPE);
+    CCD_CHECK((long)steps * norm_width <= ccd::TS_COLS, CCD_ESHAPE);
+    CCD_LAUNCH(ccd::text_score_kernel<true>, dim3((unsigned)((batch + ccd::TS_WAVES - 1) / ccd::TS_WAVES)), dim3(ccd::TS_THREADS), 0, stream, scores,
+               sample_stride, step_stride, batch, steps, classes, table_raw, raw_width, table_norm, norm_width, -1, -1, gt,
                gt_stride, gt_cols, gt_len, records);
     return ccd_rt_last_error();
 }
@@ -1312,6 +1328,73 @@ int ccd_text_accumulate(const int* records, int batch, long* totals, double* tot
     if (batch == 0) return CCD_OK;
     CCD_CHECK(records && totals && total_ned, CCD_EINVAL);
     CCD_LAUNCH(ccd::text_accumulate_kernel, dim3(1), dim3(ccd::TS_THREADS), 0, stream, records, batch, totals, total_ned);
+    return ccd_rt_last_error();
+}
+
+// ------------------------------------------------------------------------------- CTC recognition head (kernels/ctc.h)
+static_assert(CCD_CTC_MAX_STEPS == ccd::CTC_MAX_T && CCD_CTC_MAX_CLASSES == ccd::CTC_MAX_C && CCD_CTC_MAX_LABELS == ccd::CTC_MAX_L, "");
+static int ccd_ctc_pool_launch(bool bwd, const ccd_bf16* src, ccd_bf16* dst, int images, int rows, int cols, int E, void* stream) {
+    CCD_CHECK(images >= 0 && rows >= 0 && cols >= 0 && E >= 0, CCD_EINVAL);
+    if (images == 0) return CCD_OK;
+    CCD_CHECK(src && dst && CCD_ALIGNED16(src) && CCD_ALIGNED16(dst), CCD_EINVAL);
+    CCD_CHECK(rows >= 1 && rows <= 64 && cols >= 1 && E >= 8 && E % 8 == 0, CCD_ESHAPE);
+    const long chunks = (long)images * cols * (E / 8);
+    const dim3 grid(ccd_stream_blocks(chunks, 1)), block(256);
+    if (bwd) CCD_LAUNCH(ccd::ctc_pool_bwd_kernel, grid, block, 0, stream, reinterpret_cast<const ccd::bf16_t*>(src),
+                        reinterpret_cast<ccd::bf16_t*>(dst), chunks, rows, cols, E / 8);
+    else CCD_LAUNCH(ccd::ctc_pool_fwd_kernel, grid, block, 0, stream, reinterpret_cast<const ccd::bf16_t*>(src),
+                    reinterpret_cast<ccd::bf16_t*>(dst), chunks, rows, cols, E / 8);
+    return ccd_rt_last_error();
+}
+int ccd_ctc_pool_fwd(const ccd_bf16* tokens, ccd_bf16* frames, int images, int rows, int cols, int E, void* stream) {
+    return ccd_ctc_pool_launch(false, tokens, frames, images, rows, cols, E, stream);
+}
+int ccd_ctc_pool_bwd(const ccd_bf16* d_frames, ccd_bf16* d_tokens, int images, int rows, int cols, int E, void* stream) {
+    return ccd_ctc_pool_launch(true, d_frames, d_tokens, images, rows, cols, E, stream);
+}
+long ccd_ctc_loss_ws_bytes(int batch, int steps) {
+    return batch > 0 && steps > 0 ? (long)batch * ccd::ctc_ws_stride(steps) * (long)sizeof(ccd::ctc_real) : 0;
+}
+static int ccd_ctc_shape(int batch, int steps, int classes, long ld) {
+    CCD_CHECK(batch >= 0 && ld >= 0, CCD_EINVAL);
+    CCD_CHECK(classes >= 1 && classes <= ccd::CTC_MAX_C && steps >= 1 && steps <= ccd::CTC_MAX_T && ld >= classes, CCD_ESHAPE);
+    return CCD_OK;
+}
+int ccd_ctc_loss_fwd(const float* logits, long ldl, int batch, int steps, int classes, const int64_t* targets, int max_len, float* nll,
+                     float* acc, void* ws, void* stream) {
+    CCD_CHECK(max_len >= 0, CCD_EINVAL);
+    const int shape = ccd_ctc_shape(batch, steps, classes, ldl);
+    if (shape != CCD_OK) return shape;
+    CCD_CHECK(max_len <= ccd::CTC_MAX_L, CCD_ESHAPE);
+    if (batch == 0) return CCD_OK;
+    CCD_CHECK(logits && nll && acc && ws && (targets || max_len == 0) && (((uintptr_t)ws) & 7u) == 0, CCD_EINVAL);
+    ccd::ctc_real* const w = reinterpret_cast<ccd::ctc_real*>(ws);
+    CCD_LAUNCH(ccd::ctc_loss_fwd_kernel, dim3((unsigned)((batch + ccd::CTC_WAVES - 1) / ccd::CTC_WAVES)), dim3(ccd::CTC_THREADS), 0, stream,
+               logits, ldl, batch, steps, classes, reinterpret_cast<const long*>(targets), max_len, nll, w);
+    CCD_LAUNCH(ccd::ctc_loss_acc_kernel, dim3(1), dim3(ccd::CTC_THREADS), 0, stream, static_cast<const ccd::ctc_real*>(w), batch, steps, acc);
+    return ccd_rt_last_error();
+}
+int ccd_ctc_loss_bwd(const float* logits, long ldl, int batch, int steps, int classes, const int64_t* targets, int max_len, const void* ws,
+                     const float* upstream, ccd_bf16* d_logits, long ldd, void* stream) {
+    CCD_CHECK(max_len >= 0 && ldd >= 0, CCD_EINVAL);
+    const int shape = ccd_ctc_shape(batch, steps, classes, ldl);
+    if (shape != CCD_OK) return shape;
+    CCD_CHECK(max_len <= ccd::CTC_MAX_L && ldd >= classes, CCD_ESHAPE);
+    if (batch == 0) return CCD_OK;
+    CCD_CHECK(logits && ws && d_logits && (targets || max_len == 0) && (((uintptr_t)ws) & 7u) == 0, CCD_EINVAL);
+    CCD_LAUNCH(ccd::ctc_loss_bwd_kernel, dim3((unsigned)((batch + ccd::CTC_WAVES - 1) / ccd::CTC_WAVES)), dim3(ccd::CTC_THREADS), 0, stream,
+               logits, ldl, batch, steps, classes, reinterpret_cast<const long*>(targets), max_len, reinterpret_cast<const ccd::ctc_real*>(ws),
+               upstream, reinterpret_cast<ccd::bf16_t*>(d_logits), ldd);
+    return ccd_rt_last_error();
+}
+int ccd_ctc_greedy(const float* logits, long sample_stride, long step_stride, int batch, int steps, int classes, int* path, int* length,
+                   float* conf, void* stream) {
+    CCD_CHECK(batch >= 0 && sample_stride >= 0 && step_stride >= 0, CCD_EINVAL);
+    CCD_CHECK(classes >= 1 && classes <= ccd::CTC_MAX_C && steps >= 1 && steps <= ccd::CTC_MAX_T, CCD_ESHAPE);
+    if (batch == 0) return CCD_OK;
+    CCD_CHECK(logits && path && length && conf, CCD_EINVAL);
+    CCD_LAUNCH(ccd::ctc_greedy_kernel, dim3((unsigned)((batch + ccd::CTC_WAVES - 1) / ccd::CTC_WAVES)), dim3(ccd::CTC_THREADS), 0, stream,
+               logits, sample_stride, step_stride, batch, steps, classes, path, length, conf);
     return ccd_rt_last_error();
 }
 

@@ -64,6 +64,9 @@ __device__ __forceinline__ int ts_row_len(const int* __restrict__ row, int width
 }
 
 // grid = ceil(B / TS_WAVES).  The launcher has checked T * norm_width <= TS_COLS (hence T <= 128: two steps per lane).
+// CTC = true (ccd_text_score_ctc): the steps are frames of a CTC head - a step counts where its class is not the blank (class 0) and
+// differs from the step before; there is no end class and nothing is skipped as padding (end_idx, pad_idx unused).
+template <bool CTC>
 __global__ __launch_bounds__(TS_THREADS) void text_score_kernel(const float* __restrict__ scores, long sample_stride, long step_stride,
                                                                 int B, int T, int C, const int* __restrict__ tbl_raw, int raw_width,
                                                                 const int* __restrict__ tbl_norm, int norm_width, int end_idx, int pad_idx,
@@ -93,14 +96,22 @@ __global__ __launch_bounds__(TS_THREADS) void text_score_kernel(const float* __r
             cls[h] = arg;
         }
     }
-    const unsigned long long e0 = ballot(cls[0] == end_idx), e1 = ballot(cls[1] == end_idx);
-    const int end = e0 ? __builtin_ctzll(e0) : (e1 ? 64 + __builtin_ctzll(e1) : T);
+    int end = T;
+    bool counts[2] = {cls[0] != pad_idx, cls[1] != pad_idx};
+    if constexpr (CTC) {
+        const int before0 = shfl(cls[0], lane ? lane - 1 : 0), last0 = shfl(cls[0], 63), before1 = shfl(cls[1], lane ? lane - 1 : 0);
+        counts[0] = cls[0] > 0 && (lane == 0 || cls[0] != before0);
+        counts[1] = cls[1] > 0 && cls[1] != (lane == 0 ? last0 : before1);
+    } else {
+        const unsigned long long e0 = ballot(cls[0] == end_idx), e1 = ballot(cls[1] == end_idx);
+        end = e0 ? __builtin_ctzll(e0) : (e1 ? 64 + __builtin_ctzll(e1) : T);
+    }
 
     // ---- where each step's characters lie in the raw and in the normalised prediction (lengths packed: raw | norm << 16)
     int len[2] = {0, 0}, at[2] = {0, 0}, total = 0;
     for (int h = 0; h < halves; ++h) {
         const int t = lane + 64 * h;
-        if (t < end && cls[h] != pad_idx)
+        if (t < end && counts[h])
             len[h] = ts_row_len(tbl_raw + (long)cls[h] * raw_width, raw_width) | (ts_row_len(tbl_norm + (long)cls[h] * norm_width, norm_width) << 16);
         const int incl = ts_scan_add(len[h], lane);
         at[h] = total + incl - len[h];

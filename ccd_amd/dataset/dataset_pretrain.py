@@ -26,7 +26,7 @@ from .datasetsupervised_kmeans import MEAN, STD, resize_bilinear
 
 class ImageDataset(Dataset):
     def __init__(self, path, is_training=True, img_h=32, img_w=128, max_length=25, case_sensitive=False, type="DICT90",
-                 convert_mode="RGB", data_aug=True, multiscales=False, data_portion=1.0, **_ignored):
+                 convert_mode="RGB", data_aug=True, multiscales=False, data_portion=1.0, label_convertor=None, **_ignored):
         from ..convertor.attn import AttnConvertor
         self.path = os.fspath(path)
         if not os.path.isdir(self.path):
@@ -35,7 +35,8 @@ class ImageDataset(Dataset):
             raise NotImplementedError("multiscales=True is not used by the CCD configs")
         self.is_training, self.img_h, self.img_w, self.convert_mode = bool(is_training), int(img_h), int(img_w), convert_mode
         self.data_aug = bool(is_training) and bool(data_aug)                       # (:68 `if self.is_training and self.data_aug`)
-        self.label_convertor = AttnConvertor(dict_type=type, max_seq_len=max_length, with_unknown=True)
+        # (label_convertor: the model's own codec where it is not the attention decoder's, e.g. a CTCConvertor)
+        self.label_convertor = label_convertor or AttnConvertor(dict_type=type, max_seq_len=max_length, with_unknown=True)
         self._env = None
         with lmdb_file.LmdbReader(self.path) as env:
             dataset_length = int(env.get(b"num-samples"))

@@ -16,7 +16,8 @@ sums in two launches per batch, no host synchronisation - and `result()` reads t
 those of `update` on the decoded strings: the counts exactly, `ned` up to the order of its fp64 sum.  The device path needs
 `AttnConvertor.score_table()` (None when max_seq_len steps of the longest class do not fit the kernel: host path) and takes the
 first maximum of the scores themselves where `tensor2idx` takes the maximum of their softmax; the two differ only where two
-classes of a step are closer than the softmax resolves.
+classes of a step are closer than the softmax resolves.  With a CTCConvertor the same path decodes by the greedy CTC rule
+(ops.text_score_ctc: repeats collapsed, blanks dropped); everything behind the decode step is shared.
 """
 from __future__ import annotations
 
@@ -27,6 +28,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..convertor.ctc import is_ctc
 
 _KEEP = re.compile("[^A-Z^a-z^0-9^一-龥]")      # the reference's pattern, verbatim semantics: '^' itself is kept too
 
@@ -117,7 +119,11 @@ class TextAccuracy:
         if len(lens) != scores.shape[0]:
             raise ValueError(f"update_scores: {scores.shape[0]} samples but {len(lens)} ground-truth strings")
         both = _to_device(np.concatenate([codes.ravel(), lens]), dev)         # one host-to-device copy for both
-        records = ops.text_score(scores, raw, norm, conv.end_idx, conv.padding_idx, both[:codes.size].view(codes.shape), both[codes.size:])
+        gt, gt_len = both[:codes.size].view(codes.shape), both[codes.size:]
+        if is_ctc(conv):                                                      # CTCConvertor: frames, not decoding steps
+            records = ops.text_score_ctc(scores, raw, norm, gt, gt_len)
+        else:
+            records = ops.text_score(scores, raw, norm, conv.end_idx, conv.padding_idx, gt, gt_len)
         ops.text_accumulate(records, self._totals)
         return records
 

@@ -141,10 +141,16 @@ class ABIDINOModel(ArenaModule):
 # ------------------------------------------------------------------------------------------------ finetune
 class DINO_Finetune(ArenaModule):
     """Text recogniser of the finetune stage (Dino/model/dino_vision.py:134-290): ViT backbone -> Mlp "encoder" ->
-    NRTR decoder -> TFLoss.  Same constructor (a config object), parameter names and init RNG order as the reference."""
+    NRTR decoder -> TFLoss.  Same constructor (a config object), parameter names and init RNG order as the reference.
+    `decoder.type: 'CTCDecoder'` builds the CTC head instead (no reference counterpart): backbone -> CTCDecoder (frame pooling + one
+    linear layer) -> CTCLoss, with a CTCConvertor; there is no `encoder` Mlp then.  Any other value builds the NRTR recogniser."""
 
     def __init__(self, config):
         super().__init__()
+        self.ctc = getattr(config, "decoder_type", None) == "CTCDecoder"
+        if self.ctc:
+            self._init_ctc(config)
+            return
         from ..convertor.attn import AttnConvertor
         from ..decoder.nrtr_decoder import Mlp, NRTRDecoder
         from ..loss.ce_loss import TFLoss
@@ -166,16 +172,32 @@ class DINO_Finetune(ArenaModule):
             start_idx=config.decoder_start_idx, padding_idx=config.decoder_padding_idx)
         self.loss = TFLoss(ignore_index=self.label_convertor.padding_idx)
 
+    def _init_ctc(self, config):
+        from ..convertor.ctc import CTCConvertor
+        from ..decoder.ctc_decoder import CTCDecoder
+        from ..loss.ctc_loss import CTCLoss
+        from ..modules import vision_transformer as vits
+        self.label_convertor = CTCConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len or 25, with_unknown=True)
+        config.arch = config.arch.replace("deit", "vit")
+        if config.arch not in vits.__dict__:
+            raise NotImplementedError(f"Unknow architecture: {config.arch} (HIP kernels cover vit_tiny / vit_small / vit_base)")
+        self.backbone = vits.__dict__[config.arch](patch_size=config.patch_size, drop_path_rate=config.drop_path_rate)
+        config.decoder_num_classes = self.label_convertor.num_classes()
+        self.decoder = CTCDecoder(in_features=self.backbone.embed_dim, num_classes=config.decoder_num_classes)
+        self.loss = CTCLoss(blank=self.label_convertor.blank_idx, zero_infinity=True)
+
     # ------------------------------------------------------------------------------------------- arena
     def _transposed_names(self):
-        return ["backbone." + n for n in self.backbone._transposed_names()] + \
-               ["encoder." + n for n in self.encoder._transposed_names()] + \
-               ["decoder." + n for n in self.decoder._transposed_names()]
+        names = ["backbone." + n for n in self.backbone._transposed_names()]
+        if not self.ctc:
+            names += ["encoder." + n for n in self.encoder._transposed_names()]
+        return names + ["decoder." + n for n in self.decoder._transposed_names()]
 
     def attach_arena(self, arena, prefix):
         super().attach_arena(arena, prefix)
         self.backbone.attach_arena(arena, prefix + "backbone.")
-        self.encoder.attach_arena(arena, prefix + "encoder.")
+        if not self.ctc:
+            self.encoder.attach_arena(arena, prefix + "encoder.")
         self.decoder.attach_arena(arena, prefix + "decoder.")
 
     def unused_parameter_names(self):
@@ -202,14 +224,20 @@ class DINO_Finetune(ArenaModule):
         """img [N,3,32,128], img_metas = padded target indices int64 [N,T] -> (loss, attn [N,H,T,256])."""
         feat = self.extract_feat(img)
         targets_dict = {'padded_targets': img_metas}
+        if self.ctc:                                       # (no attention maps: the second value is None)
+            return self.loss(self.decoder.forward_train(feat), targets_dict), None
         out_enc = self.encoder(feat)
         out_dec, attn = self.decoder(feat, out_enc, targets_dict, train_mode=True)
         return self.loss(out_dec, targets_dict), attn
 
     def forward_test(self, img):
         feat = self.extract_feat(img)
+        if self.ctc:
+            return self.decoder.forward_test(feat)
         return self.decoder(feat, self.encoder(feat), None, train_mode=False)
 
     def forward_test_speed(self, img):
         feat = self.extract_feat(img)
+        if self.ctc:                                       # (one pass either way: nothing to stop early)
+            return self.decoder.forward_test(feat)
         return self.decoder(feat, self.encoder(feat), None, train_mode=False, test_speed=True)

@@ -801,6 +801,105 @@ def text_accumulate(records, totals):
         _call("ccd_text_accumulate", records, records.shape[0], totals[:5], totals[5:].view(F64))
 
 
+def text_score_ctc(logits, table_raw, table_norm, gt_codes, gt_len):
+    """text_score for the logits fp32 [B, T, C] of a CTC head (any sample / step stride): a frame counts where its arg-max class is
+    not the blank (class 0) and differs from the frame before.  Tables as CTCConvertor.score_table gives them; records as text_score."""
+    if logits.dim() != 3 or gt_codes.dim() != 2 or gt_codes.shape[0] != logits.shape[0] or tuple(gt_len.shape) != (logits.shape[0],):
+        raise ValueError(f"text_score_ctc: expects logits [B, T, C], gt [B, L] and gt_len [B], got {list(logits.shape)}, "
+                         f"{list(gt_codes.shape)}, {list(gt_len.shape)}")
+    if logits.shape[2] > 1 and logits.stride(2) != 1:
+        raise ValueError("text_score_ctc: the classes of a frame must be contiguous")
+    B, T, C = logits.shape
+    for name, t in (("table_raw", table_raw), ("table_norm", table_norm)):
+        if t.dim() != 2 or t.shape[0] < C or not t.is_contiguous():
+            raise ValueError(f"text_score_ctc: {name} must be a contiguous [>= {C}, width] table, got {list(t.shape)}")
+    assert gt_len.is_contiguous()
+    records = torch.empty((B, len(TEXT_RECORD)), dtype=I32, device=logits.device)
+    if B:
+        _call("ccd_text_score_ctc", logits, logits.stride(0), logits.stride(1), B, T, C, table_raw, table_raw.shape[1], table_norm,
+              table_norm.shape[1], gt_codes if gt_codes.shape[1] else None, gt_codes.stride(0), gt_codes.shape[1], gt_len, records)
+    return records
+
+
+# ------------------------------------------------------------------------------------------ CTC recognition head (kernels/ctc.h)
+CTC_MAX_STEPS, CTC_MAX_CLASSES, CTC_MAX_LABELS = 64, 128, 31         # ccd_hip.h: CCD_CTC_MAX_*
+
+
+def ctc_pool_fwd(tokens, rows=8, cols=32):
+    """tokens bf16 [N, rows * cols, E] (token = row * cols + column) -> frames bf16 [N * cols, E]: the mean over the rows."""
+    if tokens.dim() != 3 or tokens.shape[1] != rows * cols or not tokens.is_contiguous():
+        raise ValueError(f"ctc_pool_fwd: expects contiguous tokens [N, {rows * cols}, E], got {list(tokens.shape)}")
+    N, _, E = tokens.shape
+    frames = torch.empty((N * cols, E), dtype=BF16, device=tokens.device)
+    if N:
+        _call("ccd_ctc_pool_fwd", tokens, frames, N, rows, cols, E)
+    return frames
+
+
+def ctc_pool_bwd(d_frames, rows=8, cols=32):
+    """d_frames bf16 [N * cols, E] -> d_tokens bf16 [N, rows * cols, E] = d_frames / rows at every row."""
+    if d_frames.dim() != 2 or d_frames.shape[0] % cols or not d_frames.is_contiguous():
+        raise ValueError(f"ctc_pool_bwd: expects contiguous d_frames [N * {cols}, E], got {list(d_frames.shape)}")
+    N, E = d_frames.shape[0] // cols, d_frames.shape[1]
+    d_tokens = torch.empty((N, rows * cols, E), dtype=BF16, device=d_frames.device)
+    if N:
+        _call("ccd_ctc_pool_bwd", d_frames, d_tokens, N, rows, cols, E)
+    return d_tokens
+
+
+def _ctc_rows(logits, C, T, targets, name):
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] % T or not 1 <= C <= logits.shape[1]:
+        raise ValueError(f"{name}: expects logits [B * {T}, >= {C}] with dense rows, got {list(logits.shape)}")
+    B = logits.shape[0] // T
+    if targets.dim() != 2 or targets.shape[0] != B or not targets.is_contiguous():
+        raise ValueError(f"{name}: expects contiguous targets [{B}, Lmax], got {list(targets.shape)}")
+    return B
+
+
+def _ctc_ws_elements(B, T):
+    return (_lib.get().ccd_ctc_loss_ws_bytes(B, T) + 7) // 8
+
+
+def ctc_loss_fwd(logits, C, targets, T):
+    """logits fp32 [B * T, ld] (C valid columns, class 0 = blank), targets int64 [B, Lmax] zero-padded
+    -> (nll fp32 [B], acc fp32 [3] = {sum nll / max(L, 1) over the feasible samples, B, infeasible samples}, workspace for
+    ctc_loss_bwd).  The loss of torch.nn.CTCLoss(reduction='mean', zero_infinity=True) is acc[0] / acc[1]."""
+    B = _ctc_rows(logits, C, T, targets, "ctc_loss_fwd")
+    nll = torch.empty(B, dtype=F32, device=logits.device)
+    acc = torch.zeros(3, dtype=F32, device=logits.device)
+    ws = torch.empty(_ctc_ws_elements(B, T), dtype=F64, device=logits.device)
+    _call("ccd_ctc_loss_fwd", logits, logits.stride(0), B, T, C, targets if targets.shape[1] else None, targets.shape[1], nll, acc, ws)
+    return nll, acc, ws
+
+
+def ctc_loss_bwd(logits, C, targets, T, ws, upstream=None, ldd=None):
+    """-> d_logits bf16 [B * T, ldd] (default ldd: C rounded up to 8): (softmax - class posterior) * upstream / (max(L, 1) * B), zero
+    behind column C and for an infeasible sample.  upstream: fp32 device scalar [1] or None (= 1)."""
+    B = _ctc_rows(logits, C, T, targets, "ctc_loss_bwd")
+    ldd = (C + 7) // 8 * 8 if ldd is None else int(ldd)
+    if ws.dtype != F64 or not ws.is_contiguous() or ws.numel() != _ctc_ws_elements(B, T):
+        raise ValueError(f"ctc_loss_bwd: ws must be the workspace ctc_loss_fwd returned for B = {B}, T = {T}")
+    assert upstream is None or upstream.numel() == 1
+    d = torch.empty((B * T, ldd), dtype=BF16, device=logits.device)
+    _call("ccd_ctc_loss_bwd", logits, logits.stride(0), B, T, C, targets if targets.shape[1] else None, targets.shape[1], ws, upstream,
+          d, ldd)
+    return d
+
+
+def ctc_greedy(logits):
+    """logits fp32 [B, T, C] (any sample / step stride) -> (path int32 [B, T] left-aligned, -1-padded; length int32 [B]; conf fp32
+    [B, T]): arg-max class per frame (first maximum), repeats collapsed, blanks dropped; conf = the softmax probability of the first
+    frame of each kept run."""
+    if logits.dim() != 3 or (logits.shape[2] > 1 and logits.stride(2) != 1):
+        raise ValueError(f"ctc_greedy: expects logits [B, T, C] with contiguous classes, got {list(logits.shape)}, strides {logits.stride()}")
+    B, T, C = logits.shape
+    path = torch.empty((B, T), dtype=I32, device=logits.device)
+    length = torch.empty(B, dtype=I32, device=logits.device)
+    conf = torch.empty((B, T), dtype=F32, device=logits.device)
+    _call("ccd_ctc_greedy", logits, logits.stride(0), logits.stride(1), B, T, C, path, length, conf)
+    return path, length, conf
+
+
 class SsimFn(torch.autograd.Function):
     """apply(window, taps, size_average, img1, img2[, img3]) -> mean (0-dim) or per-image means [N]; backward on the kernels."""
 

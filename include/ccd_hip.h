@@ -416,6 +416,50 @@ int ccd_text_score(const float* scores, long sample_stride, long step_stride, in
                    int raw_width, const int* table_norm, int norm_width, int end_idx, int pad_idx, const int* gt, long gt_stride,
                    int gt_cols, const int* gt_len, int* records, void* stream);
 int ccd_text_accumulate(const int* records, int batch, long* totals, double* total_ned, void* stream);
+/* The same records from the logits of a CTC head (ABI 20; no reference counterpart: the reference has no CTC head).  scores fp32
+ * [batch, steps, classes] are frames; the class of a frame is its first maximum, a frame counts where its class is not the blank
+ * (class 0) and differs from the frame before.  There is no end class and no padding class; tables, ground truth, records, error
+ * codes and limits as for ccd_text_score (row 0 of the tables, the blank, is never read).  The records feed ccd_text_accumulate. */
+int ccd_text_score_ctc(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, const int* table_raw,
+                       int raw_width, const int* table_norm, int norm_width, const int* gt, long gt_stride, int gt_cols, const int* gt_len,
+                       int* records, void* stream);
+
+/* ---------------------------------------------------------------- CTC recognition head (ABI 20)
+ * No reference counterpart (the reference has no CTC head); the semantics are those of
+ * torch.nn.CTCLoss(blank=0, reduction='mean', zero_infinity=True) applied to log_softmax(logits).
+ * ccd_ctc_pool_fwd: tokens bf16 [images, rows * cols, E] (token = row * cols + column) -> frames bf16 [images * cols, E], frame c = the
+ *   mean over the rows of column c, summed in fp32.  ccd_ctc_pool_bwd: d_tokens bf16 [images, rows * cols, E] = d_frames / rows at
+ *   every row.  E % 8 == 0, rows 1..64 (CCD_ESHAPE otherwise); images == 0 is a no-op.
+ * ccd_ctc_loss_fwd, one wavefront per sample, lane s = state s of the extended label sequence:
+ *   logits   fp32 [batch * steps, ldl], `classes` valid columns (the columns behind them are never read), class 0 = blank;
+ *   targets  int64 [batch, max_len], zero-padded: the label length L is the number of leading non-zero entries (found on the device);
+ *   nll      fp32 [batch]: -log p(target | logits), 0 for an infeasible sample: L + adjacent equal labels > steps, a label outside
+ *            [1, classes) (never used as an index), or no alignment of finite probability;
+ *   acc      fp32 [3] = {sum of nll / max(L, 1) over the feasible samples, batch, infeasible samples}: the loss is acc[0] / acc[1].
+ *            Folded by one workgroup in a fixed order, no atomics: the same inputs give the same bits;
+ *   ws       ccd_ctc_loss_ws_bytes(batch, steps) bytes, 8-byte aligned: the forward variables, the frames' log-sum-exp and the
+ *            per-sample result, read by ccd_ctc_loss_bwd.
+ * ccd_ctc_loss_bwd: d_logits bf16 [batch * steps, ldd] = (softmax[t, c] - posterior of class c at frame t) * upstream / (max(L, 1) *
+ *   batch), columns classes..ldd-1 and the rows of an infeasible sample zero; upstream = optional device scalar (NULL: 1).  The
+ *   posterior of a class is the sum over the states that carry it (the blanks, a repeated character), formed in a fixed order.
+ * ccd_ctc_greedy: arg-max class per frame (first maximum), repeats collapsed, blanks dropped -> path int32 [batch, steps]
+ *   left-aligned, padded with -1; length int32 [batch]; conf fp32 [batch, steps] = the softmax probability of the first frame of each
+ *   kept run, padded with 0.  logits fp32 [batch, steps, classes] with sample / step strides in elements.
+ * The recursion runs in the log domain in fp64 (kernels/ctc.h says why); log-sum-exp of nothing is -inf, never NaN.
+ * batch == 0 is a no-op.  CCD_EINVAL: a missing pointer, a negative size or stride; CCD_ESHAPE: classes outside
+ * 1..CCD_CTC_MAX_CLASSES, steps outside 1..CCD_CTC_MAX_STEPS, max_len > CCD_CTC_MAX_LABELS, ldl or ldd < classes. */
+#define CCD_CTC_MAX_STEPS 64
+#define CCD_CTC_MAX_CLASSES 128
+#define CCD_CTC_MAX_LABELS 31
+int ccd_ctc_pool_fwd(const ccd_bf16* tokens, ccd_bf16* frames, int images, int rows, int cols, int E, void* stream);
+int ccd_ctc_pool_bwd(const ccd_bf16* d_frames, ccd_bf16* d_tokens, int images, int rows, int cols, int E, void* stream);
+long ccd_ctc_loss_ws_bytes(int batch, int steps);
+int ccd_ctc_loss_fwd(const float* logits, long ldl, int batch, int steps, int classes, const int64_t* targets, int max_len, float* nll,
+                     float* acc, void* ws, void* stream);
+int ccd_ctc_loss_bwd(const float* logits, long ldl, int batch, int steps, int classes, const int64_t* targets, int max_len, const void* ws,
+                     const float* upstream, ccd_bf16* d_logits, long ldd, void* stream);
+int ccd_ctc_greedy(const float* logits, long sample_stride, long step_stride, int batch, int steps, int classes, int* path, int* length,
+                   float* conf, void* stream);
 
 /* ---------------------------------------------------------------- DINOHead pieces, vit.py:313,326 */
 int ccd_l2norm_fwd(const ccd_bf16* x, ccd_bf16* y, float* inv, int max_rows, const int* d_rows, int rows_mul, int D,

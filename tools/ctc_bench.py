@@ -1,0 +1,176 @@
+#!/usr/bin/env python3
+"""Time the CTC recognition head (kernels/ctc.h, ccd_amd/decoder/ctc_decoder.py) on the GPU.
+
+    python tools/ctc_bench.py [--iters 30] [--rounds 5] [--out profiles/ctc_head.json]
+
+Three cases, each in a process of its own under its own time limit; the next one starts only if the one before ended well:
+  loss    ccd_ctc_loss_fwd + _bwd on logits fp32 [512 * 32, 128] (92 classes), words of 3..15 characters, against
+          F.log_softmax + F.ctc_loss(reduction='mean', zero_infinity=True) forward + backward of torch on the same GPU (the yardstick);
+  step    one finetune step (forward, backward, AdamW) at B = 512, vit_small: CTC head and NRTR head in the same process, rounds
+          alternating;
+  infer   inference images/s at B = 512, vit_small, eval mode: CTC head (one pass) against NRTR greedy decoding (25 steps).
+Warm-up first, HIP events around every timed call, a figure is the median of the round medians with the lowest and highest
+round.  No threshold is set; the file records what was measured.  `--case NAME` runs one case and prints its JSON line."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+B, T, C = 512, 32, 92
+LIMITS = {"loss": 240, "step": 420, "infer": 300}           # seconds per case
+
+
+def event_ms(fn, iters):
+    import torch
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return statistics.median(a.elapsed_time(b) for a, b in ev)
+
+
+def summary(rounds):
+    return {"median_ms": round(statistics.median(rounds), 4), "lowest_ms": round(min(rounds), 4), "highest_ms": round(max(rounds), 4)}
+
+
+def _targets(conv, seed):
+    import numpy as np
+    rs = np.random.RandomState(seed)
+    words = ["".join(conv.idx2char[1 + c] for c in rs.randint(0, 90, size=int(rs.randint(3, 16)))) for _ in range(B)]
+    return conv.str2tensor(words)
+
+
+def case_loss(a):
+    import torch
+    import torch.nn.functional as F
+    from ccd_amd import ops
+    from ccd_amd.convertor.ctc import CTCConvertor
+    dev = torch.device("cuda")
+    targets = _targets(CTCConvertor(), 1).to(dev)
+    g = torch.Generator().manual_seed(2)
+    buf = torch.zeros(B * T, 128)
+    buf[:, :C] = torch.randn(B * T, C, generator=g) * 2.0
+    buf = buf.to(dev)
+    one = torch.ones(1, device=dev)
+
+    def ours():
+        _, _, ws = ops.ctc_loss_fwd(buf, C, targets, T)
+        ops.ctc_loss_bwd(buf, C, targets, T, ws, one, 128)
+
+    lengths = (targets != 0).sum(1)
+    flat = targets[targets != 0]
+    frames = torch.full((B,), T, dtype=torch.long, device=dev)
+    x = buf[:, :C].reshape(B, T, C).contiguous().requires_grad_(True)
+
+    def torchs():
+        x.grad = None
+        lp = F.log_softmax(x, -1).transpose(0, 1)
+        F.ctc_loss(lp, flat, frames, lengths, blank=0, reduction="mean", zero_infinity=True).backward()
+
+    # the two must agree before either is timed
+    nll, acc, ws = ops.ctc_loss_fwd(buf, C, targets, T)
+    torchs()
+    d = ops.ctc_loss_bwd(buf, C, targets, T, ws, one, 128)[:, :C].float().view(B, T, C)
+    ref = F.ctc_loss(F.log_softmax(x, -1).transpose(0, 1), flat, frames, lengths, blank=0, reduction="mean", zero_infinity=True)
+    out = {"shape": [B, T, C], "loss_kernel": float(acc[0] / acc[1]), "loss_torch": float(ref),
+           "max_gradient_difference": float((d - x.grad).abs().max())}
+    ours_r, torch_r = [], []
+    for _ in range(a.rounds):
+        ours_r.append(event_ms(ours, a.iters))
+        torch_r.append(event_ms(torchs, a.iters))
+    o, t = summary(ours_r), summary(torch_r)
+    out.update({"kernels_fwd_bwd": o, "torch_log_softmax_ctc_loss_fwd_bwd": t, "torch_over_kernels": round(t["median_ms"] / o["median_ms"], 2),
+                "kernels_not_slower_beyond_spread": o["highest_ms"] <= t["lowest_ms"]})
+    return out
+
+
+def _models(dropout=None):
+    import torch
+    from ccd_amd import finetune as ft
+    dev = torch.device("cuda")
+    torch.manual_seed(0)
+    cfg = ft.FinetuneConfig()
+    cfg.decoder_type = "CTCDecoder"
+    return ft.build_model(cfg, dev, dropout=dropout), ft.build_model(ft.FinetuneConfig(), dev, dropout=dropout)
+
+
+def case_step(a):
+    import torch
+    from ccd_amd import finetune as ft
+    dev = torch.device("cuda")
+    ctc, nrtr = _models()
+    img = torch.randn(B, 3, 32, 128, generator=torch.Generator().manual_seed(3)).to(dev)
+    words = ["".join(ctc.label_convertor.idx2char[1 + (i * 7 + j) % 90] for j in range(3 + i % 13)) for i in range(B)]
+    sides = []
+    for model in (ctc, nrtr):
+        sides.append((model, ft.make_optimizer(model), model.label_convertor.str2tensor(words).to(dev)))
+    rounds = ([], [])
+    iters = max(3, a.iters // 3)
+    for _ in range(a.rounds):
+        for k, (model, opt, tg) in enumerate(sides):
+            rounds[k].append(event_ms(lambda: ft.training_iteration(model, opt, img, tg, 1e-4), iters))
+    c, n = summary(rounds[0]), summary(rounds[1])
+    return {"batch": B, "arch": "vit_small", "ctc_step": c, "nrtr_step": n, "nrtr_over_ctc": round(n["median_ms"] / c["median_ms"], 2)}
+
+
+def case_infer(a):
+    import torch
+    dev = torch.device("cuda")
+    ctc, nrtr = _models(dropout=0.0)
+    img = torch.randn(B, 3, 32, 128, generator=torch.Generator().manual_seed(4)).to(dev)
+    rounds = ([], [])
+    iters = max(3, a.iters // 3)
+    with torch.no_grad():
+        for model in (ctc, nrtr):
+            model.eval()
+        for _ in range(a.rounds):
+            for k, model in enumerate((ctc, nrtr)):
+                rounds[k].append(event_ms(lambda: model(img, None, return_loss=False), iters))
+    c, n = summary(rounds[0]), summary(rounds[1])
+    return {"batch": B, "arch": "vit_small", "ctc_forward": c, "nrtr_greedy": n, "ctc_images_per_s": round(B / (c["median_ms"] * 1e-3)),
+            "nrtr_images_per_s": round(B / (n["median_ms"] * 1e-3))}
+
+
+CASES = {"loss": case_loss, "step": case_step, "infer": case_infer}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--case", choices=sorted(CASES), default=None)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.case is not None:
+        import torch
+        assert torch.cuda.is_available(), "ctc_bench needs an MI355X"
+        print(json.dumps({a.case: CASES[a.case](a)}))
+        return
+    out = {"iters": a.iters, "rounds": a.rounds, "unit": "ms per call, HIP events (median of round medians; lowest and highest round)"}
+    for name in ("loss", "step", "infer"):
+        # a fresh process per case under its own time limit; a case that fails or runs out of time ends the run
+        run = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name, "--iters", str(a.iters), "--rounds", str(a.rounds)],
+                             capture_output=True, text=True, timeout=LIMITS[name])
+        if run.returncode != 0:
+            sys.stderr.write(run.stdout[-2000:] + run.stderr[-4000:])
+            sys.exit(f"ctc_bench: case {name} ended with status {run.returncode}; nothing further was started")
+        out.update(json.loads(run.stdout.strip().splitlines()[-1]))
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(json.dumps(out, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -26,6 +26,7 @@ from Dino.model.dino_vision import DINO_Finetune
 from Dino.modules import utils
 from Dino.utils.utils import Config, Logger
 from ccd_amd import finetune as ft
+from ccd_amd.convertor.ctc import is_ctc
 from ccd_amd.parallel import DataParallel
 
 
@@ -42,7 +43,8 @@ class SyntheticLabelledSet(torch.utils.data.Dataset):
     def __getitem__(self, i):
         g = torch.Generator().manual_seed(self.seed * 1_000_003 + i)
         n = int(torch.randint(3, 16, (1,), generator=g))
-        word = "".join(self.convertor.idx2char[int(c)] for c in torch.randint(0, 90, (n,), generator=g))
+        first = 1 if is_ctc(self.convertor) else 0                         # (a CTCConvertor's alphabet starts behind the blank)
+        word = "".join(self.convertor.idx2char[first + int(c)] for c in torch.randint(0, 90, (n,), generator=g))
         return torch.randn(3, 32, 128, generator=g), self.convertor.str2tensor([word])
 
 
@@ -56,6 +58,8 @@ def _loader(config, convertor, world, rank):
                   max_length=int(config.decoder_max_seq_len or 25), type=config.dataset_charset_type or "DICT90",
                   data_portion=float(config.dataset_portion or 1.0), is_training=True,
                   data_aug=bool(config.dataset_data_aug))             # the YAML's `data_aug` (dataset_pretrain.py:68-158)
+        if is_ctc(convertor):                                         # CTC head: targets are the classes, zero-padded
+            kw["label_convertor"] = convertor
         parts = [ImageDataset(path=p, **kw) for p in _lmdb_dirs(config.dataset_train_roots)]
         ds = parts[0] if len(parts) == 1 else torch.utils.data.ConcatDataset(parts)
         sampler = torch.utils.data.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True) if world > 1 else None
@@ -80,10 +84,11 @@ def word_accuracy(model, images, labels):
         probs = model(images, None, return_loss=False)
     mod.train()
     idx, _ = mod.label_convertor.tensor2idx(torch.log(probs.clamp_min(1e-30)))
-    truth = []
-    for row in labels.tolist():
-        body = row[1:]
-        truth.append(body[:body.index(mod.label_convertor.end_idx)] if mod.label_convertor.end_idx in body else body)
+    if is_ctc(mod.label_convertor):                      # CTC targets: the classes, zero-padded
+        truth = [row[:row.index(0)] if 0 in row else row for row in labels.tolist()]
+    else:                                                # <BOS> classes <EOS> <PAD>...
+        end = mod.label_convertor.end_idx
+        truth = [row[1:][:row[1:].index(end)] if end in row[1:] else row[1:] for row in labels.tolist()]
     return sum(int(a == b) for a, b in zip(idx, truth)) / max(1, len(truth))
 
 
