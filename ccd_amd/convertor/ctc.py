@@ -5,6 +5,10 @@ classes.  A target row is the word's classes followed by zeros, cut to `max_seq_
 row is its count of leading non-zero entries (what ccd_ctc_loss_fwd reads on the device).  Decoding is the greedy CTC rule: the
 arg-max class of every frame (first maximum), repeats collapsed, blanks dropped.  The reference has no CTC head; the surface follows
 AttnConvertor's so that DINO_Finetune, TextAccuracy, train_finetune.py and test.py take either.
+
+`beam_width` > 0 asks for CTC prefix beam search (ops.ctc_beam_search) where words are scored (TextAccuracy) and in `tensor2nbest`,
+which returns an n-best list with the log-probability of each word summed over its alignments; 0, the default, is the greedy rule
+everywhere, and `tensor2idx` is the greedy rule whatever the width.
 """
 from __future__ import annotations
 
@@ -20,11 +24,12 @@ def is_ctc(convertor):
 
 
 class CTCConvertor:
-    """CTCConvertor(dict_type='DICT90', with_unknown=True, max_seq_len=25, lower=False) - see the module docstring."""
+    """CTCConvertor(dict_type='DICT90', with_unknown=True, max_seq_len=25, lower=False, beam_width=0) - see the module docstring."""
 
     dicts = {name: tuple(chars) for name, chars in ALPHABETS.items()}
 
-    def __init__(self, dict_type="DICT90", dict_file=None, dict_list=None, with_unknown=True, max_seq_len=25, lower=False, **_ignored):
+    def __init__(self, dict_type="DICT90", dict_file=None, dict_list=None, with_unknown=True, max_seq_len=25, lower=False, beam_width=0,
+                 **_ignored):
         if dict_file is not None:
             alphabet = _read_alphabet_file(dict_file)
         elif dict_list is not None:
@@ -36,6 +41,10 @@ class CTCConvertor:
         if len(set(alphabet)) != len(alphabet):
             raise AssertionError("dictionary holds a character twice")
         self.with_unknown, self.max_seq_len, self.lower = bool(with_unknown), int(max_seq_len), bool(lower)
+        self.beam_width = int(beam_width or 0)
+        from ..ops import CTC_MAX_BEAM
+        if not 0 <= self.beam_width <= CTC_MAX_BEAM:
+            raise ValueError(f"beam_width must lie in 0..{CTC_MAX_BEAM} (0: greedy decoding), got {beam_width}")
         self.blank_idx = 0
         self.idx2char = ["<BLK>"] + alphabet
         self.unknown_idx = None
@@ -119,3 +128,21 @@ class CTCConvertor:
         indexes = [cls_np[i][keep[i]].tolist() for i in range(cls_np.shape[0])]
         scores = [conf_np[i][keep[i]].tolist() for i in range(cls_np.shape[0])]
         return indexes, scores
+
+    @torch.no_grad()
+    def tensor2nbest(self, outputs, beam_width=None, nbest=1, normalized=True):
+        """[N, T, C] frame scores on the device - probabilities (normalized=True: what CTCDecoder.forward_test returns) or logits
+        -> (indexes, log_probs) by CTC prefix beam search of width `beam_width` (default: the convertor's own, which must then be
+        > 0): indexes[i] holds up to `nbest` index lists, best first; log_probs is a float tensor [N, nbest], the log of each word's
+        probability summed over the alignments the beam kept, -inf where a slot is empty."""
+        from .. import ops
+        width = self.beam_width if beam_width is None else int(beam_width)
+        nbest = int(nbest)
+        if width < 1:
+            raise ValueError("tensor2nbest: needs a beam_width >= 1 (the convertor's is 0: greedy decoding)")
+        if not 1 <= nbest <= width:
+            raise ValueError(f"tensor2nbest: nbest must lie in 1..beam_width = {width}, got {nbest}")
+        paths, lengths, scores = ops.ctc_beam_search(outputs.float(), width, normalized=normalized)
+        paths, lengths = paths[:, :nbest].cpu().numpy(), lengths[:, :nbest].cpu().numpy()
+        indexes = [[paths[i, r, :lengths[i, r]].tolist() for r in range(nbest) if lengths[i, r] >= 0] for i in range(paths.shape[0])]
+        return indexes, scores[:, :nbest].cpu()

@@ -24,6 +24,7 @@
 #include "kernels/segmetric.h"
 #include "kernels/textscore.h"
 #include "kernels/ctc.h"
+#include "kernels/ctc_beam.h"
 #include "kernels/datapipe.h"
 #include "kernels/embed.h"
 #include "kernels/head.h"
@@ -338,7 +339,7 @@ static int ccd_seg_prepare(int images, long pixels, int* cm, int* status, int* c
 
 extern "C" {
 
-int ccd_abi_version(void) { return 20; }   // 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
+int ccd_abi_version(void) { return 21; }   // 21: ccd_ctc_beam_search, ccd_text_score_paths (CTC prefix beam search, n-best word scores); 20: ccd_ctc_pool_fwd / _bwd, ccd_ctc_loss_fwd / _bwd, ccd_ctc_greedy, ccd_text_score_ctc (the CTC recognition head); 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
 const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi16"; }
 int ccd_policy_set(const char* key, int value) {
     CCD_CHECK(key, CCD_EINVAL);
@@ -1303,7 +1304,7 @@ int ccd_text_score(const float* scores, long sample_stride, long step_stride, in
               norm_width <= ccd::TS_MAX_WIDTH, CCD_ESHAPE);
     CCD_CHECK((long)steps * norm_width <= ccd::TS_COLS, CCD_ESHAPE);          // the longest normalised prediction: two columns per lane
     CCD_CHECK(end_idx >= 0 && end_idx < classes, CCD_ESHAPE);      // (a pad_idx no step can take skips nothing: a decoder without a padding output)
-    CCD_LAUNCH(ccd::text_score_kernel<false>, dim3((unsigned)((batch + ccd::TS_WAVES - 1) / ccd::TS_WAVES)), dim3(ccd::TS_THREADS), 0, stream, scores,
+    CCD_LAUNCH(ccd::text_score_kernel<ccd::TS_ATTN>, dim3((unsigned)((batch + ccd::TS_WAVES - 1) / ccd::TS_WAVES)), dim3(ccd::TS_THREADS), 0, stream, scores,
                sample_stride, step_stride, batch, steps, classes, table_raw, raw_width, table_norm, norm_width, end_idx, pad_idx, gt,
                gt_stride, gt_cols, gt_len, records);
     return ccd_rt_last_error();
@@ -1318,9 +1319,24 @@ int ccd_text_score_ctc(const float* scores, long sample_stride, long step_stride
     CCD_CHECK(steps >= 1 && classes >= 1 && raw_width >= 1 && raw_width <= ccd::TS_MAX_WIDTH && norm_width >= 1 &&
               norm_width <= ccd::TS_MAX_WIDTH, CCD_ESHAPE);
     CCD_CHECK((long)steps * norm_width <= ccd::TS_COLS, CCD_ESHAPE);
-    CCD_LAUNCH(ccd::text_score_kernel<true>, dim3((unsigned)((batch + ccd::TS_WAVES - 1) / ccd::TS_WAVES)), dim3(ccd::TS_THREADS), 0, stream, scores,
+    CCD_LAUNCH(ccd::text_score_kernel<ccd::TS_CTC>, dim3((unsigned)((batch + ccd::TS_WAVES - 1) / ccd::TS_WAVES)), dim3(ccd::TS_THREADS), 0, stream, scores,
                sample_stride, step_stride, batch, steps, classes, table_raw, raw_width, table_norm, norm_width, -1, -1, gt,
                gt_stride, gt_cols, gt_len, records);
+    return ccd_rt_last_error();
+}
+int ccd_text_score_paths(const int* paths, long path_stride, int batch, int steps, int classes, const int* table_raw, int raw_width,
+                         const int* table_norm, int norm_width, const int* gt, long gt_stride, int gt_cols, const int* gt_len, int* records,
+                         void* stream) {
+    CCD_CHECK(batch >= 0, CCD_EINVAL);
+    if (batch == 0) return CCD_OK;
+    CCD_CHECK(paths && table_raw && table_norm && gt_len && records && (gt || gt_cols == 0), CCD_EINVAL);
+    CCD_CHECK(path_stride >= 0 && gt_stride >= 0 && gt_cols >= 0, CCD_EINVAL);
+    CCD_CHECK(steps >= 1 && classes >= 1 && raw_width >= 1 && raw_width <= ccd::TS_MAX_WIDTH && norm_width >= 1 &&
+              norm_width <= ccd::TS_MAX_WIDTH, CCD_ESHAPE);
+    CCD_CHECK((long)steps * norm_width <= ccd::TS_COLS, CCD_ESHAPE);
+    CCD_LAUNCH(ccd::text_score_kernel<ccd::TS_PATHS>, dim3((unsigned)((batch + ccd::TS_WAVES - 1) / ccd::TS_WAVES)), dim3(ccd::TS_THREADS), 0, stream,
+               paths, path_stride, 1L, batch, steps, classes, table_raw, raw_width, table_norm, norm_width, -1, -1, gt, gt_stride, gt_cols,
+               gt_len, records);
     return ccd_rt_last_error();
 }
 int ccd_text_accumulate(const int* records, int batch, long* totals, double* total_ned, void* stream) {
@@ -1332,7 +1348,8 @@ int ccd_text_accumulate(const int* records, int batch, long* totals, double* tot
 }
 
 // ------------------------------------------------------------------------------- CTC recognition head (kernels/ctc.h)
-static_assert(CCD_CTC_MAX_STEPS == ccd::CTC_MAX_T && CCD_CTC_MAX_CLASSES == ccd::CTC_MAX_C && CCD_CTC_MAX_LABELS == ccd::CTC_MAX_L, "");
+static_assert(CCD_CTC_MAX_STEPS == ccd::CTC_MAX_T && CCD_CTC_MAX_CLASSES == ccd::CTC_MAX_C && CCD_CTC_MAX_LABELS == ccd::CTC_MAX_L &&
+              CCD_CTC_MAX_BEAM == ccd::CTC_MAX_BEAM, "");
 static int ccd_ctc_pool_launch(bool bwd, const ccd_bf16* src, ccd_bf16* dst, int images, int rows, int cols, int E, void* stream) {
     CCD_CHECK(images >= 0 && rows >= 0 && cols >= 0 && E >= 0, CCD_EINVAL);
     if (images == 0) return CCD_OK;
@@ -1395,6 +1412,17 @@ int ccd_ctc_greedy(const float* logits, long sample_stride, long step_stride, in
     CCD_CHECK(logits && path && length && conf, CCD_EINVAL);
     CCD_LAUNCH(ccd::ctc_greedy_kernel, dim3((unsigned)((batch + ccd::CTC_WAVES - 1) / ccd::CTC_WAVES)), dim3(ccd::CTC_THREADS), 0, stream,
                logits, sample_stride, step_stride, batch, steps, classes, path, length, conf);
+    return ccd_rt_last_error();
+}
+int ccd_ctc_beam_search(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
+                        int beam, int* paths, int* lengths, float* hyp_scores, void* stream) {
+    CCD_CHECK(batch >= 0 && sample_stride >= 0 && step_stride >= 0, CCD_EINVAL);
+    CCD_CHECK(beam >= 1 && beam <= ccd::CTC_MAX_BEAM && steps >= 1 && steps <= ccd::CTC_MAX_T && classes >= 2 && classes <= ccd::CTC_MAX_C &&
+              (normalized == 0 || normalized == 1), CCD_ESHAPE);
+    if (batch == 0) return CCD_OK;
+    CCD_CHECK(scores && paths && lengths && hyp_scores, CCD_EINVAL);
+    CCD_LAUNCH(ccd::ctc_beam_kernel, dim3((unsigned)((batch + ccd::CTC_WAVES - 1) / ccd::CTC_WAVES)), dim3(ccd::CTC_THREADS), 0, stream,
+               scores, sample_stride, step_stride, batch, steps, classes, normalized, beam, paths, lengths, hyp_scores);
     return ccd_rt_last_error();
 }
 

@@ -1,0 +1,236 @@
+// ctc_beam.h - CTC prefix beam search for the CTC head (ccd_ctc_beam_search):
+//   ctc_beam_kernel   frame scores fp32 [B, T, C] (logits or probabilities) -> the W most probable words with the log of their
+//                     probability summed over alignments: paths int32 [B, W, T], lengths int32 [B, W], scores fp32 [B, W], by rank.
+// Best-path decoding (ctc_greedy_kernel) picks the most probable alignment; this picks the most probable words.  The semantics
+// are restated in numpy in tests/ctc_beam_np.py, which is the specification:
+//   a beam entry is a prefix of classes 1..C-1 with pb / pnb, the log mass of its alignments ending in the blank / in a non-blank;
+//   the start is the empty prefix, pb = 0, pnb = -inf.  Per frame, tot_i = logaddexp(pb_i, pnb_i):
+//     stay (i, 0)    same prefix: pb' = tot_i + lp[0], pnb' = pnb_i + lp[last_i] (-inf for the empty prefix)
+//     extend (i, c)  prefix_i + c: pb' = -inf, pnb' = (c == last_i ? pb_i : tot_i) + lp[c]
+//     merge          an extend candidate that spells the prefix of a live entry j is log-added into the pnb' of j's stay candidate
+//                    and disappears (prefixes are unique: j absorbs at most one, no two extend candidates coincide)
+//     select         the W best candidates of finite score logaddexp(pb', pnb'), by (score descending, k = rank * C + class ascending).
+//
+// Lane mapping: ONE WAVEFRONT PER SAMPLE, as the loss kernels.  Lane l owns the classes l and l + 64 in every role: it loads their
+// scores, keeps their log-probabilities in registers and scans the candidates (i, l) and (i, l + 64) of every entry i - at most
+// 2 W = 32 candidates per lane, none of them stored: a candidate's score is one add of the entry's pb or tot (read from LDS at a
+// wave-uniform address: a broadcast) and the lane's own lp, minus the candidates a 64-bit mask per (entry, half) marks as merged.
+// Selection is W rounds of a wave arg-max on the key (score, k): each lane folds the candidates it has not given away yet (a 32-bit
+// mask in a register), six xor-shuffle steps fold the lanes.  The entries (pb, pnb, length, last class) and the prefixes - bytes,
+// classes are < 128; two buffers of W x 64, swapped per frame - live in LDS: 4.1 KB per wave, 16.5 KB per workgroup.
+// The merge test: the 16 x 16 pairs (i, j) four to a lane, prefiltered on len_j = len_i + 1 and on the last class of prefix_i; the
+// survivors (a ballot mask, so the walk is wave-uniform) compare the len_i positions one per lane and a second ballot decides.
+//
+// Every loop that shuffles or ballots has a wave-uniform trip count (T, W, the live entries, the bits of a ballot mask); no lane
+// of a live wave leaves before the last shuffle; no atomics: the same input gives the same bits.
+//
+// Arithmetic is fp64 (ctc_real) throughout, log-softmax included: the selection compares scores whose neighbours lie 1e-5 nats
+// apart at |score| ~ 150, which is one fp32 ulp.  log-sum-exp of nothing is -inf, never NaN; values are finite or -inf, and -inf
+// masks a class.  The sum over the classes of a frame runs in ascending class order (every lane adds the same 128 LDS words).
+// What the software fp64 exp / log and the W-fold rescan cost on the device: tools/ctc_bench.py, case `beam`.
+#pragma once
+
+#include "ctc.h"
+
+namespace ccd {
+
+constexpr int CTC_MAX_BEAM = 16;
+
+// log(exp(a) + exp(b)); -inf when both are
+__device__ __forceinline__ ctc_real ctc_lae(ctc_real a, ctc_real b) {
+    const ctc_real m = a > b ? a : b, lo = a > b ? b : a;
+    if (m == ctc_neg_inf()) return m;
+    return m + ::log1p(::exp(lo - m));
+}
+
+struct CtcBeamWave {
+    ctc_real lp[CTC_MAX_C];                                      // this frame: first the terms of the sum, then the log-probabilities
+    ctc_real pb[CTC_MAX_BEAM], pnb[CTC_MAX_BEAM], tot[CTC_MAX_BEAM];
+    ctc_real stay_pb[CTC_MAX_BEAM], stay_pnb[CTC_MAX_BEAM], stay_score[CTC_MAX_BEAM];
+    unsigned long long merged[CTC_MAX_BEAM][2];                  // bit c & 63 of [i][c >> 6]: extend candidate (i, c) was merged away
+    int len[CTC_MAX_BEAM], last[CTC_MAX_BEAM], absorb[CTC_MAX_BEAM];     // last: 0 for the empty prefix; absorb: the entry whose
+    unsigned char prefix[2][CTC_MAX_BEAM][CTC_MAX_T];            // extension this entry's stay candidate takes in, or -1
+};
+
+// grid = ceil(B / CTC_WAVES).  The launcher has checked 1 <= W <= CTC_MAX_BEAM, 1 <= T <= CTC_MAX_T, 2 <= C <= CTC_MAX_C.
+__global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __restrict__ scores, long sample_stride, long step_stride, int B,
+                                                               int T, int C, int normalized, int W, int* __restrict__ paths,
+                                                               int* __restrict__ lengths, float* __restrict__ hyp_scores) {
+    __shared__ CtcBeamWave waves[CTC_WAVES];
+    const int lane = lane_id(), b = blockIdx.x * CTC_WAVES + wave_id();
+    if (b >= B) return;                                                    // (whole waves; no workgroup barrier below)
+    CtcBeamWave& s = waves[wave_id()];
+    const float* const x = scores + (long)b * sample_stride;
+    const int c0 = lane, c1 = lane + 64;
+    const bool has0 = c0 < C, has1 = c1 < C;
+
+    if (lane < CTC_MAX_BEAM) {
+        s.pb[lane] = lane == 0 ? (ctc_real)0 : ctc_neg_inf();
+        s.pnb[lane] = ctc_neg_inf();
+        s.len[lane] = lane == 0 ? 0 : -1;
+        s.last[lane] = 0;
+    }
+    wave_lds_fence();
+    int n = 1, cur = 0;                                                    // live entries (wave-uniform), the prefix buffer that holds them
+    float next0 = has0 ? x[c0] : 0.f, next1 = has1 ? x[c1] : 0.f;
+    for (int t = 0; t < T; ++t) {
+        const float v0 = next0, v1 = next1;
+        if (t + 1 < T) {                                                   // the next frame is requested before this frame's arithmetic
+            const float* const p = x + (long)(t + 1) * step_stride;
+            next0 = has0 ? p[c0] : 0.f;
+            next1 = has1 ? p[c1] : 0.f;
+        }
+        // ---- log-probabilities of the lane's two classes
+        ctc_real num0, num1, e0, e1;
+        bool live0, live1;
+        if (normalized) {
+            live0 = has0 && v0 > 0.f;
+            live1 = has1 && v1 > 0.f;
+            e0 = live0 ? (ctc_real)v0 : 0;
+            e1 = live1 ? (ctc_real)v1 : 0;
+            num0 = live0 ? ::log(e0) : 0;
+            num1 = live1 ? ::log(e1) : 0;
+        } else {
+            const float ninf = -__builtin_inff();
+            float mx = has0 ? v0 : ninf;
+            mx = has1 && v1 > mx ? v1 : mx;
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) {
+                const float o = shfl_xor(mx, m);
+                mx = o > mx ? o : mx;
+            }
+            live0 = has0 && v0 > ninf;
+            live1 = has1 && v1 > ninf;
+            num0 = live0 ? (ctc_real)v0 - (ctc_real)mx : 0;
+            num1 = live1 ? (ctc_real)v1 - (ctc_real)mx : 0;
+            e0 = live0 ? ::exp(num0) : 0;
+            e1 = live1 ? ::exp(num1) : 0;
+        }
+        if (has0) s.lp[c0] = e0;
+        if (has1) s.lp[c1] = e1;
+        wave_lds_fence();
+        ctc_real sum = 0;
+        for (int c = 0; c < C; ++c) sum += s.lp[c];                        // ascending class order, the same on every lane
+        const ctc_real lsum = ::log(sum);
+        const ctc_real lp0 = live0 ? num0 - lsum : ctc_neg_inf(), lp1 = live1 ? num1 - lsum : ctc_neg_inf();
+        wave_lds_fence();
+        if (has0) s.lp[c0] = lp0;
+        if (has1) s.lp[c1] = lp1;
+        if (lane < n) {
+            s.tot[lane] = ctc_lae(s.pb[lane], s.pnb[lane]);
+            s.absorb[lane] = -1;
+        }
+        if (lane < 2 * CTC_MAX_BEAM) s.merged[lane >> 1][lane & 1] = 0ull;
+        wave_lds_fence();
+
+        // ---- merges: extend candidate (i, last_j) spells live entry j where prefix_j = prefix_i + last_j
+        for (int q = 0; q * 4 < n; ++q) {                                  // pair (i, j) = (p >> 4, p & 15), p = 64 q + lane: rows i < n
+            const int p = q * 64 + lane, i = p >> 4, j = p & 15;
+            bool maybe = i < n && j < n;
+            if (maybe) {
+                const int li = s.len[i];
+                maybe = s.len[j] == li + 1 && (li == 0 || s.prefix[cur][j][li - 1] == s.last[i]);
+            }
+            unsigned long long pairs = ballot(maybe);
+            while (pairs) {
+                const int bit = __builtin_ctzll(pairs);
+                pairs &= pairs - 1;
+                const int pi = q * 4 + (bit >> 4), pj = bit & 15, li = s.len[pi];
+                const bool differs = lane < li && s.prefix[cur][pi][lane] != s.prefix[cur][pj][lane];
+                if (ballot(differs) == 0ull && lane == 0) {
+                    const int lj = s.last[pj];
+                    s.absorb[pj] = pi;
+                    s.merged[pi][lj >> 6] |= 1ull << (lj & 63);
+                }
+            }
+        }
+        wave_lds_fence();
+
+        // ---- the stay candidate of entry `lane`
+        if (lane < n) {
+            const int lj = s.last[lane], from = s.absorb[lane];
+            const ctc_real lpl = s.lp[lj];
+            ctc_real pnb = s.len[lane] > 0 ? s.pnb[lane] + lpl : ctc_neg_inf();
+            if (from >= 0) pnb = ctc_lae(pnb, (s.last[from] == lj ? s.pb[from] : s.tot[from]) + lpl);
+            const ctc_real pb = s.tot[lane] + s.lp[0];
+            s.stay_pb[lane] = pb;
+            s.stay_pnb[lane] = pnb;
+            s.stay_score[lane] = ctc_lae(pb, pnb);
+        }
+        wave_lds_fence();
+
+        // ---- the W best candidates, one per round; lane r keeps the entry of rank r
+        unsigned given = 0u;                                               // bit 2 i + h: this lane's candidate (i, lane + 64 h) is taken
+        ctc_real new_pb = ctc_neg_inf(), new_pnb = ctc_neg_inf();
+        int new_len = -1, new_last = 0, n_new = 0;
+        for (int r = 0; r < W; ++r) {
+            ctc_real best = ctc_neg_inf();
+            int best_k = 0x7fffffff;
+            for (int i = 0; i < n; ++i) {                                  // k ascends along the scan: `>` keeps the lowest k of equals
+                const ctc_real pbi = s.pb[i], toti = s.tot[i];
+                const int lasti = s.last[i];
+                if (has0 && !((given >> (2 * i)) & 1u)) {
+                    const bool gone = (s.merged[i][0] >> lane) & 1ull;
+                    const ctc_real sc = c0 == 0 ? s.stay_score[i] : (gone ? ctc_neg_inf() : (c0 == lasti ? pbi : toti) + lp0);
+                    if (sc > best) {
+                        best = sc;
+                        best_k = i * C + c0;
+                    }
+                }
+                if (has1 && !((given >> (2 * i + 1)) & 1u)) {
+                    const bool gone = (s.merged[i][1] >> lane) & 1ull;
+                    const ctc_real sc = gone ? ctc_neg_inf() : (c1 == lasti ? pbi : toti) + lp1;
+                    if (sc > best) {
+                        best = sc;
+                        best_k = i * C + c1;
+                    }
+                }
+            }
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) {
+                const ctc_real os = shfl_xor(best, m);
+                const int ok = shfl_xor(best_k, m);
+                if (os > best || (os == best && ok < best_k)) {
+                    best = os;
+                    best_k = ok;
+                }
+            }
+            if (best > ctc_neg_inf()) {                                    // wave-uniform: every lane holds the same winner
+                const int i = best_k / C, c = best_k - i * C, li = s.len[i];
+                if (lane == (c & 63)) given |= 1u << (2 * i + (c >> 6));
+                if (lane < li) s.prefix[cur ^ 1][r][lane] = s.prefix[cur][i][lane];
+                if (c > 0 && lane == li) s.prefix[cur ^ 1][r][li] = (unsigned char)c;      // (li <= t <= 63)
+                if (lane == r) {
+                    new_pb = c > 0 ? ctc_neg_inf() : s.stay_pb[i];
+                    new_pnb = c > 0 ? best : s.stay_pnb[i];
+                    new_len = li + (c > 0 ? 1 : 0);
+                    new_last = c > 0 ? c : s.last[i];
+                }
+                ++n_new;
+            }
+        }
+        wave_lds_fence();                                                  // every read of the old entries is done
+        if (lane < CTC_MAX_BEAM) {
+            s.pb[lane] = new_pb;
+            s.pnb[lane] = new_pnb;
+            s.len[lane] = new_len;
+            s.last[lane] = new_last;
+        }
+        n = uniform_i32(n_new);
+        cur ^= 1;
+        wave_lds_fence();
+    }
+
+    // ---- the entries are in rank order: the selection of the last frame sorted them by logaddexp(pb, pnb)
+    if (lane < W) {
+        const int len = s.len[lane];
+        lengths[(long)b * W + lane] = len;
+        hyp_scores[(long)b * W + lane] = len >= 0 ? (float)ctc_lae(s.pb[lane], s.pnb[lane]) : -__builtin_inff();
+    }
+    for (int r = 0; r < W; ++r) {
+        const int len = s.len[r];
+        if (lane < T) paths[((long)b * W + r) * T + lane] = lane < len ? (int)s.prefix[cur][r][lane] : -1;
+    }
+}
+
+}  // namespace ccd

@@ -64,10 +64,18 @@ __device__ __forceinline__ int ts_row_len(const int* __restrict__ row, int width
 }
 
 // grid = ceil(B / TS_WAVES).  The launcher has checked T * norm_width <= TS_COLS (hence T <= 128: two steps per lane).
-// CTC = true (ccd_text_score_ctc): the steps are frames of a CTC head - a step counts where its class is not the blank (class 0) and
-// differs from the step before; there is no end class and nothing is skipped as padding (end_idx, pad_idx unused).
-template <bool CTC>
-__global__ __launch_bounds__(TS_THREADS) void text_score_kernel(const float* __restrict__ scores, long sample_stride, long step_stride,
+// How a sample's classes are found (everything behind the decode step is shared):
+//   TS_ATTN   (ccd_text_score)        the arg-max of every decoding step, up to the first end class, padding classes skipped;
+//   TS_CTC    (ccd_text_score_ctc)    the steps are frames of a CTC head - a step counts where its arg-max class is not the blank
+//                                     (class 0) and differs from the step before; no end class, nothing skipped as padding;
+//   TS_PATHS  (ccd_text_score_paths)  the classes are given: `scores` is an int32 row per sample (ccd_ctc_beam_search's paths),
+//                                     read up to the first negative entry; a class outside [1, C) is never an index and counts nothing.
+// end_idx and pad_idx are used by TS_ATTN alone.
+constexpr int TS_ATTN = 0, TS_CTC = 1, TS_PATHS = 2;
+template <int MODE> struct TsInput { typedef float type; };
+template <> struct TsInput<TS_PATHS> { typedef int type; };
+template <int MODE>
+__global__ __launch_bounds__(TS_THREADS) void text_score_kernel(const typename TsInput<MODE>::type* __restrict__ scores, long sample_stride, long step_stride,
                                                                 int B, int T, int C, const int* __restrict__ tbl_raw, int raw_width,
                                                                 const int* __restrict__ tbl_norm, int norm_width, int end_idx, int pad_idx,
                                                                 const int* __restrict__ gt, long gt_stride, int gt_cols,
@@ -83,22 +91,31 @@ __global__ __launch_bounds__(TS_THREADS) void text_score_kernel(const float* __r
     for (int h = 0; h < halves; ++h) {
         const int t = lane + 64 * h;
         if (t < T) {
-            const float* const p = scores + (long)b * sample_stride + (long)t * step_stride;
-            float best = p[0];
-            int arg = 0;
-            for (int c = 1; c < C; ++c) {
-                const float v = p[c];
-                if (v > best) {
-                    best = v;
-                    arg = c;
+            const auto* const p = scores + (long)b * sample_stride + (long)t * step_stride;
+            if constexpr (MODE == TS_PATHS) {
+                cls[h] = p[0] < 0 ? -1 : p[0];
+            } else {
+                float best = p[0];
+                int arg = 0;
+                for (int c = 1; c < C; ++c) {
+                    const float v = p[c];
+                    if (v > best) {
+                        best = v;
+                        arg = c;
+                    }
                 }
+                cls[h] = arg;
             }
-            cls[h] = arg;
         }
     }
     int end = T;
     bool counts[2] = {cls[0] != pad_idx, cls[1] != pad_idx};
-    if constexpr (CTC) {
+    if constexpr (MODE == TS_PATHS) {
+        const unsigned long long e0 = ballot(cls[0] < 0), e1 = ballot(cls[1] < 0);      // (the lanes behind T hold -1)
+        end = e0 ? __builtin_ctzll(e0) : (e1 ? 64 + __builtin_ctzll(e1) : T);
+        counts[0] = cls[0] > 0 && cls[0] < C;
+        counts[1] = cls[1] > 0 && cls[1] < C;
+    } else if constexpr (MODE == TS_CTC) {
         const int before0 = shfl(cls[0], lane ? lane - 1 : 0), last0 = shfl(cls[0], 63), before1 = shfl(cls[1], lane ? lane - 1 : 0);
         counts[0] = cls[0] > 0 && (lane == 0 || cls[0] != before0);
         counts[1] = cls[1] > 0 && cls[1] != (lane == 0 ? last0 : before1);

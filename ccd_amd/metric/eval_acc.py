@@ -17,7 +17,9 @@ those of `update` on the decoded strings: the counts exactly, `ned` up to the or
 `AttnConvertor.score_table()` (None when max_seq_len steps of the longest class do not fit the kernel: host path) and takes the
 first maximum of the scores themselves where `tensor2idx` takes the maximum of their softmax; the two differ only where two
 classes of a step are closer than the softmax resolves.  With a CTCConvertor the same path decodes by the greedy CTC rule
-(ops.text_score_ctc: repeats collapsed, blanks dropped); everything behind the decode step is shared.
+(ops.text_score_ctc: repeats collapsed, blanks dropped); everything behind the decode step is shared.  A CTCConvertor with
+`beam_width` > 0 decodes by CTC prefix beam search instead (ops.ctc_beam_search on the head's probabilities) and scores the best
+word (ops.text_score_paths): three launches per batch, still no host synchronisation.
 """
 from __future__ import annotations
 
@@ -120,7 +122,10 @@ class TextAccuracy:
             raise ValueError(f"update_scores: {scores.shape[0]} samples but {len(lens)} ground-truth strings")
         both = _to_device(np.concatenate([codes.ravel(), lens]), dev)         # one host-to-device copy for both
         gt, gt_len = both[:codes.size].view(codes.shape), both[codes.size:]
-        if is_ctc(conv):                                                      # CTCConvertor: frames, not decoding steps
+        if is_ctc(conv) and conv.beam_width > 0:                              # prefix beam search on the probabilities, rank 0 scored
+            paths, _, _ = ops.ctc_beam_search(scores, conv.beam_width, normalized=True)
+            records = ops.text_score_paths(paths[:, 0], raw, norm, gt, gt_len)
+        elif is_ctc(conv):                                                    # CTCConvertor: frames, not decoding steps
             records = ops.text_score_ctc(scores, raw, norm, gt, gt_len)
         else:
             records = ops.text_score(scores, raw, norm, conv.end_idx, conv.padding_idx, gt, gt_len)
@@ -158,7 +163,10 @@ class TextAccuracy:
             image_tensors = image_tensors.to(device)
             start = time.time()
             out_dec = model(image_tensors, text=None, return_loss=False, test_speed=False)
-            label_indexes, _scores = net.label_convertor.tensor2idx(out_dec)
+            if is_ctc(convertor) and convertor.beam_width > 0:                # the best word of the beam (the kernel, on any device)
+                label_indexes = [words[0] if words else [] for words in convertor.tensor2nbest(out_dec, nbest=1)[0]]
+            else:
+                label_indexes, _scores = net.label_convertor.tensor2idx(out_dec)
             pt_text = net.label_convertor.idx2str(label_indexes)
             self.inference_time += time.time() - start
             self.update(list(label_tensors[0]), pt_text)

@@ -143,7 +143,8 @@ class DINO_Finetune(ArenaModule):
     """Text recogniser of the finetune stage (Dino/model/dino_vision.py:134-290): ViT backbone -> Mlp "encoder" ->
     NRTR decoder -> TFLoss.  Same constructor (a config object), parameter names and init RNG order as the reference.
     `decoder.type: 'CTCDecoder'` builds the CTC head instead (no reference counterpart): backbone -> CTCDecoder (frame pooling + one
-    linear layer) -> CTCLoss, with a CTCConvertor; there is no `encoder` Mlp then.  Any other value builds the NRTR recogniser."""
+    linear layer) -> CTCLoss, with a CTCConvertor; there is no `encoder` Mlp then.  `decoder.beam_width` > 0 makes evaluation decode by
+    CTC prefix beam search of that width (absent or 0: the greedy rule).  Any other type builds the NRTR recogniser."""
 
     def __init__(self, config):
         super().__init__()
@@ -177,7 +178,8 @@ class DINO_Finetune(ArenaModule):
         from ..decoder.ctc_decoder import CTCDecoder
         from ..loss.ctc_loss import CTCLoss
         from ..modules import vision_transformer as vits
-        self.label_convertor = CTCConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len or 25, with_unknown=True)
+        self.label_convertor = CTCConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len or 25, with_unknown=True,
+                                            beam_width=int(getattr(config, "decoder_beam_width", 0) or 0))     # absent or 0: greedy
         config.arch = config.arch.replace("deit", "vit")
         if config.arch not in vits.__dict__:
             raise NotImplementedError(f"Unknow architecture: {config.arch} (HIP kernels cover vit_tiny / vit_small / vit_base)")

@@ -821,8 +821,29 @@ def text_score_ctc(logits, table_raw, table_norm, gt_codes, gt_len):
     return records
 
 
+def text_score_paths(paths, table_raw, table_norm, gt_codes, gt_len):
+    """text_score for classes that are already decoded: paths int32 [B, T] (any row stride, e.g. rank 0 of ctc_beam_search's
+    paths[:, 0]), a sample's classes in front of its first negative entry.  Tables as CTCConvertor.score_table gives them; records as
+    text_score."""
+    if paths.dim() != 2 or gt_codes.dim() != 2 or gt_codes.shape[0] != paths.shape[0] or tuple(gt_len.shape) != (paths.shape[0],):
+        raise ValueError(f"text_score_paths: expects paths [B, T], gt [B, L] and gt_len [B], got {list(paths.shape)}, "
+                         f"{list(gt_codes.shape)}, {list(gt_len.shape)}")
+    if paths.shape[1] > 1 and paths.stride(1) != 1:
+        raise ValueError("text_score_paths: the steps of a path must be contiguous")
+    B, T = paths.shape
+    for name, t in (("table_raw", table_raw), ("table_norm", table_norm)):
+        if t.dim() != 2 or t.shape[0] != table_raw.shape[0] or not t.is_contiguous():
+            raise ValueError(f"text_score_paths: {name} must be a contiguous [classes, width] table, got {list(t.shape)}")
+    assert gt_len.is_contiguous()
+    records = torch.empty((B, len(TEXT_RECORD)), dtype=I32, device=paths.device)
+    if B:
+        _call("ccd_text_score_paths", paths, paths.stride(0), B, T, table_raw.shape[0], table_raw, table_raw.shape[1], table_norm,
+              table_norm.shape[1], gt_codes if gt_codes.shape[1] else None, gt_codes.stride(0), gt_codes.shape[1], gt_len, records)
+    return records
+
+
 # ------------------------------------------------------------------------------------------ CTC recognition head (kernels/ctc.h)
-CTC_MAX_STEPS, CTC_MAX_CLASSES, CTC_MAX_LABELS = 64, 128, 31         # ccd_hip.h: CCD_CTC_MAX_*
+CTC_MAX_STEPS, CTC_MAX_CLASSES, CTC_MAX_LABELS, CTC_MAX_BEAM = 64, 128, 31, 16         # ccd_hip.h: CCD_CTC_MAX_*
 
 
 def ctc_pool_fwd(tokens, rows=8, cols=32):
@@ -898,6 +919,24 @@ def ctc_greedy(logits):
     conf = torch.empty((B, T), dtype=F32, device=logits.device)
     _call("ccd_ctc_greedy", logits, logits.stride(0), logits.stride(1), B, T, C, path, length, conf)
     return path, length, conf
+
+
+def ctc_beam_search(scores, beam_width, normalized=False):
+    """CTC prefix beam search (kernels/ctc_beam.h): scores fp32 [B, T, C] (any sample / step stride), logits or - normalized=True -
+    probabilities, as CTCDecoder.forward_test returns them -> (paths int32 [B, W, T] by rank, -1-padded; lengths int32 [B, W], -1 for
+    an unused slot; hyp_scores fp32 [B, W]: the log of the word's probability summed over the alignments the beam kept, -inf for an
+    unused slot).  W = beam_width in 1..CTC_MAX_BEAM."""
+    if scores.dim() != 3 or (scores.shape[2] > 1 and scores.stride(2) != 1):
+        raise ValueError(f"ctc_beam_search: expects scores [B, T, C] with contiguous classes, got {list(scores.shape)}, strides {scores.stride()}")
+    B, T, C = scores.shape
+    W = int(beam_width)
+    if not 1 <= W <= CTC_MAX_BEAM:
+        raise ValueError(f"ctc_beam_search: beam_width must lie in 1..{CTC_MAX_BEAM}, got {beam_width}")
+    paths = torch.empty((B, W, T), dtype=I32, device=scores.device)
+    lengths = torch.empty((B, W), dtype=I32, device=scores.device)
+    hyp_scores = torch.empty((B, W), dtype=F32, device=scores.device)
+    _call("ccd_ctc_beam_search", scores, scores.stride(0), scores.stride(1), B, T, C, 1 if normalized else 0, W, paths, lengths, hyp_scores)
+    return paths, lengths, hyp_scores
 
 
 class SsimFn(torch.autograd.Function):

@@ -423,6 +423,13 @@ int ccd_text_accumulate(const int* records, int batch, long* totals, double* tot
 int ccd_text_score_ctc(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, const int* table_raw,
                        int raw_width, const int* table_norm, int norm_width, const int* gt, long gt_stride, int gt_cols, const int* gt_len,
                        int* records, void* stream);
+/* The same records for classes that are already decoded (ABI 21): paths int32 [batch, >= steps] with row stride path_stride, a
+ * sample's classes in front of its first negative entry (at most `steps` of them) - a rank of ccd_ctc_beam_search's paths, row
+ * stride beam * steps.  A class outside [1, classes) is never an index and counts no characters.  Tables, ground truth, records,
+ * error codes and limits as for ccd_text_score. */
+int ccd_text_score_paths(const int* paths, long path_stride, int batch, int steps, int classes, const int* table_raw, int raw_width,
+                         const int* table_norm, int norm_width, const int* gt, long gt_stride, int gt_cols, const int* gt_len, int* records,
+                         void* stream);
 
 /* ---------------------------------------------------------------- CTC recognition head (ABI 20)
  * No reference counterpart (the reference has no CTC head); the semantics are those of
@@ -460,6 +467,26 @@ int ccd_ctc_loss_bwd(const float* logits, long ldl, int batch, int steps, int cl
                      const float* upstream, ccd_bf16* d_logits, long ldd, void* stream);
 int ccd_ctc_greedy(const float* logits, long sample_stride, long step_stride, int batch, int steps, int classes, int* path, int* length,
                    float* conf, void* stream);
+/* CTC prefix beam search (ABI 21; kernels/ctc_beam.h, restated in numpy in tests/ctc_beam_np.py), one wavefront per sample:
+ *   scores      fp32 [batch, steps, classes], classes contiguous, sample and step strides in elements; class 0 = blank.
+ *               normalized = 0: logits, lp = x - max - log sum exp(x - max); normalized = 1: probabilities (CTCDecoder.forward_test),
+ *               lp = log p - log sum p, a zero probability gives -inf.  Both in fp64 from the fp32 values, the sum over the classes in
+ *               ascending order.  -inf masks a class.
+ *   beam        1..CCD_CTC_MAX_BEAM entries.  An entry is a prefix of classes 1..classes-1 with pb / pnb, the log mass of its alignments
+ *               ending in the blank / a non-blank; the start is the empty prefix (pb 0, pnb -inf).  Per frame, tot = logaddexp(pb, pnb):
+ *               stay: pb' = tot + lp[0], pnb' = pnb + lp[last]; extend by c: pb' = -inf, pnb' = (c == last ? pb : tot) + lp[c]; an
+ *               extension that spells a live entry's prefix is log-added into that entry's stay pnb' and disappears.  The `beam` best
+ *               candidates of finite score logaddexp(pb', pnb') survive, by score descending, then parent rank * classes + class
+ *               ascending (stay = class 0).  fp64 throughout; log-sum-exp of nothing is -inf, never NaN.
+ *   paths       int32 [batch, beam, steps] by rank, padded with -1; lengths int32 [batch, beam], -1 for an unused slot (fewer than
+ *               `beam` finite candidates: steps = 1, an all -inf frame); hyp_scores fp32 [batch, beam] = logaddexp(pb, pnb) rounded
+ *               once, -inf for an unused slot: a lower bound of the word's log CTC probability, exact when nothing was pruned.
+ * No atomics: the same input gives the same bits.  batch == 0 is a no-op.  CCD_EINVAL: a missing pointer, a negative size or stride;
+ * CCD_ESHAPE: beam outside 1..CCD_CTC_MAX_BEAM, steps outside 1..CCD_CTC_MAX_STEPS, classes outside 2..CCD_CTC_MAX_CLASSES, normalized
+ * not 0 or 1.  Nothing is launched on an error. */
+#define CCD_CTC_MAX_BEAM 16
+int ccd_ctc_beam_search(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
+                        int beam, int* paths, int* lengths, float* hyp_scores, void* stream);
 
 /* ---------------------------------------------------------------- DINOHead pieces, vit.py:313,326 */
 int ccd_l2norm_fwd(const ccd_bf16* x, ccd_bf16* y, float* inv, int max_rows, const int* d_rows, int rows_mul, int D,

@@ -66,6 +66,7 @@ def main():
     ap.add_argument("--checkpoint", type=str, default=None)
     ap.add_argument("--test_root", type=str, default=None)
     ap.add_argument("--batch_size", type=int, default=None)
+    ap.add_argument("--beam_width", type=int, default=None, help="CTC head: prefix beam search of this width (0: greedy decoding)")
     a = ap.parse_args()
     config = Config(a.config)
     if a.checkpoint is not None:
@@ -74,6 +75,8 @@ def main():
         config.dataset_test_roots = [a.test_root]
     if a.batch_size is not None:
         config.dataset_test_batch_size = a.batch_size
+    if a.beam_width is not None:
+        config.decoder_beam_width = a.beam_width
     Logger.init(config.global_workdir, config.global_name, "test")
     utils.fix_random_seeds(int(config.global_seed or 0))
     logging.info("Construct dataset.")

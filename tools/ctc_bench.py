@@ -2,13 +2,18 @@
 """Time the CTC recognition head (kernels/ctc.h, ccd_amd/decoder/ctc_decoder.py) on the GPU.
 
     python tools/ctc_bench.py [--iters 30] [--rounds 5] [--out profiles/ctc_head.json]
+    python tools/ctc_bench.py --cases beam --out profiles/ctc_beam.json
 
-Three cases, each in a process of its own under its own time limit; the next one starts only if the one before ended well:
+The cases, each in a process of its own under its own time limit; the next one starts only if the one before ended well (by
+default the first three):
   loss    ccd_ctc_loss_fwd + _bwd on logits fp32 [512 * 32, 128] (92 classes), words of 3..15 characters, against
           F.log_softmax + F.ctc_loss(reduction='mean', zero_infinity=True) forward + backward of torch on the same GPU (the yardstick);
   step    one finetune step (forward, backward, AdamW) at B = 512, vit_small: CTC head and NRTR head in the same process, rounds
           alternating;
-  infer   inference images/s at B = 512, vit_small, eval mode: CTC head (one pass) against NRTR greedy decoding (25 steps).
+  infer   inference images/s at B = 512, vit_small, eval mode: CTC head (one pass) against NRTR greedy decoding (25 steps);
+  beam    ccd_ctc_beam_search (kernels/ctc_beam.h) on probabilities fp32 [512, 32, 92] read from a 128-wide buffer, beam widths
+          1, 4, 8, 16, next to ccd_ctc_greedy on the same buffer; then evaluation images/s at B = 512, vit_small (forward +
+          TextAccuracy.update_scores, what TextAccuracy.compute does per batch) with beam_width 8 against greedy decoding.
 Warm-up first, HIP events around every timed call, a figure is the median of the round medians with the lowest and highest
 round.  No threshold is set; the file records what was measured.  `--case NAME` runs one case and prints its JSON line."""
 import argparse
@@ -22,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 B, T, C = 512, 32, 92
-LIMITS = {"loss": 240, "step": 420, "infer": 300}           # seconds per case
+LIMITS = {"loss": 240, "step": 420, "infer": 300, "beam": 300}           # seconds per case
 
 
 def event_ms(fn, iters):
@@ -141,7 +146,60 @@ def case_infer(a):
             "nrtr_images_per_s": round(B / (n["median_ms"] * 1e-3))}
 
 
-CASES = {"loss": case_loss, "step": case_step, "infer": case_infer}
+def case_beam(a):
+    import torch
+    from ccd_amd import finetune as ft, ops
+    from ccd_amd.metric.eval_acc import TextAccuracy
+    dev = torch.device("cuda")
+    g = torch.Generator().manual_seed(5)
+    logits = torch.randn(B, T, C, generator=g)                               # moderately peaked frames: 60 % a character, else the blank
+    peak = torch.where(torch.rand(B, T, generator=g) < 0.6, torch.randint(0, C, (B, T), generator=g), torch.zeros(B, T, dtype=torch.long))
+    logits.scatter_add_(2, peak[..., None], 2.0 + 6.0 * torch.rand(B, T, 1, generator=g))
+    buf = torch.zeros(B * T, 128)
+    buf[:, :C] = logits.softmax(-1).reshape(B * T, C)
+    probs = buf.to(dev).view(B, T, 128)[:, :, :C]
+    out = {"shape": [B, T, C], "input": "fp32 probabilities, normalized = 1"}
+    widths = (1, 4, 8, 16)
+    rounds = {w: [] for w in widths}
+    greedy = []
+    for _ in range(a.rounds):
+        greedy.append(event_ms(lambda: ops.ctc_greedy(probs), a.iters))
+        for w in widths:
+            rounds[w].append(event_ms(lambda: ops.ctc_beam_search(probs, w, normalized=True), a.iters))
+    out["ctc_greedy"] = summary(greedy)
+    for w in widths:
+        out[f"ctc_beam_search_w{w}"] = summary(rounds[w])
+    best = ops.ctc_beam_search(probs, 16, normalized=True)
+    path, length, _ = ops.ctc_greedy(probs)
+    same = ((best[0][:, 0] == path).all(1) & (best[1][:, 0] == length)).sum()
+    out["samples_whose_best_word_at_w16_is_not_the_greedy_word"] = int(B - same)
+    # evaluation: forward + scoring, the body of TextAccuracy.compute
+    torch.manual_seed(0)
+    cfg = ft.FinetuneConfig()
+    cfg.decoder_type = "CTCDecoder"
+    model = ft.build_model(cfg, dev, dropout=0.0).eval()
+    conv = model.label_convertor
+    img = torch.randn(B, 3, 32, 128, generator=torch.Generator().manual_seed(4)).to(dev)
+    words = ["".join(conv.idx2char[1 + (i * 7 + j) % 90] for j in range(3 + i % 13)) for i in range(B)]
+    metric = TextAccuracy()
+
+    def evaluate():
+        metric.update_scores(model(img, text=None, return_loss=False, test_speed=False).float(), words, conv)
+
+    sides = {0: [], 8: []}
+    iters = max(3, a.iters // 3)
+    with torch.no_grad():
+        for _ in range(a.rounds):
+            for width in sides:
+                conv.beam_width = width
+                sides[width].append(event_ms(evaluate, iters))
+    g0, b8 = summary(sides[0]), summary(sides[8])
+    out.update({"batch": B, "arch": "vit_small", "evaluate_greedy": g0, "evaluate_beam_width_8": b8,
+                "greedy_images_per_s": round(B / (g0["median_ms"] * 1e-3)), "beam_width_8_images_per_s": round(B / (b8["median_ms"] * 1e-3))})
+    return out
+
+
+CASES = {"loss": case_loss, "step": case_step, "infer": case_infer, "beam": case_beam}
 
 
 def main():
@@ -149,6 +207,7 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--case", choices=sorted(CASES), default=None)
+    ap.add_argument("--cases", default="loss,step,infer", help="comma-separated cases of a whole run, in order")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.case is not None:
@@ -157,7 +216,9 @@ def main():
         print(json.dumps({a.case: CASES[a.case](a)}))
         return
     out = {"iters": a.iters, "rounds": a.rounds, "unit": "ms per call, HIP events (median of round medians; lowest and highest round)"}
-    for name in ("loss", "step", "infer"):
+    names = [n for n in a.cases.split(",") if n]
+    assert names and all(n in CASES for n in names), f"--cases takes names out of {sorted(CASES)}"
+    for name in names:
         # a fresh process per case under its own time limit; a case that fails or runs out of time ends the run
         run = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name, "--iters", str(a.iters), "--rounds", str(a.rounds)],
                              capture_output=True, text=True, timeout=LIMITS[name])
