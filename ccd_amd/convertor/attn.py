@@ -38,12 +38,14 @@ def _read_alphabet_file(path):
 
 
 class AttnConvertor:
-    """AttnConvertor(dict_type='DICT90', max_seq_len=40, with_unknown=True) - see the module docstring."""
+    """AttnConvertor(dict_type='DICT90', max_seq_len=40, with_unknown=True, beam_width=0) - see the module docstring.  `beam_width` > 0
+    asks for beam search over the decoder (DINO_Finetune.forward_beam) where words are scored (TextAccuracy.compute); 0, the default,
+    is greedy decoding everywhere, and `tensor2idx` is the greedy rule whatever the width."""
 
     dicts = {name: tuple(chars) for name, chars in ALPHABETS.items()}      # same table name as the reference exposes
 
     def __init__(self, dict_type="DICT90", dict_file=None, dict_list=None, with_unknown=True, max_seq_len=40, lower=False,
-                 start_end_same=True, **_ignored):
+                 start_end_same=True, beam_width=0, **_ignored):
         if dict_file is not None:
             alphabet = _read_alphabet_file(dict_file)
         elif dict_list is not None:
@@ -56,6 +58,10 @@ class AttnConvertor:
             raise AssertionError("dictionary holds a character twice")
         self.with_unknown, self.max_seq_len = bool(with_unknown), int(max_seq_len)
         self.lower, self.start_end_same = bool(lower), bool(start_end_same)
+        self.beam_width = int(beam_width or 0)
+        from ..ops import NRTR_MAX_BEAM
+        if not 0 <= self.beam_width <= NRTR_MAX_BEAM:
+            raise ValueError(f"beam_width must lie in 0..{NRTR_MAX_BEAM} (0: greedy decoding), got {beam_width}")
         # special classes behind the alphabet, in the reference's order
         self.idx2char = alphabet
         self.unknown_idx = self._append("<UKN>") if self.with_unknown else None
@@ -137,6 +143,16 @@ class AttnConvertor:
             self._score_table = tuple(tables) if self.max_seq_len * tables[1].shape[1] <= TEXT_COLS else None
         return self._score_table
 
+    def path_score_table(self):
+        """score_table() for classes that are already decoded (ops.text_score_paths, which never takes class 0 for an index - it is
+        the CTC blank there): the same two tables behind one empty row, so that class c sits in row c + 1.  The caller hands the
+        kernel `paths + 1`: the -1 padding becomes row 0 and counts nothing.  None where score_table() is None."""
+        if not hasattr(self, "_path_score_table"):
+            tables = self.score_table()
+            self._path_score_table = None if tables is None else tuple(
+                np.concatenate([np.full((1, t.shape[1]), -1, dtype=np.int32), t]) for t in tables)
+        return self._path_score_table
+
     @torch.no_grad()
     def tensor2idx(self, outputs, img_metas=None):
         """[N, T, C] class scores -> (class indices, softmax confidences) per sample: positions up to the first <EOS>,
@@ -150,3 +166,18 @@ class AttnConvertor:
         indexes = [cls_np[i][keep[i]].tolist() for i in range(cls_np.shape[0])]
         scores = [conf_np[i][keep[i]].tolist() for i in range(cls_np.shape[0])]
         return indexes, scores
+
+    @torch.no_grad()
+    def paths2nbest(self, paths, lengths, scores, nbest=1):
+        """What DINO_Finetune.forward_beam returns - paths [N, W, T], lengths [N, W], scores [N, W] - -> (indexes, log_probs) as
+        CTCConvertor.tensor2nbest returns them: indexes[i] holds up to `nbest` index lists, best first (an unused slot gives none);
+        log_probs is a float tensor [N, nbest] on the host, the log-probability of each word with its <EOS>, -inf for an unused slot."""
+        nbest = int(nbest)
+        if paths.dim() != 3 or tuple(lengths.shape) != tuple(paths.shape[:2]) or tuple(scores.shape) != tuple(paths.shape[:2]):
+            raise ValueError(f"paths2nbest: expects paths [N, W, T], lengths [N, W] and scores [N, W], got {list(paths.shape)}, "
+                             f"{list(lengths.shape)}, {list(scores.shape)}")
+        if not 1 <= nbest <= paths.shape[1]:
+            raise ValueError(f"paths2nbest: nbest must lie in 1..beam_width = {paths.shape[1]}, got {nbest}")
+        paths, lengths = paths[:, :nbest].cpu().numpy(), lengths[:, :nbest].cpu().numpy()
+        indexes = [[paths[i, r, :lengths[i, r]].tolist() for r in range(nbest) if lengths[i, r] >= 0] for i in range(paths.shape[0])]
+        return indexes, scores[:, :nbest].float().cpu()

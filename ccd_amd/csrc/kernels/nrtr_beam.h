@@ -1,0 +1,225 @@
+// nrtr_beam.h - beam search over the NRTR attention decoder (ccd_nrtr_beam_step, ccd_nrtr_beam_reorder):
+//   nrtr_beam_step_kernel     one decoding position: the logits of the W hypotheses of a sample -> the W best successors, their
+//                             parents, the permuted token sequences; at the caller's wish the n-best lists as ctc_beam_kernel writes them
+//   nrtr_beam_reorder_kernel  the per-layer q|k|v cache of the incremental decoder, permuted by those parents
+// The semantics are restated in numpy in tests/nrtr_beam_np.py, which is the specification:
+//   a sample holds W slots by rank; a slot is live, finished or unused and carries a token sequence and an fp64 score, the sum of
+//   log_softmax(logits)[token] over its steps.  Start: slot 0 live with score 0, the others unused with score -inf.
+//   candidates at a step   live slot r: (r, c) for every class c, score[r] + log_softmax(logits[r])[c] (fp64 over the fp32 row);
+//                          finished slot r: (r, end_idx) alone, score unchanged, stays finished, writes padding_idx;
+//                          unused slot: none.  A candidate of score -inf (a -inf logit) is no candidate.
+//   selection              the W best by (score descending, k = r * C + c ascending); fewer candidates leave unused slots behind;
+//                          class end_idx finishes the hypothesis (the token is written).
+//
+// Step kernel: ONE WAVEFRONT PER SAMPLE, one wavefront per workgroup (the candidate table is 16 KB of LDS).  Lane l owns the classes l
+// and l + 64 of every slot and the positions l and l + 64 of every sequence, in every role: it loads them, it scans them, it stores
+// them - so whatever a lane writes to global memory it has read itself before, and the update is in place without a second buffer.
+//   1. every old sequence (positions 0..step, as 16-bit tokens) and the old scores / states go to LDS;
+//   2. per live slot: row maximum by shuffles, exp(x - max) in fp64 to LDS, the sum in ascending class order (every lane adds the same
+//      C words), then cand[r][c] = score[r] + (x - max - log sum).  Finished: cand[r][end_idx] = score[r].  Everything else -inf;
+//   3. W rounds of a wave arg-max on the key (score, k): a lane folds its <= 2 W candidates (k ascends along the scan, `>` keeps the
+//      lowest of equals), six xor-shuffle steps fold the lanes; the owner of the winner overwrites it with -inf.  Lane r keeps rank r;
+//   4. the new rows: positions 0..step from the parent's row in LDS, position step + 1 the new token; score, state, parent by lane r.
+// Every loop that shuffles has a wave-uniform trip count (W, the slots); no atomics: the same input gives the same bits.
+// fp64 throughout (ctc_real): neighbouring candidates lie closer than an fp32 ulp at |score| ~ 100.
+//
+// Reorder kernel: pure data movement.  One thread owns the same 16-byte piece of the K | V columns of one (layer, sample, position)
+// in all W rows: it loads the piece of row parent[r] for every r whose parent differs (compile-time register index r, the gather is
+// in the address: nothing goes to scratch), waits for all loads, then stores row r.  Cycles (0 <-> 1) and shared parents are safe
+// because no other thread touches these bytes; rows with parent[r] == r (or an unused slot, parent -1) move nothing.
+#pragma once
+
+#include "ctc.h"
+
+namespace ccd {
+
+constexpr int NRTR_MAX_BEAM = 16;
+constexpr int NRTR_MAX_C = 128;
+constexpr int NRTR_MAX_LEN = 128;                                  // positions of a sequence (max_seq_len + 1)
+constexpr int NRTR_UNUSED = 0, NRTR_LIVE = 1, NRTR_FINISHED = 2;
+
+struct NrtrBeamWave {
+    ctc_real cand[NRTR_MAX_BEAM][NRTR_MAX_C];
+    ctc_real score[NRTR_MAX_BEAM];
+    int state[NRTR_MAX_BEAM];
+    unsigned short tok[NRTR_MAX_BEAM][NRTR_MAX_LEN];
+};
+
+// grid = B, block = 64.  The launcher has checked 1 <= W <= 16, 1 <= C <= 128, 0 <= step, step + 2 <= seq_len <= 128, end_idx in
+// [0, C), pad_idx in [0, 65536).  paths / lengths / hyp_scores: all three or none.
+__global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restrict__ logits, long ldl, int W, int C, int step, int end_idx,
+                                                            int pad_idx, long long* seq, int seq_len, ctc_real* score, int* state,
+                                                            int* __restrict__ parent, int* __restrict__ paths, int* __restrict__ lengths,
+                                                            float* __restrict__ hyp_scores) {
+    __shared__ NrtrBeamWave s;
+    const int lane = lane_id(), b = blockIdx.x;
+    const int c0 = lane, c1 = lane + 64;
+    const bool has0 = c0 < C, has1 = c1 < C;
+    const long row0 = (long)b * W;
+    const float ninf = -__builtin_inff();
+
+    // ---- 1. the old state
+    ctc_real my_score = ctc_neg_inf();
+    int my_state = NRTR_UNUSED;
+    if (lane < W) {
+        my_score = score[row0 + lane];
+        my_state = state[row0 + lane];
+    }
+    if (lane < NRTR_MAX_BEAM) {
+        s.score[lane] = my_score;
+        s.state[lane] = my_state;
+    }
+    for (int r = 0; r < W; ++r) {
+        const long long* const q = seq + (row0 + r) * seq_len;
+        if (c0 <= step) s.tok[r][c0] = (unsigned short)q[c0];
+        if (c1 <= step) s.tok[r][c1] = (unsigned short)q[c1];
+    }
+    wave_lds_fence();
+
+    // ---- 2. the candidates
+    for (int r = 0; r < W; ++r) {
+        const int st = s.state[r];                                         // wave-uniform
+        const ctc_real sc = s.score[r];
+        if (st == NRTR_LIVE) {
+            const float* const x = logits + (row0 + r) * ldl;
+            const float v0 = has0 ? x[c0] : ninf, v1 = has1 ? x[c1] : ninf;
+            float mx = v0 > v1 ? v0 : v1;
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) {
+                const float o = shfl_xor(mx, m);
+                mx = o > mx ? o : mx;
+            }
+            const bool live0 = has0 && v0 > ninf, live1 = has1 && v1 > ninf;
+            const ctc_real num0 = live0 ? (ctc_real)v0 - (ctc_real)mx : 0, num1 = live1 ? (ctc_real)v1 - (ctc_real)mx : 0;
+            if (has0) s.cand[r][c0] = live0 ? ::exp(num0) : 0;
+            if (has1) s.cand[r][c1] = live1 ? ::exp(num1) : 0;
+            wave_lds_fence();
+            ctc_real sum = 0;
+            for (int c = 0; c < C; ++c) sum += s.cand[r][c];               // ascending class order, the same on every lane
+            const ctc_real lsum = ::log(sum);
+            wave_lds_fence();
+            if (has0) s.cand[r][c0] = live0 ? sc + (num0 - lsum) : ctc_neg_inf();
+            if (has1) s.cand[r][c1] = live1 ? sc + (num1 - lsum) : ctc_neg_inf();
+        } else {
+            const bool carry = st == NRTR_FINISHED;
+            if (has0) s.cand[r][c0] = carry && c0 == end_idx ? sc : ctc_neg_inf();
+            if (has1) s.cand[r][c1] = carry && c1 == end_idx ? sc : ctc_neg_inf();
+        }
+    }
+    wave_lds_fence();
+
+    // ---- 3. the W best, one per round; lane r keeps the slot of rank r
+    ctc_real new_score = ctc_neg_inf();
+    int new_state = NRTR_UNUSED, new_parent = -1, new_tok = pad_idx;
+    for (int r = 0; r < W; ++r) {
+        ctc_real best = ctc_neg_inf();
+        int best_k = 0x7fffffff;
+        for (int i = 0; i < W; ++i) {                                      // k ascends along the scan: `>` keeps the lowest k of equals
+            if (has0) {
+                const ctc_real v = s.cand[i][c0];
+                if (v > best) {
+                    best = v;
+                    best_k = i * C + c0;
+                }
+            }
+            if (has1) {
+                const ctc_real v = s.cand[i][c1];
+                if (v > best) {
+                    best = v;
+                    best_k = i * C + c1;
+                }
+            }
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const ctc_real os = shfl_xor(best, m);
+            const int ok = shfl_xor(best_k, m);
+            if (os > best || (os == best && ok < best_k)) {
+                best = os;
+                best_k = ok;
+            }
+        }
+        if (best > ctc_neg_inf()) {                                        // wave-uniform: every lane holds the same winner
+            const int i = best_k / C, c = best_k - i * C;
+            if (lane == (c & 63)) s.cand[i][c] = ctc_neg_inf();            // (only this lane ever reads the entry again)
+            if (lane == r) {
+                const bool was_finished = s.state[i] == NRTR_FINISHED;
+                new_score = best;
+                new_parent = i;
+                new_state = was_finished || c == end_idx ? NRTR_FINISHED : NRTR_LIVE;
+                new_tok = was_finished ? pad_idx : c;
+            }
+        }
+        wave_lds_fence();
+    }
+
+    // ---- 4. the new state, in place: a lane stores what it loaded in phase 1 (positions) or owns (slot `lane`)
+    if (lane < W) {
+        score[row0 + lane] = new_score;
+        state[row0 + lane] = new_state;
+        parent[row0 + lane] = new_parent;
+        if (hyp_scores) hyp_scores[row0 + lane] = new_state == NRTR_UNUSED ? ninf : (float)new_score;
+    }
+    const int T = seq_len - 1;
+    for (int r = 0; r < W; ++r) {
+        const int p = shfl(new_parent, r), tk = shfl(new_tok, r);          // wave-uniform
+        long long* const q = seq + (row0 + r) * seq_len;
+        int t0 = -1, t1 = -1;                                              // the new row's tokens at this lane's positions
+        if (p >= 0) {
+            if (c0 <= step) t0 = s.tok[p][c0];
+            if (c1 <= step) t1 = s.tok[p][c1];
+            if (c0 == step + 1) t0 = tk;
+            if (c1 == step + 1) t1 = tk;
+            if (p != r) {
+                if (c0 <= step) q[c0] = t0;
+                if (c1 <= step) q[c1] = t1;
+            }
+        }
+        if (c0 == step + 1) q[c0] = tk;                                    // (an unused slot: padding_idx)
+        if (c1 == step + 1) q[c1] = tk;
+        if (paths) {                                                       // the classes in front of the first end_idx behind position 0
+            const bool e0 = p >= 0 && c0 >= 1 && c0 <= step + 1 && t0 == end_idx, e1 = p >= 0 && c1 <= step + 1 && t1 == end_idx;
+            const unsigned long long m0 = ballot(e0), m1 = ballot(e1);
+            const int first = m0 ? __builtin_ctzll(m0) : (m1 ? 64 + __builtin_ctzll(m1) : step + 2);
+            const int len = p >= 0 ? first - 1 : -1;
+            int* const o = paths + (row0 + r) * T;
+            if (c0 >= 1 && c0 <= T) o[c0 - 1] = c0 - 1 < len ? t0 : -1;
+            if (c1 <= T) o[c1 - 1] = c1 - 1 < len ? t1 : -1;
+            if (lane == 0) lengths[row0 + r] = len;
+        }
+    }
+}
+
+// One thread per 16-byte piece of the K | V columns of (layer, sample, position <= step): total = L * B * (step + 1) * chunks threads,
+// chunks = 2 D / 8.  cache bf16 [L, B * W * Tp, 3 D] (q | k | v per row, row = (b * W + r) * Tp + position), 16-byte aligned, D % 8 == 0.
+__global__ __launch_bounds__(256) void nrtr_beam_reorder_kernel(bf16_t* cache, const int* __restrict__ parent, int L, int B, int W, int Tp,
+                                                                int D, int step, long total) {
+    const long id = (long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= total) return;
+    const int chunks = D / 4;
+    const int chunk = (int)(id % chunks);
+    long rest = id / chunks;
+    const int t = (int)(rest % (step + 1));
+    rest /= step + 1;
+    const int b = (int)(rest % B), l = (int)(rest / B);
+    const long ld = 3L * D;
+    bf16_t* const base = cache + (((long)l * B + b) * W * Tp + t) * ld + D + 8L * chunk;      // slot 0; slot r lies r * Tp rows further
+    const int* const par = parent + (long)b * W;
+    u32x4 v[NRTR_MAX_BEAM];
+    bool move[NRTR_MAX_BEAM];
+#pragma unroll
+    for (int r = 0; r < NRTR_MAX_BEAM; ++r) {
+        move[r] = false;
+        if (r < W) {
+            const int p = par[r];
+            move[r] = p != r && (unsigned)p < (unsigned)W;
+            if (move[r]) v[r] = *reinterpret_cast<const u32x4*>(base + (long)p * Tp * ld);
+        }
+    }
+    glds_wait_all();                                                       // every load has landed before the first store leaves
+#pragma unroll
+    for (int r = 0; r < NRTR_MAX_BEAM; ++r)
+        if (move[r]) *reinterpret_cast<u32x4*>(base + (long)r * Tp * ld) = v[r];
+}
+
+}  // namespace ccd

@@ -97,6 +97,8 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
                                        start_idx=start_idx, padding_idx=padding_idx, dropout=dropout)
         self.packed = None
         self._graphs = {}
+        self.beam_width = 0            # forward_beam's default width (DINO_Finetune sets it from decoder.beam_width); 0: none
+        self._beam_graphs = {}
 
     def _transposed_names(self):
         names = []
@@ -157,6 +159,45 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
         static_in.copy_(out_enc)
         graph.replay()
         return static_out.clone()
+
+    def forward_beam(self, feat, out_enc, beam_width=None):
+        """Beam search of width `beam_width` (default: self.beam_width, which must then be > 0) -> (paths int32 [N, W, max_seq_len] by
+        rank, -1-padded; lengths int32 [N, W], -1 for an unused slot; scores fp32 [N, W], the log-probability of the word with its
+        <EOS>, -inf for an unused slot): fe.beam_decode.  On the GPU the loop is captured into a HIP graph per (batch shape, width) and
+        replayed, as forward_test's (CCD_DECODE_GRAPH=0: eager)."""
+        from ..ops import NRTR_MAX_BEAM
+        width = int(self.beam_width if beam_width is None else beam_width)
+        if not 1 <= width <= NRTR_MAX_BEAM:
+            raise ValueError(f"forward_beam: beam_width must lie in 1..{NRTR_MAX_BEAM}, got {width}")
+        self._ready()
+        out_enc = out_enc.to(torch.bfloat16)
+        if out_enc.is_cuda and os.environ.get("CCD_DECODE_GRAPH", "1") != "0":
+            return self._graphed_beam(out_enc, width)
+        return fe.beam_decode(self, out_enc, width)
+
+    def _graphed_beam(self, out_enc, width):
+        """_graphed_decode for the beam: one graph per (batch shape, arena, width), captured on a single stream."""
+        key = (tuple(out_enc.shape), out_enc.device, self.arena.flat.data_ptr(), width)
+        entry = self._beam_graphs.get(key)
+        if entry is None:
+            static_in = torch.empty_like(out_enc)
+            static_in.copy_(out_enc)
+            cur = torch.cuda.current_stream()
+            side = torch.cuda.Stream(device=out_enc.device)
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):                  # warm-up outside the capture (lazy one-time kernel attributes)
+                fe.beam_decode(self, static_in, width)
+            cur.wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                static_out = fe.beam_decode(self, static_in, width)
+            if len(self._beam_graphs) >= 4:
+                self._beam_graphs.pop(next(iter(self._beam_graphs)))
+            entry = self._beam_graphs[key] = (graph, static_in, static_out)
+        graph, static_in, static_out = entry
+        static_in.copy_(out_enc)
+        graph.replay()
+        return tuple(t.clone() for t in static_out)
 
     def forward_test_speed(self, feat, out_enc, img_metas=None):
         self._ready()

@@ -400,3 +400,54 @@ def greedy_decode(module, out_enc, stop_on_eos_of_first=False):
             done = s + 1
             break
     return probs[:, :done]
+
+
+@torch.no_grad()
+def beam_decode(module, out_enc, beam_width):
+    """Beam search of width W over the incremental decoder of `greedy_decode` (the rules: INTEGRATION.md, "Beam search over the NRTR
+    decoder"; kernels/nrtr_beam.h) -> (paths int32 [B, W, max_seq_len] by rank, -1-padded; lengths int32 [B, W]; scores fp32 [B, W]),
+    as ops.ctc_beam_search returns them.  The W hypotheses of a sample are rows b * W .. b * W + W - 1 of every activation: the
+    self-attention runs per hypothesis (B * W samples, causal, padding mask from the hypothesis' own tokens), the encoder-decoder
+    attention takes them as the W queries of sample b, so the encoder keys and values are never replicated.  Every step ends with the
+    selection (ops.nrtr_beam_step) and the permutation of the cached keys and values by the parents (ops.nrtr_beam_reorder).  No length
+    normalisation, no early exit: all max_seq_len steps run, nothing is read back."""
+    arena, pre, spec, packed = module.arena, module.arena_prefix, module.dec_spec, module.packed
+    B, W = out_enc.shape[0], int(beam_width)
+    D, H, L, C = spec.D, spec.H, spec.L, spec.C
+    steps, T = spec.max_seq_len, spec.max_seq_len + 1
+    dev = out_enc.device
+    scale = 64 ** -0.5
+    R = B * W
+    packed.refresh(arena, pre, spec)
+    kv = encoder_kv(arena, pre, spec, out_enc.reshape(-1, D))
+    seq, score, state, parent = ops.nrtr_beam_state(B, W, T, spec.start_idx, spec.padding_idx, dev)
+    cache = torch.zeros((L, R * T, 3 * D), dtype=BF16, device=dev)     # q | k | v of position t of every hypothesis
+    emb, pos = arena.w(pre + "trg_word_emb.weight"), module.pos_table
+    out = None
+    for s in range(steps):
+        x = ops.dec_embed_fwd(seq[:, s].contiguous().view(R, 1), emb, pos[s:s + 1])              # [R, D] fp32
+        for l in range(L):
+            b = f"{pre}layer_stack.{l}."
+            qkv = cache[l]
+            y, _, _ = ops.ln_fwd(x, arena.w(b + "norm1.weight"), arena.w(b + "norm1.bias"), 1e-5)
+            ops.gemm_nt(y, arena.span(b + "self_attn.linear_q.weight", 3 * D, "wb"), out=qkv.view(R, T, 3 * D)[:, s])
+            att, _, _ = ops.dec_attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], R, H, T, T, scale, tokens=seq,
+                                         pad_idx=spec.padding_idx, causal=True)
+            x = ops.gemm_nt(att.view(R, T, D)[:, s], arena.wb(b + "self_attn.fc.weight"), epilogue=ops.EPI_RESID, resid=x,
+                            rows_per_sample=1)
+            y, _, _ = ops.ln_fwd(x, arena.w(b + "norm2.weight"), arena.w(b + "norm2.bias"), 1e-5)
+            q2 = ops.gemm_nt(y, arena.wb(b + "enc_attn.linear_q.weight"))
+            att, _, _ = ops.dec_attn_fwd(q2, kv[:, l * 2 * D:l * 2 * D + D], kv[:, l * 2 * D + D:(l + 1) * 2 * D], B, H, W, 256,
+                                         scale)                                                  # W queries per sample
+            x = ops.gemm_nt(att, arena.wb(b + "enc_attn.fc.weight"), epilogue=ops.EPI_RESID, resid=x, rows_per_sample=1)
+            y, _, _ = ops.ln_fwd(x, arena.w(b + "norm3.weight"), arena.w(b + "norm3.bias"), 1e-5)
+            _, g3 = ops.gemm_nt(y, arena.wb(b + "mlp.w_1.weight"), epilogue=ops.EPI_GELU, bias=arena.w(b + "mlp.w_1.bias"),
+                                store_u=False)
+            x = ops.gemm_nt(g3, arena.wb(b + "mlp.w_2.weight"), epilogue=ops.EPI_RESID, bias=arena.w(b + "mlp.w_2.bias"),
+                            resid=x, rows_per_sample=1)
+        y, _, _ = ops.ln_fwd(x, arena.w(pre + "layer_norm.weight"), arena.w(pre + "layer_norm.bias"), 1e-6)
+        logits = ops.gemm_nt(y, packed.cls, epilogue=ops.EPI_F32, bias=packed.cls_bias)
+        out = ops.nrtr_beam_step(logits, C, s, spec.start_idx, spec.padding_idx, seq, score, state, parent, final=s == steps - 1)
+        if s + 1 < steps and W > 1:
+            ops.nrtr_beam_reorder(cache, parent, T, s)
+    return out

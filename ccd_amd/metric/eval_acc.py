@@ -19,7 +19,9 @@ first maximum of the scores themselves where `tensor2idx` takes the maximum of t
 classes of a step are closer than the softmax resolves.  With a CTCConvertor the same path decodes by the greedy CTC rule
 (ops.text_score_ctc: repeats collapsed, blanks dropped); everything behind the decode step is shared.  A CTCConvertor with
 `beam_width` > 0 decodes by CTC prefix beam search instead (ops.ctc_beam_search on the head's probabilities) and scores the best
-word (ops.text_score_paths): three launches per batch, still no host synchronisation.
+word (ops.text_score_paths): three launches per batch, still no host synchronisation.  An AttnConvertor with `beam_width` > 0
+makes `compute` decode by beam search over the NRTR decoder (`DINO_Finetune.forward_beam`) and score the best word the same way
+(`update_paths`; on the host path: `idx2str` of `paths2nbest`); `forward_test` itself stays greedy.
 """
 from __future__ import annotations
 
@@ -81,6 +83,7 @@ class TextAccuracy:
         self.total_ed = self.total_ned = self.inference_time = 0.0
         self._totals = None          # device path: int64 [6] on the device (ops.TEXT_TOTALS), read by result()
         self._tables = None          # (convertor, device, raw table, normalised table) of the last update_scores
+        self._path_tables = None     # the same for update_paths (AttnConvertor.path_score_table)
         self._spans = []             # device path of compute(): (start, end) events around each batch
 
     def update(self, gt_text, pt_text):
@@ -132,6 +135,30 @@ class TextAccuracy:
         ops.text_accumulate(records, self._totals)
         return records
 
+    def update_paths(self, paths, gt_text, convertor):
+        """Score one batch of decoded words on the device: paths int32 [B, T] (any row stride: rank 0 of forward_beam's paths), the
+        classes of an AttnConvertor, -1-padded.  Records and totals as update_scores; nothing is read back."""
+        if self.case_sensitive:
+            raise NotImplementedError("TextAccuracy is defined for case_sensitive=False (eval_acc.py:40-46)")
+        dev = paths.device
+        if self._path_tables is None or self._path_tables[0] is not convertor or self._path_tables[1] != dev:
+            tables = convertor.path_score_table()
+            if tables is None:
+                raise ValueError("update_paths: max_seq_len steps of the convertor's longest class exceed ops.TEXT_COLS characters; "
+                                 "score on the host with update()")
+            self._path_tables = (convertor, dev) + tuple(_to_device(t, dev) for t in tables)
+        _, _, raw, norm = self._path_tables
+        if self._totals is None:
+            self._totals = ops.text_totals(dev)
+        codes, lens = encode_truth(gt_text)
+        if len(lens) != paths.shape[0]:
+            raise ValueError(f"update_paths: {paths.shape[0]} samples but {len(lens)} ground-truth strings")
+        both = _to_device(np.concatenate([codes.ravel(), lens]), dev)
+        gt, gt_len = both[:codes.size].view(codes.shape), both[codes.size:]
+        records = ops.text_score_paths(paths + 1, raw, norm, gt, gt_len)      # class c in row c + 1; the -1 padding counts nothing
+        ops.text_accumulate(records, self._totals)
+        return records
+
     def result(self):
         cc, tc, cw, words, ed, ned = self.correct_num_char, self.total_num_char, self.correct_num_word, self.total_num_word, \
             self.total_ed, self.total_ned
@@ -149,19 +176,29 @@ class TextAccuracy:
         net = model.module if hasattr(model, "module") else model
         device = next(net.parameters()).device
         convertor = net.label_convertor
+        attn_beam = not is_ctc(convertor) and getattr(convertor, "beam_width", 0) > 0     # beam search over the NRTR decoder, rank 0 scored
         if device.type == "cuda" and not self.case_sensitive and convertor.score_table() is not None:
             for image_tensors, label_tensors in dataloader:
                 image_tensors = image_tensors.to(device)
                 span = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 span[0].record()
-                out_dec = model(image_tensors, text=None, return_loss=False, test_speed=False)
-                self.update_scores(out_dec.float(), list(label_tensors[0]), convertor)
+                if attn_beam:
+                    self.update_paths(net.forward_beam(image_tensors, convertor.beam_width)[0][:, 0], list(label_tensors[0]), convertor)
+                else:
+                    out_dec = model(image_tensors, text=None, return_loss=False, test_speed=False)
+                    self.update_scores(out_dec.float(), list(label_tensors[0]), convertor)
                 span[1].record()
                 self._spans.append(span)                                      # read in result(), behind its copy
             return self.result()
         for image_tensors, label_tensors in dataloader:
             image_tensors = image_tensors.to(device)
             start = time.time()
+            if attn_beam:
+                beam = net.forward_beam(image_tensors, convertor.beam_width)
+                label_indexes = [words[0] if words else [] for words in convertor.paths2nbest(*beam)[0]]
+                self.inference_time += time.time() - start
+                self.update(list(label_tensors[0]), convertor.idx2str(label_indexes))
+                continue
             out_dec = model(image_tensors, text=None, return_loss=False, test_speed=False)
             if is_ctc(convertor) and convertor.beam_width > 0:                # the best word of the beam (the kernel, on any device)
                 label_indexes = [words[0] if words else [] for words in convertor.tensor2nbest(out_dec, nbest=1)[0]]

@@ -144,7 +144,10 @@ class DINO_Finetune(ArenaModule):
     NRTR decoder -> TFLoss.  Same constructor (a config object), parameter names and init RNG order as the reference.
     `decoder.type: 'CTCDecoder'` builds the CTC head instead (no reference counterpart): backbone -> CTCDecoder (frame pooling + one
     linear layer) -> CTCLoss, with a CTCConvertor; there is no `encoder` Mlp then.  `decoder.beam_width` > 0 makes evaluation decode by
-    CTC prefix beam search of that width (absent or 0: the greedy rule).  Any other type builds the NRTR recogniser."""
+    CTC prefix beam search of that width (absent or 0: the greedy rule).  Any other type builds the NRTR recogniser; there
+    `decoder.beam_width` > 0 is the width of `forward_beam` (beam search over the attention decoder: n-best words with their
+    log-probabilities), which TextAccuracy then scores the best word of.  `forward_test` and `forward_test_speed` return the greedy
+    probabilities whatever the width: a beam has no per-step distribution to return."""
 
     def __init__(self, config):
         super().__init__()
@@ -156,7 +159,8 @@ class DINO_Finetune(ArenaModule):
         from ..decoder.nrtr_decoder import Mlp, NRTRDecoder
         from ..loss.ce_loss import TFLoss
         from ..modules import vision_transformer as vits
-        self.label_convertor = AttnConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len, with_unknown=True)
+        self.label_convertor = AttnConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len, with_unknown=True,
+                                             beam_width=int(getattr(config, "decoder_beam_width", 0) or 0))    # absent or 0: greedy
         config.arch = config.arch.replace("deit", "vit")
         if config.arch not in vits.__dict__:
             raise NotImplementedError(f"Unknow architecture: {config.arch} (HIP kernels cover vit_tiny / vit_small / vit_base)")
@@ -171,6 +175,7 @@ class DINO_Finetune(ArenaModule):
             d_k=config.decoder_d_k, d_v=config.decoder_d_v, d_model=config.decoder_d_model, d_inner=config.decoder_d_inner,
             n_position=200, dropout=0.1, num_classes=config.decoder_num_classes, max_seq_len=config.decoder_max_seq_len,
             start_idx=config.decoder_start_idx, padding_idx=config.decoder_padding_idx)
+        self.decoder.beam_width = self.label_convertor.beam_width
         self.loss = TFLoss(ignore_index=self.label_convertor.padding_idx)
 
     def _init_ctc(self, config):
@@ -237,6 +242,15 @@ class DINO_Finetune(ArenaModule):
         if self.ctc:
             return self.decoder.forward_test(feat)
         return self.decoder(feat, self.encoder(feat), None, train_mode=False)
+
+    def forward_beam(self, img, beam_width=None):
+        """img [N,3,32,128] -> (paths int32 [N, W, max_seq_len] by rank, -1-padded; lengths int32 [N, W]; scores fp32 [N, W]): the W
+        best words of the NRTR decoder's beam search and their log-probabilities (NRTRDecoder.forward_beam; W defaults to
+        `decoder.beam_width`).  AttnConvertor.paths2nbest turns them into index lists."""
+        if self.ctc:
+            raise NotImplementedError("forward_beam is the NRTR head's; the CTC head's beam is CTCConvertor.tensor2nbest on forward_test")
+        feat = self.extract_feat(img)
+        return self.decoder.forward_beam(feat, self.encoder(feat), beam_width)
 
     def forward_test_speed(self, img):
         feat = self.extract_feat(img)

@@ -939,6 +939,75 @@ def ctc_beam_search(scores, beam_width, normalized=False):
     return paths, lengths, hyp_scores
 
 
+# ------------------------------------------------------------------------------------------ NRTR beam search (kernels/nrtr_beam.h)
+NRTR_MAX_BEAM = 16                                        # ccd_hip.h: CCD_NRTR_MAX_BEAM
+NRTR_UNUSED, NRTR_LIVE, NRTR_FINISHED = 0, 1, 2           # ccd_hip.h: CCD_NRTR_UNUSED ..
+
+
+def nrtr_beam_state(B, beam_width, seq_len, start_idx, pad_idx, device):
+    """The state in front of step 0 -> (seq int64 [B * W, seq_len] = start, padding, ...; score fp64 [B, W] = 0, -inf, ...; state int32
+    [B, W] = live, unused, ...; parent int32 [B, W])."""
+    W = int(beam_width)
+    if not 1 <= W <= NRTR_MAX_BEAM:
+        raise ValueError(f"nrtr_beam_state: beam_width must lie in 1..{NRTR_MAX_BEAM}, got {beam_width}")
+    seq = torch.full((B * W, seq_len), pad_idx, dtype=I64, device=device)
+    seq[:, 0] = start_idx
+    score = torch.full((B, W), float("-inf"), dtype=F64, device=device)
+    score[:, 0] = 0.0
+    state = torch.zeros((B, W), dtype=I32, device=device)
+    state[:, 0] = NRTR_LIVE
+    return seq, score, state, torch.full((B, W), -1, dtype=I32, device=device)
+
+
+def nrtr_beam_step(logits, C, step, end_idx, pad_idx, seq, score, state, parent, final=False):
+    """One decoding position of the beam over the NRTR decoder, in place: logits fp32 [B * W, ld >= C] (row b * W + r = slot r of sample
+    b), seq int64 [B * W, seq_len], score fp64 [B, W], state int32 [B, W], parent int32 [B, W] (written) - the layout of ccd_hip.h.
+    Writes seq[:, step + 1].  final=True also returns (paths int32 [B, W, seq_len - 1] by rank, -1-padded; lengths int32 [B, W], -1
+    for an unused slot; hyp_scores fp32 [B, W], -inf for an unused slot) of the new state, as ctc_beam_search returns them."""
+    if score.dim() != 2 or not 1 <= score.shape[1] <= NRTR_MAX_BEAM:
+        raise ValueError(f"nrtr_beam_step: score must be [B, W] with W in 1..{NRTR_MAX_BEAM}, got {list(score.shape)}")
+    B, W = score.shape
+    for name, t, dtype in (("score", score, F64), ("state", state, I32), ("parent", parent, I32), ("seq", seq, I64), ("logits", logits, F32)):
+        if t.dtype != dtype:
+            raise ValueError(f"nrtr_beam_step: {name} must be {dtype}, got {t.dtype}")
+    for name, t in (("score", score), ("state", state), ("parent", parent)):
+        if tuple(t.shape) != (B, W) or not t.is_contiguous():
+            raise ValueError(f"nrtr_beam_step: {name} must be contiguous [{B}, {W}], got {list(t.shape)}")
+    if seq.dim() != 2 or seq.shape[0] != B * W or not seq.is_contiguous():
+        raise ValueError(f"nrtr_beam_step: seq must be contiguous [{B * W}, seq_len], got {list(seq.shape)}")
+    if logits.dim() != 2 or logits.shape[0] != B * W or logits.stride(1) != 1 or not 1 <= int(C) <= logits.shape[1]:
+        raise ValueError(f"nrtr_beam_step: expects logits [{B * W}, >= {C}] with dense rows, got {list(logits.shape)}")
+    seq_len = seq.shape[1]
+    if not 0 <= int(step) <= seq_len - 2:
+        raise ValueError(f"nrtr_beam_step: step must lie in 0..seq_len - 2 = {seq_len - 2}, got {step}")
+    if not 0 <= int(end_idx) < int(C) or not 0 <= int(pad_idx) < 65536:
+        raise ValueError(f"nrtr_beam_step: end_idx must lie in [0, {C}) and pad_idx in [0, 65536), got {end_idx}, {pad_idx}")
+    out = (None, None, None)
+    if final:
+        out = (torch.empty((B, W, seq_len - 1), dtype=I32, device=seq.device), torch.empty((B, W), dtype=I32, device=seq.device),
+               torch.empty((B, W), dtype=F32, device=seq.device))
+    _call("ccd_nrtr_beam_step", logits, logits.stride(0), B, W, int(C), int(step), int(end_idx), int(pad_idx), seq, seq_len, score, state,
+          parent, *out)
+    return out if final else None
+
+
+def nrtr_beam_reorder(cache, parent, positions, step):
+    """The decode loop's cache bf16 [L, B * W * positions, 3 D] (q | k | v of position t of slot r of sample b in row (b * W + r) *
+    positions + t), in place: for every position <= step, the K and V columns of slot r become those of slot parent[r] (int32 [B, W];
+    -1 or r: nothing moves).  The Q columns of those positions are unspecified afterwards; the positions behind `step` stay."""
+    if parent.dim() != 2 or parent.dtype != I32 or not parent.is_contiguous() or not 1 <= parent.shape[1] <= NRTR_MAX_BEAM:
+        raise ValueError(f"nrtr_beam_reorder: parent must be contiguous int32 [B, W] with W in 1..{NRTR_MAX_BEAM}, got "
+                         f"{parent.dtype} {list(parent.shape)}")
+    B, W = parent.shape
+    if cache.dtype != BF16 or cache.dim() != 3 or not cache.is_contiguous() or cache.shape[1] != B * W * int(positions) or \
+            cache.shape[2] % 24:
+        raise ValueError(f"nrtr_beam_reorder: cache must be contiguous bfloat16 [L, {B * W} * {positions}, 3 D] with D a multiple of 8, got "
+                         f"{cache.dtype} {list(cache.shape)}")
+    if not 0 <= int(step) < int(positions):
+        raise ValueError(f"nrtr_beam_reorder: step must lie in 0..positions - 1 = {int(positions) - 1}, got {step}")
+    _call("ccd_nrtr_beam_reorder", cache, parent, cache.shape[0], B, W, int(positions), cache.shape[2] // 3, int(step))
+
+
 class SsimFn(torch.autograd.Function):
     """apply(window, taps, size_average, img1, img2[, img3]) -> mean (0-dim) or per-image means [N]; backward on the kernels."""
 

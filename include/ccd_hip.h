@@ -488,6 +488,44 @@ int ccd_ctc_greedy(const float* logits, long sample_stride, long step_stride, in
 int ccd_ctc_beam_search(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
                         int beam, int* paths, int* lengths, float* hyp_scores, void* stream);
 
+/* Beam search over the NRTR attention decoder (ABI 22; kernels/nrtr_beam.h, restated in numpy in tests/nrtr_beam_np.py).  The decode
+ * loop (finetune_engine.beam_decode) runs the incremental decoder on batch * beam rows, row b * beam + r = slot r of sample b, and calls
+ * these two at the end of every step.
+ * State of a sample, slots ordered by rank:
+ *   seq     int64 [batch * beam, seq_len]: the tokens of every slot as ccd_dec_embed_fwd / ccd_dec_attn_fwd read them; position 0 holds
+ *           the start token, positions behind the last decoded one the padding token.  Tokens are < 65536.
+ *   score   fp64 [batch, beam]: the sum of log_softmax(logits)[token] over the slot's steps; -inf for an unused slot.
+ *   state   int32 [batch, beam]: CCD_NRTR_UNUSED (0), CCD_NRTR_LIVE (1), CCD_NRTR_FINISHED (2).
+ *   Before step 0: slot 0 live with score 0, the others unused with score -inf; every row of seq = start, padding, padding, ...
+ * ccd_nrtr_beam_step, one wavefront per sample, updates the state in place for decoding position `step` (it writes seq[:, step + 1]):
+ *   logits  fp32 [batch * beam, ldl >= classes]; only the rows of live slots are read.
+ *   A live slot r gives the candidates (r, c), c < classes, of score[r] + log_softmax(logits[r])[c]: fp64 over the fp32 row, the sum
+ *   over the classes in ascending order; a -inf logit gives no candidate.  A finished slot gives (r, end_idx) alone: score unchanged,
+ *   still finished, pad_idx is the token written.  An unused slot gives none.  The new slots are the `beam` best candidates by score
+ *   descending, then r * classes + c ascending; slots left over are unused (score -inf, parent -1, token pad_idx).  Class end_idx
+ *   finishes a hypothesis; the end_idx token is written.  A new slot's sequence is its parent's positions 0..step and the new token.
+ *   parent  int32 [batch, beam], written: the old slot every new slot continues, -1 for an unused one.
+ *   paths / lengths / hyp_scores: all three or none (pass them with the last step); written as ccd_ctc_beam_search writes them from the
+ *   new state: paths int32 [batch, beam, seq_len - 1], the classes in front of the first end_idx behind position 0, padded with -1;
+ *   lengths int32 [batch, beam], step + 1 for a hypothesis that has not finished, -1 for an unused slot; hyp_scores fp32 [batch, beam],
+ *   the score rounded once (the end_idx term included), -inf for an unused slot.
+ * ccd_nrtr_beam_reorder permutes the cache of the incremental decoder by `parent`, in place:
+ *   cache   bf16 [layers, batch * beam * positions, 3 D], 16-byte aligned, D % 8 == 0: the q | k | v columns of position t of slot r of
+ *           sample b in row (b * beam + r) * positions + t.  For every position <= step the K and V columns (D .. 3 D) of slot r become
+ *           those slot parent[r] held before the call, whatever cycles or shared parents the permutation has; the Q columns (never read
+ *           again) and the positions behind `step` stay.  A slot with parent[r] == r or outside [0, beam) moves nothing.
+ * No atomics: the same input gives the same bits.  batch == 0 (or layers == 0) is a no-op.  CCD_EINVAL: a missing pointer, a negative
+ * size, stride or step, paths / lengths / hyp_scores given in part, a misaligned cache; CCD_ESHAPE: beam outside 1..CCD_NRTR_MAX_BEAM,
+ * classes outside 1..128, ldl < classes, seq_len outside 2..128, step + 2 > seq_len (step >= positions for the reorder), end_idx outside
+ * [0, classes), pad_idx outside [0, 65536), D not a positive multiple of 8.  Nothing is launched on an error. */
+#define CCD_NRTR_MAX_BEAM 16
+#define CCD_NRTR_UNUSED 0
+#define CCD_NRTR_LIVE 1
+#define CCD_NRTR_FINISHED 2
+int ccd_nrtr_beam_step(const float* logits, long ldl, int batch, int beam, int classes, int step, int end_idx, int pad_idx, int64_t* seq,
+                       int seq_len, double* score, int* state, int* parent, int* paths, int* lengths, float* hyp_scores, void* stream);
+int ccd_nrtr_beam_reorder(ccd_bf16* cache, const int* parent, int layers, int batch, int beam, int positions, int D, int step, void* stream);
+
 /* ---------------------------------------------------------------- DINOHead pieces, vit.py:313,326 */
 int ccd_l2norm_fwd(const ccd_bf16* x, ccd_bf16* y, float* inv, int max_rows, const int* d_rows, int rows_mul, int D,
                    void* stream);

@@ -66,7 +66,8 @@ def main():
     ap.add_argument("--checkpoint", type=str, default=None)
     ap.add_argument("--test_root", type=str, default=None)
     ap.add_argument("--batch_size", type=int, default=None)
-    ap.add_argument("--beam_width", type=int, default=None, help="CTC head: prefix beam search of this width (0: greedy decoding)")
+    ap.add_argument("--beam_width", type=int, default=None,
+                    help="beam search of this width, 1..16, for either head (CTC: prefix beam search; NRTR: beam over the decoder); 0: greedy decoding")
     a = ap.parse_args()
     config = Config(a.config)
     if a.checkpoint is not None:

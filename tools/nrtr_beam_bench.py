@@ -1,0 +1,195 @@
+#!/usr/bin/env python3
+"""Time beam search over the NRTR decoder (kernels/nrtr_beam.h, finetune_engine.beam_decode) on the GPU.
+
+    python tools/nrtr_beam_bench.py [--iters 30] [--rounds 5] [--out profiles/nrtr_beam.json]
+
+The cases, each in a process of its own under its own time limit; the next one starts only if the one before ended well:
+  kernels  ccd_nrtr_beam_step and ccd_nrtr_beam_reorder per launch at B = 512, T = 25, C = 92 (logits rows 128 wide), D = 512,
+           L = 6, beam widths 1, 4, 8, 16.  The step kernel runs on a state some steps into a peaked random decode; the reorder
+           kernel permutes positions 0..12 and 0..24 by a random permutation per sample, so every row moves (the worst case: in a
+           decode the slots that keep their rank move nothing), with the bytes it reads and writes and the rate;
+  eval     evaluation images/s at B = 512, vit_small, eval mode: forward_test (greedy, HIP graph) against forward_beam at widths
+           1, 4, 8 (HIP graph), rounds alternating;
+  rescore  the yardstick of tests/test_nrtr_beam_gpu.py: with that test's model (vit_tiny, 2 decoder layers, its seed, images and
+           <EOS> bias) the largest |sum log p_incremental - sum log p_full| along the greedy paths of greedy_decode against
+           greedy_decode_full ("rescore_base"; the test gates the beam's scores against teacher forcing at 4 x that).
+Warm-up first, HIP events around every timed call, a figure is the median of the round medians with the lowest and highest
+round.  No threshold is set; the file records what was measured.  `--case NAME` runs one case and prints its JSON line."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+B, T, C, D, L = 512, 25, 92, 512, 6
+WIDTHS = (1, 4, 8, 16)
+LIMITS = {"kernels": 240, "eval": 420, "rescore": 180}                   # seconds per case
+
+
+def event_ms(fn, iters):
+    import torch
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return statistics.median(a.elapsed_time(b) for a, b in ev)
+
+
+def summary(rounds):
+    return {"median_ms": round(statistics.median(rounds), 4), "lowest_ms": round(min(rounds), 4), "highest_ms": round(max(rounds), 4)}
+
+
+def case_kernels(a):
+    import torch
+    from ccd_amd import ops
+    dev = torch.device("cuda")
+    out = {"shape": {"B": B, "T": T, "C": C, "D": D, "L": L}}
+    for W in WIDTHS:
+        g = torch.Generator().manual_seed(W)
+        logits = torch.randn(B * W, 128, generator=g) * 2.0
+        logits.scatter_add_(1, torch.randint(0, C, (B * W, 1), generator=g), torch.full((B * W, 1), 6.0))
+        logits = logits.to(dev)
+        seq, score, state, parent = ops.nrtr_beam_state(B, W, T + 1, C - 1, C, dev)
+        for s in range(8):                                                    # eight steps in: every slot is in use
+            ops.nrtr_beam_step(logits.roll(s, 0), C, s, C - 1, C, seq, score, state, parent)
+        saved = [t.clone() for t in (seq, score, state)]
+
+        def step():
+            for t, keep in zip((seq, score, state), saved):
+                t.copy_(keep)
+            ops.nrtr_beam_step(logits, C, 8, C - 1, C, seq, score, state, parent)
+
+        def restore():
+            for t, keep in zip((seq, score, state), saved):
+                t.copy_(keep)
+
+        cache = torch.zeros((L, B * W * (T + 1), 3 * D), dtype=torch.bfloat16, device=dev)
+        perm = torch.stack([torch.randperm(W, generator=g) for _ in range(B)]).int().to(dev)
+        moved = float((perm != torch.arange(W, device=dev)).sum())
+        entry = {}
+        with_copy, copies = [], []
+        reorder = {12: [], 24: []}
+        for _ in range(a.rounds):
+            with_copy.append(event_ms(step, a.iters))
+            copies.append(event_ms(restore, a.iters))
+            for s in reorder:
+                reorder[s].append(event_ms(lambda: ops.nrtr_beam_reorder(cache, perm, T + 1, s), a.iters))
+        entry["step_with_state_restore"] = summary(with_copy)
+        entry["state_restore_alone"] = summary(copies)
+        entry["step_kernel_ms"] = round(entry["step_with_state_restore"]["median_ms"] - entry["state_restore_alone"]["median_ms"], 4)
+        for s, rounds in reorder.items():
+            r = summary(rounds)
+            nbytes = 2.0 * L * moved * (s + 1) * 2 * D * 2                     # read + write of the K | V columns that move
+            r["gigabytes_moved"] = round(nbytes * 1e-9, 3)
+            r["gigabytes_per_s"] = round(nbytes * 1e-9 / (r["median_ms"] * 1e-3), 1) if moved else 0.0
+            entry[f"reorder_positions_0_to_{s}"] = r
+        entry["rows_that_move"] = f"{int(moved)} of {B * W}"
+        out[f"w{W}"] = entry
+        del cache
+    return out
+
+
+def case_eval(a):
+    import torch
+    from ccd_amd import finetune as ft
+    dev = torch.device("cuda")
+    torch.manual_seed(0)
+    model = ft.build_model(ft.FinetuneConfig(), dev, dropout=0.0).eval()
+    img = torch.randn(B, 3, 32, 128, generator=torch.Generator().manual_seed(4)).to(dev)
+    sides = {0: [], 1: [], 4: [], 8: []}
+    iters = max(3, a.iters // 6)
+    with torch.no_grad():
+        for _ in range(a.rounds):
+            for width in sides:
+                fn = (lambda: model.forward_test(img)) if width == 0 else (lambda: model.forward_beam(img, width))
+                sides[width].append(event_ms(fn, iters))
+    out = {"batch": B, "arch": "vit_small", "decode_graph": os.environ.get("CCD_DECODE_GRAPH", "1") != "0"}
+    for width, rounds in sides.items():
+        name = "greedy" if width == 0 else f"beam_width_{width}"
+        out[name] = summary(rounds)
+        out[name + "_images_per_s"] = round(B / (out[name]["median_ms"] * 1e-3))
+    return out
+
+
+def case_rescore(a):
+    import numpy as np
+    import torch
+    from ccd_amd import finetune as ft, finetune_engine as fe
+    dev = torch.device("cuda")
+    out = {}
+    for bias in a.end_bias:
+        torch.manual_seed(2)
+        model = ft.build_model(ft.FinetuneConfig(arch="vit_tiny", drop_path_rate=0.0, decoder_n_layers=2), dev).eval()
+        with torch.no_grad():
+            model.arena.w("decoder.classifier.bias")[91] += bias
+        model.arena.refresh_mirrors()
+        worst, compared, lengths = 0.0, 0, []
+        for n in (5, 16):
+            img = torch.randn(n, 3, 32, 128, generator=torch.Generator().manual_seed(5 + n))      # tests/test_nrtr_beam_gpu.py: images()
+            g = torch.Generator().manual_seed(50 + n)
+            img = (img * 0.25 + 2.0 * torch.randn(n, 3, 1, 1, generator=g) + torch.randn(n, 3, 1, 128, generator=g)).to(dev)
+            with torch.no_grad():
+                feat = model.extract_feat(img)
+                out_enc = model.encoder(feat).to(torch.bfloat16)
+                model.decoder._ready()
+                inc = fe.greedy_decode(model.decoder, out_enc).double().cpu().numpy()
+                full = fe.greedy_decode_full(model.decoder, out_enc).double().cpu().numpy()
+            for b in range(n):
+                tok_i, tok_f = inc[b].argmax(-1), full[b].argmax(-1)
+                ends = np.nonzero(tok_i == 91)[0]
+                steps = int(ends[0]) + 1 if len(ends) else inc.shape[1]
+                lengths.append(steps - 1 if len(ends) else steps)
+                if (tok_i[:steps] == tok_f[:steps]).all():
+                    t = np.arange(steps)
+                    worst = max(worst, abs(float(np.log(inc[b, t, tok_i[:steps]]).sum() - np.log(full[b, t, tok_i[:steps]]).sum())))
+                    compared += 1
+        out[f"end_bias_{bias:g}"] = {"rescore_base": worst, "greedy_paths_compared": compared, "greedy_word_lengths": lengths}
+    return out
+
+
+CASES = {"kernels": case_kernels, "eval": case_eval, "rescore": case_rescore}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--case", choices=sorted(CASES), default=None)
+    ap.add_argument("--cases", default="kernels,eval,rescore", help="comma-separated cases of a whole run, in order")
+    ap.add_argument("--end_bias", type=float, nargs="+", default=[0.5], help="rescore: the <EOS> bias of tests/test_nrtr_beam_gpu.py (END_BIAS)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.case is not None:
+        import torch
+        assert torch.cuda.is_available(), "nrtr_beam_bench needs an MI355X"
+        print(json.dumps({a.case: CASES[a.case](a)}))
+        return
+    out = {"iters": a.iters, "rounds": a.rounds, "unit": "ms per call, HIP events (median of round medians; lowest and highest round)"}
+    names = [n for n in a.cases.split(",") if n]
+    assert names and all(n in CASES for n in names), f"--cases takes names out of {sorted(CASES)}"
+    for name in names:
+        # a fresh process per case under its own time limit; a case that fails or runs out of time ends the run
+        run = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name, "--iters", str(a.iters), "--rounds", str(a.rounds),
+                              "--end_bias"] + [str(b) for b in a.end_bias], capture_output=True, text=True, timeout=LIMITS[name])
+        if run.returncode != 0:
+            sys.stderr.write(run.stdout[-2000:] + run.stderr[-4000:])
+            sys.exit(f"nrtr_beam_bench: case {name} ended with status {run.returncode}; nothing further was started")
+        out.update(json.loads(run.stdout.strip().splitlines()[-1]))
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(json.dumps(out, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()

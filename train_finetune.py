@@ -206,7 +206,8 @@ def _parse_arguments():
     parser = argparse.ArgumentParser()
     parser.add_argument("-c", "--config", type=str, required=True, help="path to config file")
     parser.add_argument("--local_rank", "--local-rank", default=0, type=int, help="set by the launcher; ignored")
-    parser.add_argument("--beam_width", type=int, default=None, help="CTC head: evaluate with prefix beam search of this width (0: greedy)")
+    parser.add_argument("--beam_width", type=int, default=None,
+                        help="evaluate with beam search of this width, 1..16, for either head (CTC: prefix beam search; NRTR: beam over the decoder); 0: greedy")
     args, _ = parser.parse_known_args()
     config = Config(args.config)
     if args.beam_width is not None:
