@@ -14,6 +14,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import checked_beam_width, nbest_lists
+
 _DIGITS_LOWER = "0123456789abcdefghijklmnopqrstuvwxyz"
 _UPPER_PUNCT = "ABCDEFGHIJKLMNOPQRSTUVWXYZ!\"#$%&'()*+,-./:;<=>?@[\\]_`~"
 ALPHABETS = {
@@ -58,10 +60,8 @@ class AttnConvertor:
             raise AssertionError("dictionary holds a character twice")
         self.with_unknown, self.max_seq_len = bool(with_unknown), int(max_seq_len)
         self.lower, self.start_end_same = bool(lower), bool(start_end_same)
-        self.beam_width = int(beam_width or 0)
         from ..ops import NRTR_MAX_BEAM
-        if not 0 <= self.beam_width <= NRTR_MAX_BEAM:
-            raise ValueError(f"beam_width must lie in 0..{NRTR_MAX_BEAM} (0: greedy decoding), got {beam_width}")
+        self.beam_width = checked_beam_width(beam_width, NRTR_MAX_BEAM)
         # special classes behind the alphabet, in the reference's order
         self.idx2char = alphabet
         self.unknown_idx = self._append("<UKN>") if self.with_unknown else None
@@ -172,12 +172,7 @@ class AttnConvertor:
         """What DINO_Finetune.forward_beam returns - paths [N, W, T], lengths [N, W], scores [N, W] - -> (indexes, log_probs) as
         CTCConvertor.tensor2nbest returns them: indexes[i] holds up to `nbest` index lists, best first (an unused slot gives none);
         log_probs is a float tensor [N, nbest] on the host, the log-probability of each word with its <EOS>, -inf for an unused slot."""
-        nbest = int(nbest)
         if paths.dim() != 3 or tuple(lengths.shape) != tuple(paths.shape[:2]) or tuple(scores.shape) != tuple(paths.shape[:2]):
             raise ValueError(f"paths2nbest: expects paths [N, W, T], lengths [N, W] and scores [N, W], got {list(paths.shape)}, "
                              f"{list(lengths.shape)}, {list(scores.shape)}")
-        if not 1 <= nbest <= paths.shape[1]:
-            raise ValueError(f"paths2nbest: nbest must lie in 1..beam_width = {paths.shape[1]}, got {nbest}")
-        paths, lengths = paths[:, :nbest].cpu().numpy(), lengths[:, :nbest].cpu().numpy()
-        indexes = [[paths[i, r, :lengths[i, r]].tolist() for r in range(nbest) if lengths[i, r] >= 0] for i in range(paths.shape[0])]
-        return indexes, scores[:, :nbest].float().cpu()
+        return nbest_lists("paths2nbest", paths, lengths, scores, nbest)

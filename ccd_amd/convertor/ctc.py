@@ -15,6 +15,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import checked_beam_width, nbest_lists
 from .attn import ALPHABETS, _NO_CLASS, _read_alphabet_file
 
 
@@ -41,10 +42,8 @@ class CTCConvertor:
         if len(set(alphabet)) != len(alphabet):
             raise AssertionError("dictionary holds a character twice")
         self.with_unknown, self.max_seq_len, self.lower = bool(with_unknown), int(max_seq_len), bool(lower)
-        self.beam_width = int(beam_width or 0)
         from ..ops import CTC_MAX_BEAM
-        if not 0 <= self.beam_width <= CTC_MAX_BEAM:
-            raise ValueError(f"beam_width must lie in 0..{CTC_MAX_BEAM} (0: greedy decoding), got {beam_width}")
+        self.beam_width = checked_beam_width(beam_width, CTC_MAX_BEAM)
         self.blank_idx = 0
         self.idx2char = ["<BLK>"] + alphabet
         self.unknown_idx = None
@@ -137,12 +136,6 @@ class CTCConvertor:
         probability summed over the alignments the beam kept, -inf where a slot is empty."""
         from .. import ops
         width = self.beam_width if beam_width is None else int(beam_width)
-        nbest = int(nbest)
         if width < 1:
             raise ValueError("tensor2nbest: needs a beam_width >= 1 (the convertor's is 0: greedy decoding)")
-        if not 1 <= nbest <= width:
-            raise ValueError(f"tensor2nbest: nbest must lie in 1..beam_width = {width}, got {nbest}")
-        paths, lengths, scores = ops.ctc_beam_search(outputs.float(), width, normalized=normalized)
-        paths, lengths = paths[:, :nbest].cpu().numpy(), lengths[:, :nbest].cpu().numpy()
-        indexes = [[paths[i, r, :lengths[i, r]].tolist() for r in range(nbest) if lengths[i, r] >= 0] for i in range(paths.shape[0])]
-        return indexes, scores[:, :nbest].cpu()
+        return nbest_lists("tensor2nbest", *ops.ctc_beam_search(outputs.float(), width, normalized=normalized), nbest)

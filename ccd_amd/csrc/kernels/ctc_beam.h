@@ -15,33 +15,24 @@
 // scores, keeps their log-probabilities in registers and scans the candidates (i, l) and (i, l + 64) of every entry i - at most
 // 2 W = 32 candidates per lane, none of them stored: a candidate's score is one add of the entry's pb or tot (read from LDS at a
 // wave-uniform address: a broadcast) and the lane's own lp, minus the candidates a 64-bit mask per (entry, half) marks as merged.
-// Selection is W rounds of a wave arg-max on the key (score, k): each lane folds the candidates it has not given away yet (a 32-bit
-// mask in a register), six xor-shuffle steps fold the lanes.  The entries (pb, pnb, length, last class) and the prefixes - bytes,
-// classes are < 128; two buffers of W x 64, swapped per frame - live in LDS: 4.1 KB per wave, 16.5 KB per workgroup.
+// The log-probabilities of a frame and the selection - W rounds of a wave arg-max, each lane folding the candidates it has not given
+// away yet (a 32-bit mask in a register) - are the steps of beam_wave.h, shared with nrtr_beam_step_kernel.  The entries (pb, pnb,
+// length, last class) and the prefixes - bytes, classes are < 128; two buffers of W x 64, swapped per frame - live in LDS: 4.1 KB per
+// wave, 16.5 KB per workgroup.
 // The merge test: the 16 x 16 pairs (i, j) four to a lane, prefiltered on len_j = len_i + 1 and on the last class of prefix_i; the
 // survivors (a ballot mask, so the walk is wave-uniform) compare the len_i positions one per lane and a second ballot decides.
 //
 // Every loop that shuffles or ballots has a wave-uniform trip count (T, W, the live entries, the bits of a ballot mask); no lane
-// of a live wave leaves before the last shuffle; no atomics: the same input gives the same bits.
-//
-// Arithmetic is fp64 (ctc_real) throughout, log-softmax included: the selection compares scores whose neighbours lie 1e-5 nats
-// apart at |score| ~ 150, which is one fp32 ulp.  log-sum-exp of nothing is -inf, never NaN; values are finite or -inf, and -inf
-// masks a class.  The sum over the classes of a frame runs in ascending class order (every lane adds the same 128 LDS words).
-// What the software fp64 exp / log and the W-fold rescan cost on the device: tools/ctc_bench.py, case `beam`.
+// of a live wave leaves before the last shuffle.  Arithmetic is fp64 (ctc_real) throughout; probabilities (normalized) go through the
+// same ascending-order sum as logits.  What the software fp64 exp / log and the W-fold rescan cost on the device: tools/ctc_bench.py,
+// case `beam`.
 #pragma once
 
-#include "ctc.h"
+#include "beam_wave.h"
 
 namespace ccd {
 
 constexpr int CTC_MAX_BEAM = 16;
-
-// log(exp(a) + exp(b)); -inf when both are
-__device__ __forceinline__ ctc_real ctc_lae(ctc_real a, ctc_real b) {
-    const ctc_real m = a > b ? a : b, lo = a > b ? b : a;
-    if (m == ctc_neg_inf()) return m;
-    return m + ::log1p(::exp(lo - m));
-}
 
 struct CtcBeamWave {
     ctc_real lp[CTC_MAX_C];                                      // this frame: first the terms of the sum, then the log-probabilities
@@ -81,39 +72,8 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
             next1 = has1 ? p[c1] : 0.f;
         }
         // ---- log-probabilities of the lane's two classes
-        ctc_real num0, num1, e0, e1;
-        bool live0, live1;
-        if (normalized) {
-            live0 = has0 && v0 > 0.f;
-            live1 = has1 && v1 > 0.f;
-            e0 = live0 ? (ctc_real)v0 : 0;
-            e1 = live1 ? (ctc_real)v1 : 0;
-            num0 = live0 ? ::log(e0) : 0;
-            num1 = live1 ? ::log(e1) : 0;
-        } else {
-            const float ninf = -__builtin_inff();
-            float mx = has0 ? v0 : ninf;
-            mx = has1 && v1 > mx ? v1 : mx;
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const float o = shfl_xor(mx, m);
-                mx = o > mx ? o : mx;
-            }
-            live0 = has0 && v0 > ninf;
-            live1 = has1 && v1 > ninf;
-            num0 = live0 ? (ctc_real)v0 - (ctc_real)mx : 0;
-            num1 = live1 ? (ctc_real)v1 - (ctc_real)mx : 0;
-            e0 = live0 ? ::exp(num0) : 0;
-            e1 = live1 ? ::exp(num1) : 0;
-        }
-        if (has0) s.lp[c0] = e0;
-        if (has1) s.lp[c1] = e1;
-        wave_lds_fence();
-        ctc_real sum = 0;
-        for (int c = 0; c < C; ++c) sum += s.lp[c];                        // ascending class order, the same on every lane
-        const ctc_real lsum = ::log(sum);
-        const ctc_real lp0 = live0 ? num0 - lsum : ctc_neg_inf(), lp1 = live1 ? num1 - lsum : ctc_neg_inf();
-        wave_lds_fence();
+        const CtcReal2 lp = beam_wave_log_probs(v0, v1, has0, has1, normalized, s.lp, C);
+        const ctc_real lp0 = lp.c0, lp1 = lp.c1;
         if (has0) s.lp[c0] = lp0;
         if (has1) s.lp[c1] = lp1;
         if (lane < n) {
@@ -186,15 +146,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
                     }
                 }
             }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const ctc_real os = shfl_xor(best, m);
-                const int ok = shfl_xor(best_k, m);
-                if (os > best || (os == best && ok < best_k)) {
-                    best = os;
-                    best_k = ok;
-                }
-            }
+            beam_wave_best(best, best_k);
             if (best > ctc_neg_inf()) {                                    // wave-uniform: every lane holds the same winner
                 const int i = best_k / C, c = best_k - i * C, li = s.len[i];
                 if (lane == (c & 63)) given |= 1u << (2 * i + (c >> 6));

@@ -15,13 +15,12 @@
 // and l + 64 of every slot and the positions l and l + 64 of every sequence, in every role: it loads them, it scans them, it stores
 // them - so whatever a lane writes to global memory it has read itself before, and the update is in place without a second buffer.
 //   1. every old sequence (positions 0..step, as 16-bit tokens) and the old scores / states go to LDS;
-//   2. per live slot: row maximum by shuffles, exp(x - max) in fp64 to LDS, the sum in ascending class order (every lane adds the same
-//      C words), then cand[r][c] = score[r] + (x - max - log sum).  Finished: cand[r][end_idx] = score[r].  Everything else -inf;
-//   3. W rounds of a wave arg-max on the key (score, k): a lane folds its <= 2 W candidates (k ascends along the scan, `>` keeps the
-//      lowest of equals), six xor-shuffle steps fold the lanes; the owner of the winner overwrites it with -inf.  Lane r keeps rank r;
+//   2. per live slot: cand[r][c] = score[r] + log_softmax(logits[r])[c] (beam_wave.h; the slot's row of the table holds the terms
+//      of the sum on the way).  Finished: cand[r][end_idx] = score[r].  Everything else -inf;
+//   3. W rounds of the wave arg-max of beam_wave.h over the table; the owner of the winner overwrites it with -inf.  Lane r keeps
+//      rank r;
 //   4. the new rows: positions 0..step from the parent's row in LDS, position step + 1 the new token; score, state, parent by lane r.
-// Every loop that shuffles has a wave-uniform trip count (W, the slots); no atomics: the same input gives the same bits.
-// fp64 throughout (ctc_real): neighbouring candidates lie closer than an fp32 ulp at |score| ~ 100.
+// Every loop that shuffles has a wave-uniform trip count (W, the slots).  fp64 throughout (ctc_real).
 //
 // Reorder kernel: pure data movement.  One thread owns the same 16-byte piece of the K | V columns of one (layer, sample, position)
 // in all W rows: it loads the piece of row parent[r] for every r whose parent differs (compile-time register index r, the gather is
@@ -29,7 +28,7 @@
 // because no other thread touches these bytes; rows with parent[r] == r (or an unused slot, parent -1) move nothing.
 #pragma once
 
-#include "ctc.h"
+#include "beam_wave.h"
 
 namespace ccd {
 
@@ -82,24 +81,9 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restr
         const ctc_real sc = s.score[r];
         if (st == NRTR_LIVE) {
             const float* const x = logits + (row0 + r) * ldl;
-            const float v0 = has0 ? x[c0] : ninf, v1 = has1 ? x[c1] : ninf;
-            float mx = v0 > v1 ? v0 : v1;
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const float o = shfl_xor(mx, m);
-                mx = o > mx ? o : mx;
-            }
-            const bool live0 = has0 && v0 > ninf, live1 = has1 && v1 > ninf;
-            const ctc_real num0 = live0 ? (ctc_real)v0 - (ctc_real)mx : 0, num1 = live1 ? (ctc_real)v1 - (ctc_real)mx : 0;
-            if (has0) s.cand[r][c0] = live0 ? ::exp(num0) : 0;
-            if (has1) s.cand[r][c1] = live1 ? ::exp(num1) : 0;
-            wave_lds_fence();
-            ctc_real sum = 0;
-            for (int c = 0; c < C; ++c) sum += s.cand[r][c];               // ascending class order, the same on every lane
-            const ctc_real lsum = ::log(sum);
-            wave_lds_fence();
-            if (has0) s.cand[r][c0] = live0 ? sc + (num0 - lsum) : ctc_neg_inf();
-            if (has1) s.cand[r][c1] = live1 ? sc + (num1 - lsum) : ctc_neg_inf();
+            const CtcReal2 lp = beam_wave_log_probs(has0 ? x[c0] : ninf, has1 ? x[c1] : ninf, has0, has1, false, s.cand[r], C);
+            if (has0) s.cand[r][c0] = sc + lp.c0;                          // (-inf stays -inf: a score is finite or -inf)
+            if (has1) s.cand[r][c1] = sc + lp.c1;
         } else {
             const bool carry = st == NRTR_FINISHED;
             if (has0) s.cand[r][c0] = carry && c0 == end_idx ? sc : ctc_neg_inf();
@@ -130,15 +114,7 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restr
                 }
             }
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            const ctc_real os = shfl_xor(best, m);
-            const int ok = shfl_xor(best_k, m);
-            if (os > best || (os == best && ok < best_k)) {
-                best = os;
-                best_k = ok;
-            }
-        }
+        beam_wave_best(best, best_k);
         if (best > ctc_neg_inf()) {                                        // wave-uniform: every lane holds the same winner
             const int i = best_k / C, c = best_k - i * C;
             if (lane == (c & 63)) s.cand[i][c] = ctc_neg_inf();            // (only this lane ever reads the entry again)

@@ -134,12 +134,12 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
             return self._graphed_decode(out_enc)
         return fe.greedy_decode(self, out_enc)
 
-    def _graphed_decode(self, out_enc):
-        """The 25 greedy steps launch ~1 800 small kernels (6 layers x ~12 kernels per step): launch-bound when issued one
-        by one.  The whole loop is captured ONCE per (batch size, arena) into a HIP graph and replayed; the graph reads
-        the arena / packed operands in place, so optimizer steps between evaluations need no re-capture."""
-        key = (tuple(out_enc.shape), out_enc.device, self.arena.flat.data_ptr())
-        entry = self._graphs.get(key)
+    def _replay(self, graphs, key, decode, out_enc):
+        """The 25 decoding steps launch ~1 800 small kernels (6 layers x ~12 kernels per step): launch-bound when issued one
+        by one.  The whole loop `decode(input)` is captured ONCE per `key` into a HIP graph, on a single stream, and replayed; the
+        graph reads the arena / packed operands in place, so optimizer steps between evaluations need no re-capture.
+        -> the graph's static outputs, which the caller clones."""
+        entry = graphs.get(key)
         if entry is None:
             static_in = torch.empty_like(out_enc)
             static_in.copy_(out_enc)
@@ -147,18 +147,23 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
             side = torch.cuda.Stream(device=out_enc.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):                  # warm-up outside the capture (lazy one-time kernel attributes)
-                fe.greedy_decode(self, static_in)
+                decode(static_in)
             cur.wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                static_out = fe.greedy_decode(self, static_in)
-            if len(self._graphs) >= 4:                     # a few batch shapes at most (last partial batch, ...)
-                self._graphs.pop(next(iter(self._graphs)))
-            entry = self._graphs[key] = (graph, static_in, static_out)
+                static_out = decode(static_in)
+            if len(graphs) >= 4:                           # a few batch shapes at most (last partial batch, ...)
+                graphs.pop(next(iter(graphs)))
+            entry = graphs[key] = (graph, static_in, static_out)
         graph, static_in, static_out = entry
         static_in.copy_(out_enc)
         graph.replay()
-        return static_out.clone()
+        return static_out
+
+    def _graphed_decode(self, out_enc):
+        """One graph per (batch shape, arena)."""
+        key = (tuple(out_enc.shape), out_enc.device, self.arena.flat.data_ptr())
+        return self._replay(self._graphs, key, lambda x: fe.greedy_decode(self, x), out_enc).clone()
 
     def forward_beam(self, feat, out_enc, beam_width=None):
         """Beam search of width `beam_width` (default: self.beam_width, which must then be > 0) -> (paths int32 [N, W, max_seq_len] by
@@ -176,28 +181,10 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
         return fe.beam_decode(self, out_enc, width)
 
     def _graphed_beam(self, out_enc, width):
-        """_graphed_decode for the beam: one graph per (batch shape, arena, width), captured on a single stream."""
+        """One graph per (batch shape, arena, width)."""
         key = (tuple(out_enc.shape), out_enc.device, self.arena.flat.data_ptr(), width)
-        entry = self._beam_graphs.get(key)
-        if entry is None:
-            static_in = torch.empty_like(out_enc)
-            static_in.copy_(out_enc)
-            cur = torch.cuda.current_stream()
-            side = torch.cuda.Stream(device=out_enc.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):                  # warm-up outside the capture (lazy one-time kernel attributes)
-                fe.beam_decode(self, static_in, width)
-            cur.wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                static_out = fe.beam_decode(self, static_in, width)
-            if len(self._beam_graphs) >= 4:
-                self._beam_graphs.pop(next(iter(self._beam_graphs)))
-            entry = self._beam_graphs[key] = (graph, static_in, static_out)
-        graph, static_in, static_out = entry
-        static_in.copy_(out_enc)
-        graph.replay()
-        return tuple(t.clone() for t in static_out)
+        out = self._replay(self._beam_graphs, key, lambda x: fe.beam_decode(self, x, width), out_enc)
+        return tuple(t.clone() for t in out)
 
     def forward_test_speed(self, feat, out_enc, img_metas=None):
         self._ready()

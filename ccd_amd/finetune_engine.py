@@ -350,6 +350,37 @@ def greedy_decode_full(module, out_enc, stop_on_eos_of_first=False):
     return probs[:, :done]
 
 
+def decoder_position(module, s, seq, cache, kv, R, Q):
+    """Position s of the incremental decoder for R hypothesis rows (R / Q samples with Q queries each in the encoder-decoder
+    attention): embed seq[:, s], the L layers (self-attention over the cached positions <= s, whose q | k | v of position s this
+    call writes into `cache`; encoder-decoder attention; MLP), final LayerNorm, classifier -> logits fp32 [R, CLS_PAD]."""
+    arena, pre, spec, packed = module.arena, module.arena_prefix, module.dec_spec, module.packed
+    D, H, T = spec.D, spec.H, spec.max_seq_len + 1
+    scale = 64 ** -0.5
+    x = ops.dec_embed_fwd(seq[:, s].contiguous().view(R, 1), arena.w(pre + "trg_word_emb.weight"), module.pos_table[s:s + 1])
+    for l in range(spec.L):                                                                      # x: [R, D] fp32
+        b = f"{pre}layer_stack.{l}."
+        qkv = cache[l]
+        y, _, _ = ops.ln_fwd(x, arena.w(b + "norm1.weight"), arena.w(b + "norm1.bias"), 1e-5)
+        ops.gemm_nt(y, arena.span(b + "self_attn.linear_q.weight", 3 * D, "wb"), out=qkv.view(R, T, 3 * D)[:, s])
+        att, _, _ = ops.dec_attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], R, H, T, T, scale, tokens=seq,
+                                     pad_idx=spec.padding_idx, causal=True)                      # row s is the new one
+        x = ops.gemm_nt(att.view(R, T, D)[:, s], arena.wb(b + "self_attn.fc.weight"), epilogue=ops.EPI_RESID, resid=x,
+                        rows_per_sample=1)
+        y, _, _ = ops.ln_fwd(x, arena.w(b + "norm2.weight"), arena.w(b + "norm2.bias"), 1e-5)
+        q2 = ops.gemm_nt(y, arena.wb(b + "enc_attn.linear_q.weight"))
+        att, _, _ = ops.dec_attn_fwd(q2, kv[:, l * 2 * D:l * 2 * D + D], kv[:, l * 2 * D + D:(l + 1) * 2 * D], R // Q, H, Q, 256,
+                                     scale)
+        x = ops.gemm_nt(att, arena.wb(b + "enc_attn.fc.weight"), epilogue=ops.EPI_RESID, resid=x, rows_per_sample=1)
+        y, _, _ = ops.ln_fwd(x, arena.w(b + "norm3.weight"), arena.w(b + "norm3.bias"), 1e-5)
+        _, g3 = ops.gemm_nt(y, arena.wb(b + "mlp.w_1.weight"), epilogue=ops.EPI_GELU, bias=arena.w(b + "mlp.w_1.bias"),
+                            store_u=False)
+        x = ops.gemm_nt(g3, arena.wb(b + "mlp.w_2.weight"), epilogue=ops.EPI_RESID, bias=arena.w(b + "mlp.w_2.bias"),
+                        resid=x, rows_per_sample=1)
+    y, _, _ = ops.ln_fwd(x, arena.w(pre + "layer_norm.weight"), arena.w(pre + "layer_norm.bias"), 1e-6)
+    return ops.gemm_nt(y, packed.cls, epilogue=ops.EPI_F32, bias=packed.cls_bias)
+
+
 @torch.no_grad()
 def greedy_decode(module, out_enc, stop_on_eos_of_first=False):
     """Greedy decoding with the SAME result as the reference's loop at 1/25 of its decoder work: under the causal mask the
@@ -358,43 +389,20 @@ def greedy_decode(module, out_enc, stop_on_eos_of_first=False):
     (The reference re-runs all positions of all layers at every step: O(T^2) row-passes.)
     stop_on_eos_of_first: forward_test_speed's early exit (:193-194, `step_result.argmax() == 91` over the flattened
     [B, C] tensor, i.e. sample 0 predicting <EOS>); costs one host sync per step."""
-    arena, pre, spec, packed = module.arena, module.arena_prefix, module.dec_spec, module.packed
+    arena, pre, spec = module.arena, module.arena_prefix, module.dec_spec
     B = out_enc.shape[0]
-    D, H, L, C = spec.D, spec.H, spec.L, spec.C
+    D, L, C = spec.D, spec.L, spec.C
     steps, T = spec.max_seq_len, spec.max_seq_len + 1
     dev = out_enc.device
-    scale = 64 ** -0.5
-    packed.refresh(arena, pre, spec)
+    module.packed.refresh(arena, pre, spec)
     kv = encoder_kv(arena, pre, spec, out_enc.reshape(-1, D))
     seq = torch.full((B, T), spec.padding_idx, dtype=torch.int64, device=dev)
     seq[:, 0] = spec.start_idx
     probs = torch.zeros((B, steps, C), dtype=F32, device=dev)
     cache = torch.zeros((L, B * T, 3 * D), dtype=BF16, device=dev)     # q | k | v of position t, written at step t
-    emb, pos = arena.w(pre + "trg_word_emb.weight"), module.pos_table
     done = steps
     for s in range(steps):
-        x = ops.dec_embed_fwd(seq[:, s].contiguous().view(B, 1), emb, pos[s:s + 1])              # [B, D] fp32
-        for l in range(L):
-            b = f"{pre}layer_stack.{l}."
-            qkv = cache[l]
-            y, _, _ = ops.ln_fwd(x, arena.w(b + "norm1.weight"), arena.w(b + "norm1.bias"), 1e-5)
-            ops.gemm_nt(y, arena.span(b + "self_attn.linear_q.weight", 3 * D, "wb"), out=qkv.view(B, T, 3 * D)[:, s])
-            att, _, _ = ops.dec_attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, H, T, T, scale, tokens=seq,
-                                         pad_idx=spec.padding_idx, causal=True)                  # row s is the new one
-            x = ops.gemm_nt(att.view(B, T, D)[:, s], arena.wb(b + "self_attn.fc.weight"), epilogue=ops.EPI_RESID, resid=x,
-                            rows_per_sample=1)
-            y, _, _ = ops.ln_fwd(x, arena.w(b + "norm2.weight"), arena.w(b + "norm2.bias"), 1e-5)
-            q2 = ops.gemm_nt(y, arena.wb(b + "enc_attn.linear_q.weight"))
-            att, _, _ = ops.dec_attn_fwd(q2, kv[:, l * 2 * D:l * 2 * D + D], kv[:, l * 2 * D + D:(l + 1) * 2 * D], B, H, 1, 256,
-                                         scale)
-            x = ops.gemm_nt(att, arena.wb(b + "enc_attn.fc.weight"), epilogue=ops.EPI_RESID, resid=x, rows_per_sample=1)
-            y, _, _ = ops.ln_fwd(x, arena.w(b + "norm3.weight"), arena.w(b + "norm3.bias"), 1e-5)
-            _, g3 = ops.gemm_nt(y, arena.wb(b + "mlp.w_1.weight"), epilogue=ops.EPI_GELU, bias=arena.w(b + "mlp.w_1.bias"),
-                                store_u=False)
-            x = ops.gemm_nt(g3, arena.wb(b + "mlp.w_2.weight"), epilogue=ops.EPI_RESID, bias=arena.w(b + "mlp.w_2.bias"),
-                            resid=x, rows_per_sample=1)
-        y, _, _ = ops.ln_fwd(x, arena.w(pre + "layer_norm.weight"), arena.w(pre + "layer_norm.bias"), 1e-6)
-        logits = ops.gemm_nt(y, packed.cls, epilogue=ops.EPI_F32, bias=packed.cls_bias)
+        logits = decoder_position(module, s, seq, cache, kv, B, 1)
         ops.greedy_step(logits, C, probs, s, seq)
         if stop_on_eos_of_first and int(probs[:, s].argmax()) == spec.start_idx:
             done = s + 1
@@ -411,42 +419,19 @@ def beam_decode(module, out_enc, beam_width):
     attention takes them as the W queries of sample b, so the encoder keys and values are never replicated.  Every step ends with the
     selection (ops.nrtr_beam_step) and the permutation of the cached keys and values by the parents (ops.nrtr_beam_reorder).  No length
     normalisation, no early exit: all max_seq_len steps run, nothing is read back."""
-    arena, pre, spec, packed = module.arena, module.arena_prefix, module.dec_spec, module.packed
+    arena, pre, spec = module.arena, module.arena_prefix, module.dec_spec
     B, W = out_enc.shape[0], int(beam_width)
-    D, H, L, C = spec.D, spec.H, spec.L, spec.C
+    D, L, C = spec.D, spec.L, spec.C
     steps, T = spec.max_seq_len, spec.max_seq_len + 1
     dev = out_enc.device
-    scale = 64 ** -0.5
     R = B * W
-    packed.refresh(arena, pre, spec)
+    module.packed.refresh(arena, pre, spec)
     kv = encoder_kv(arena, pre, spec, out_enc.reshape(-1, D))
     seq, score, state, parent = ops.nrtr_beam_state(B, W, T, spec.start_idx, spec.padding_idx, dev)
     cache = torch.zeros((L, R * T, 3 * D), dtype=BF16, device=dev)     # q | k | v of position t of every hypothesis
-    emb, pos = arena.w(pre + "trg_word_emb.weight"), module.pos_table
     out = None
     for s in range(steps):
-        x = ops.dec_embed_fwd(seq[:, s].contiguous().view(R, 1), emb, pos[s:s + 1])              # [R, D] fp32
-        for l in range(L):
-            b = f"{pre}layer_stack.{l}."
-            qkv = cache[l]
-            y, _, _ = ops.ln_fwd(x, arena.w(b + "norm1.weight"), arena.w(b + "norm1.bias"), 1e-5)
-            ops.gemm_nt(y, arena.span(b + "self_attn.linear_q.weight", 3 * D, "wb"), out=qkv.view(R, T, 3 * D)[:, s])
-            att, _, _ = ops.dec_attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], R, H, T, T, scale, tokens=seq,
-                                         pad_idx=spec.padding_idx, causal=True)
-            x = ops.gemm_nt(att.view(R, T, D)[:, s], arena.wb(b + "self_attn.fc.weight"), epilogue=ops.EPI_RESID, resid=x,
-                            rows_per_sample=1)
-            y, _, _ = ops.ln_fwd(x, arena.w(b + "norm2.weight"), arena.w(b + "norm2.bias"), 1e-5)
-            q2 = ops.gemm_nt(y, arena.wb(b + "enc_attn.linear_q.weight"))
-            att, _, _ = ops.dec_attn_fwd(q2, kv[:, l * 2 * D:l * 2 * D + D], kv[:, l * 2 * D + D:(l + 1) * 2 * D], B, H, W, 256,
-                                         scale)                                                  # W queries per sample
-            x = ops.gemm_nt(att, arena.wb(b + "enc_attn.fc.weight"), epilogue=ops.EPI_RESID, resid=x, rows_per_sample=1)
-            y, _, _ = ops.ln_fwd(x, arena.w(b + "norm3.weight"), arena.w(b + "norm3.bias"), 1e-5)
-            _, g3 = ops.gemm_nt(y, arena.wb(b + "mlp.w_1.weight"), epilogue=ops.EPI_GELU, bias=arena.w(b + "mlp.w_1.bias"),
-                                store_u=False)
-            x = ops.gemm_nt(g3, arena.wb(b + "mlp.w_2.weight"), epilogue=ops.EPI_RESID, bias=arena.w(b + "mlp.w_2.bias"),
-                            resid=x, rows_per_sample=1)
-        y, _, _ = ops.ln_fwd(x, arena.w(pre + "layer_norm.weight"), arena.w(pre + "layer_norm.bias"), 1e-6)
-        logits = ops.gemm_nt(y, packed.cls, epilogue=ops.EPI_F32, bias=packed.cls_bias)
+        logits = decoder_position(module, s, seq, cache, kv, R, W)                           # W queries per sample
         out = ops.nrtr_beam_step(logits, C, s, spec.start_idx, spec.padding_idx, seq, score, state, parent, final=s == steps - 1)
         if s + 1 < steps and W > 1:
             ops.nrtr_beam_reorder(cache, parent, T, s)

@@ -88,9 +88,7 @@ class TextAccuracy:
 
     def update(self, gt_text, pt_text):
         """Score one batch of (ground truth, prediction) strings."""
-        if self.case_sensitive:
-            # the reference only defines its normalised strings under `not case_sensitive` (:40-44) and fails otherwise
-            raise NotImplementedError("TextAccuracy is defined for case_sensitive=False (eval_acc.py:40-46)")
+        self._refuse_case_sensitive()
         for gt, pt in zip(gt_text, pt_text):
             gt_n, pt_n = _KEEP.sub("", gt.lower()), _KEEP.sub("", pt.lower())
             if gt_n == pt_n:
@@ -102,29 +100,48 @@ class TextAccuracy:
             self.correct_num_char += sum(1 for j in range(min(len(gt), len(pt))) if gt[j] == pt[j])
             self.total_num_char += len(gt)
 
+    def _refuse_case_sensitive(self):
+        # the reference only defines its normalised strings under `not case_sensitive` (:40-44) and fails otherwise
+        if self.case_sensitive:
+            raise NotImplementedError("TextAccuracy is defined for case_sensitive=False (eval_acc.py:40-46)")
+
+    def _device_tables(self, who, slot, convertor, make, dev):
+        """The convertor's (raw, normalised) tables `make()` on `dev`, uploaded once per (convertor, device) and kept in the
+        attribute `slot` as (convertor, device, raw, normalised), which is returned.  convertor None: the one of the last call."""
+        cached = getattr(self, slot)
+        if convertor is not None and (cached is None or cached[0] is not convertor or cached[1] != dev):
+            tables = make(convertor)
+            if tables is None:
+                raise ValueError(f"{who}: max_seq_len steps of the convertor's longest class exceed ops.TEXT_COLS characters; "
+                                 "score on the host with update()")
+            cached = (convertor, dev) + tuple(_to_device(t, dev) for t in tables)
+            setattr(self, slot, cached)
+        if cached is None:
+            raise ValueError(f"{who}: pass the model's label convertor")
+        return cached
+
+    @staticmethod
+    def _upload_truth(who, gt_text, samples, dev):
+        """The ground-truth strings of a batch of `samples` -> (code points int32 [B, L], lengths int32 [B]) on `dev`."""
+        codes, lens = encode_truth(gt_text)
+        if len(lens) != samples:
+            raise ValueError(f"{who}: {samples} samples but {len(lens)} ground-truth strings")
+        both = _to_device(np.concatenate([codes.ravel(), lens]), dev)         # one host-to-device copy for both
+        return both[:codes.size].view(codes.shape), both[codes.size:]
+
+    def _accumulate(self, records):
+        if self._totals is None:
+            self._totals = ops.text_totals(records.device)
+        ops.text_accumulate(records, self._totals)
+        return records
+
     def update_scores(self, scores, gt_text, convertor=None):
         """Score one batch on the device: decoder scores fp32 [B, T, C] (a strided view is read in place) against the ground-truth
         strings.  Nothing is read back; the totals stay on the device until result().  convertor: the model's AttnConvertor
         (default: the one of the last call)."""
-        if self.case_sensitive:
-            raise NotImplementedError("TextAccuracy is defined for case_sensitive=False (eval_acc.py:40-46)")
-        dev = scores.device
-        if convertor is not None and (self._tables is None or self._tables[0] is not convertor or self._tables[1] != dev):
-            tables = convertor.score_table()
-            if tables is None:
-                raise ValueError("update_scores: max_seq_len steps of the convertor's longest class exceed ops.TEXT_COLS characters; "
-                                 "score on the host with update()")
-            self._tables = (convertor, dev) + tuple(_to_device(t, dev) for t in tables)
-        if self._tables is None:
-            raise ValueError("update_scores: pass the model's label convertor")
-        conv, _, raw, norm = self._tables
-        if self._totals is None:
-            self._totals = ops.text_totals(dev)
-        codes, lens = encode_truth(gt_text)
-        if len(lens) != scores.shape[0]:
-            raise ValueError(f"update_scores: {scores.shape[0]} samples but {len(lens)} ground-truth strings")
-        both = _to_device(np.concatenate([codes.ravel(), lens]), dev)         # one host-to-device copy for both
-        gt, gt_len = both[:codes.size].view(codes.shape), both[codes.size:]
+        self._refuse_case_sensitive()
+        conv, _, raw, norm = self._device_tables("update_scores", "_tables", convertor, lambda c: c.score_table(), scores.device)
+        gt, gt_len = self._upload_truth("update_scores", gt_text, scores.shape[0], scores.device)
         if is_ctc(conv) and conv.beam_width > 0:                              # prefix beam search on the probabilities, rank 0 scored
             paths, _, _ = ops.ctc_beam_search(scores, conv.beam_width, normalized=True)
             records = ops.text_score_paths(paths[:, 0], raw, norm, gt, gt_len)
@@ -132,32 +149,16 @@ class TextAccuracy:
             records = ops.text_score_ctc(scores, raw, norm, gt, gt_len)
         else:
             records = ops.text_score(scores, raw, norm, conv.end_idx, conv.padding_idx, gt, gt_len)
-        ops.text_accumulate(records, self._totals)
-        return records
+        return self._accumulate(records)
 
     def update_paths(self, paths, gt_text, convertor):
         """Score one batch of decoded words on the device: paths int32 [B, T] (any row stride: rank 0 of forward_beam's paths), the
         classes of an AttnConvertor, -1-padded.  Records and totals as update_scores; nothing is read back."""
-        if self.case_sensitive:
-            raise NotImplementedError("TextAccuracy is defined for case_sensitive=False (eval_acc.py:40-46)")
-        dev = paths.device
-        if self._path_tables is None or self._path_tables[0] is not convertor or self._path_tables[1] != dev:
-            tables = convertor.path_score_table()
-            if tables is None:
-                raise ValueError("update_paths: max_seq_len steps of the convertor's longest class exceed ops.TEXT_COLS characters; "
-                                 "score on the host with update()")
-            self._path_tables = (convertor, dev) + tuple(_to_device(t, dev) for t in tables)
-        _, _, raw, norm = self._path_tables
-        if self._totals is None:
-            self._totals = ops.text_totals(dev)
-        codes, lens = encode_truth(gt_text)
-        if len(lens) != paths.shape[0]:
-            raise ValueError(f"update_paths: {paths.shape[0]} samples but {len(lens)} ground-truth strings")
-        both = _to_device(np.concatenate([codes.ravel(), lens]), dev)
-        gt, gt_len = both[:codes.size].view(codes.shape), both[codes.size:]
-        records = ops.text_score_paths(paths + 1, raw, norm, gt, gt_len)      # class c in row c + 1; the -1 padding counts nothing
-        ops.text_accumulate(records, self._totals)
-        return records
+        self._refuse_case_sensitive()
+        _, _, raw, norm = self._device_tables("update_paths", "_path_tables", convertor, lambda c: c.path_score_table(), paths.device)
+        gt, gt_len = self._upload_truth("update_paths", gt_text, paths.shape[0], paths.device)
+        # class c in row c + 1; the -1 padding counts nothing
+        return self._accumulate(ops.text_score_paths(paths + 1, raw, norm, gt, gt_len))
 
     def result(self):
         cc, tc, cw, words, ed, ned = self.correct_num_char, self.total_num_char, self.correct_num_word, self.total_num_word, \
@@ -194,17 +195,13 @@ class TextAccuracy:
             image_tensors = image_tensors.to(device)
             start = time.time()
             if attn_beam:
-                beam = net.forward_beam(image_tensors, convertor.beam_width)
-                label_indexes = [words[0] if words else [] for words in convertor.paths2nbest(*beam)[0]]
-                self.inference_time += time.time() - start
-                self.update(list(label_tensors[0]), convertor.idx2str(label_indexes))
-                continue
-            out_dec = model(image_tensors, text=None, return_loss=False, test_speed=False)
-            if is_ctc(convertor) and convertor.beam_width > 0:                # the best word of the beam (the kernel, on any device)
-                label_indexes = [words[0] if words else [] for words in convertor.tensor2nbest(out_dec, nbest=1)[0]]
+                nbest = convertor.paths2nbest(*net.forward_beam(image_tensors, convertor.beam_width))[0]
             else:
-                label_indexes, _scores = net.label_convertor.tensor2idx(out_dec)
-            pt_text = net.label_convertor.idx2str(label_indexes)
+                out_dec = model(image_tensors, text=None, return_loss=False, test_speed=False)
+                # a CTC beam: the best word of the beam (the kernel, on any device)
+                nbest = convertor.tensor2nbest(out_dec, nbest=1)[0] if is_ctc(convertor) and convertor.beam_width > 0 else None
+            label_indexes = convertor.tensor2idx(out_dec)[0] if nbest is None else [words[0] if words else [] for words in nbest]
+            pt_text = convertor.idx2str(label_indexes)
             self.inference_time += time.time() - start
             self.update(list(label_tensors[0]), pt_text)
         return self.result()

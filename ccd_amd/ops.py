@@ -768,24 +768,36 @@ TEXT_RECORD = ("distance", "equal_chars", "gt_chars", "word_correct")          #
 TEXT_TOTALS = ("correct_char", "total_char", "correct_word", "words", "total_ed", "total_ned")     # int64 x 5, then fp64 bits
 
 
+def _text_score(who, x, layout, inner, table_raw, table_norm, gt_codes, gt_len, extra=()):
+    """What the text_score* wrappers share: the checks, the records and the call of ccd_<who>.  x: the decoder's output, laid out as
+    `layout` says - scores whose last axis C is the rows a table needs at least, or decoded paths, where the entry point is told
+    how many rows the tables have; inner: what the last axis holds where it must be contiguous; extra: the entry point's arguments
+    between the tables and the truth."""
+    if x.dim() != layout.count(",") + 1 or gt_codes.dim() != 2 or gt_codes.shape[0] != x.shape[0] or tuple(gt_len.shape) != (x.shape[0],):
+        raise ValueError(f"{who}: expects {layout}, gt [B, L] and gt_len [B], got {list(x.shape)}, {list(gt_codes.shape)}, "
+                         f"{list(gt_len.shape)}")
+    if inner and x.shape[-1] > 1 and x.stride(-1) != 1:
+        raise ValueError(f"{who}: the {inner} must be contiguous")
+    decoded = x.dim() == 2
+    rows = "classes" if decoded else f">= {x.shape[2]}"
+    for name, t in (("table_raw", table_raw), ("table_norm", table_norm)):
+        if t.dim() != 2 or not t.is_contiguous() or (t.shape[0] != table_raw.shape[0] if decoded else t.shape[0] < x.shape[2]):
+            raise ValueError(f"{who}: {name} must be a contiguous [{rows}, width] table, got {list(t.shape)}")
+    assert gt_len.is_contiguous()
+    records = torch.empty((x.shape[0], len(TEXT_RECORD)), dtype=I32, device=x.device)
+    if x.shape[0]:
+        _call("ccd_" + who, x, *x.stride()[:-1], *x.shape, *((table_raw.shape[0],) if decoded else ()), table_raw,
+              table_raw.shape[1], table_norm, table_norm.shape[1], *extra, gt_codes if gt_codes.shape[1] else None, gt_codes.stride(0),
+              gt_codes.shape[1], gt_len, records)
+    return records
+
+
 def text_score(scores, table_raw, table_norm, end_idx, pad_idx, gt_codes, gt_len):
     """Decoder scores fp32 [B, T, C] (any sample / step stride, e.g. probs[:, :done]) against the ground truth as int32 code points
     [B, L] with lengths int32 [B] -> records int32 [B, 4] in the order of TEXT_RECORD.  table_raw / table_norm: int32 [C, width], the
     code points of every class and of its normalised form, rows padded with -1 (AttnConvertor.score_table)."""
-    if scores.dim() != 3 or gt_codes.dim() != 2 or gt_codes.shape[0] != scores.shape[0] or tuple(gt_len.shape) != (scores.shape[0],):
-        raise ValueError(f"text_score: expects scores [B, T, C], gt [B, L] and gt_len [B], got {list(scores.shape)}, {list(gt_codes.shape)}, "
-                         f"{list(gt_len.shape)}")
-    B, T, C = scores.shape
-    for name, t in (("table_raw", table_raw), ("table_norm", table_norm)):
-        if t.dim() != 2 or t.shape[0] < C or not t.is_contiguous():      # (the decoder has no <PAD> output: one row more than C)
-            raise ValueError(f"text_score: {name} must be a contiguous [>= {C}, width] table, got {list(t.shape)}")
-    assert gt_len.is_contiguous()
-    records = torch.empty((B, len(TEXT_RECORD)), dtype=I32, device=scores.device)
-    if B:
-        _call("ccd_text_score", scores, scores.stride(0), scores.stride(1), B, T, C, table_raw, table_raw.shape[1], table_norm,
-              table_norm.shape[1], int(end_idx), int(pad_idx), gt_codes if gt_codes.shape[1] else None, gt_codes.stride(0),
-              gt_codes.shape[1], gt_len, records)
-    return records
+    return _text_score("text_score", scores, "scores [B, T, C]", None, table_raw, table_norm, gt_codes, gt_len,
+                       (int(end_idx), int(pad_idx)))      # (the decoder has no <PAD> output: the tables hold one row more than C)
 
 
 def text_totals(device):
@@ -804,42 +816,14 @@ def text_accumulate(records, totals):
 def text_score_ctc(logits, table_raw, table_norm, gt_codes, gt_len):
     """text_score for the logits fp32 [B, T, C] of a CTC head (any sample / step stride): a frame counts where its arg-max class is
     not the blank (class 0) and differs from the frame before.  Tables as CTCConvertor.score_table gives them; records as text_score."""
-    if logits.dim() != 3 or gt_codes.dim() != 2 or gt_codes.shape[0] != logits.shape[0] or tuple(gt_len.shape) != (logits.shape[0],):
-        raise ValueError(f"text_score_ctc: expects logits [B, T, C], gt [B, L] and gt_len [B], got {list(logits.shape)}, "
-                         f"{list(gt_codes.shape)}, {list(gt_len.shape)}")
-    if logits.shape[2] > 1 and logits.stride(2) != 1:
-        raise ValueError("text_score_ctc: the classes of a frame must be contiguous")
-    B, T, C = logits.shape
-    for name, t in (("table_raw", table_raw), ("table_norm", table_norm)):
-        if t.dim() != 2 or t.shape[0] < C or not t.is_contiguous():
-            raise ValueError(f"text_score_ctc: {name} must be a contiguous [>= {C}, width] table, got {list(t.shape)}")
-    assert gt_len.is_contiguous()
-    records = torch.empty((B, len(TEXT_RECORD)), dtype=I32, device=logits.device)
-    if B:
-        _call("ccd_text_score_ctc", logits, logits.stride(0), logits.stride(1), B, T, C, table_raw, table_raw.shape[1], table_norm,
-              table_norm.shape[1], gt_codes if gt_codes.shape[1] else None, gt_codes.stride(0), gt_codes.shape[1], gt_len, records)
-    return records
+    return _text_score("text_score_ctc", logits, "logits [B, T, C]", "classes of a frame", table_raw, table_norm, gt_codes, gt_len)
 
 
 def text_score_paths(paths, table_raw, table_norm, gt_codes, gt_len):
     """text_score for classes that are already decoded: paths int32 [B, T] (any row stride, e.g. rank 0 of ctc_beam_search's
     paths[:, 0]), a sample's classes in front of its first negative entry.  Tables as CTCConvertor.score_table gives them; records as
     text_score."""
-    if paths.dim() != 2 or gt_codes.dim() != 2 or gt_codes.shape[0] != paths.shape[0] or tuple(gt_len.shape) != (paths.shape[0],):
-        raise ValueError(f"text_score_paths: expects paths [B, T], gt [B, L] and gt_len [B], got {list(paths.shape)}, "
-                         f"{list(gt_codes.shape)}, {list(gt_len.shape)}")
-    if paths.shape[1] > 1 and paths.stride(1) != 1:
-        raise ValueError("text_score_paths: the steps of a path must be contiguous")
-    B, T = paths.shape
-    for name, t in (("table_raw", table_raw), ("table_norm", table_norm)):
-        if t.dim() != 2 or t.shape[0] != table_raw.shape[0] or not t.is_contiguous():
-            raise ValueError(f"text_score_paths: {name} must be a contiguous [classes, width] table, got {list(t.shape)}")
-    assert gt_len.is_contiguous()
-    records = torch.empty((B, len(TEXT_RECORD)), dtype=I32, device=paths.device)
-    if B:
-        _call("ccd_text_score_paths", paths, paths.stride(0), B, T, table_raw.shape[0], table_raw, table_raw.shape[1], table_norm,
-              table_norm.shape[1], gt_codes if gt_codes.shape[1] else None, gt_codes.stride(0), gt_codes.shape[1], gt_len, records)
-    return records
+    return _text_score("text_score_paths", paths, "paths [B, T]", "steps of a path", table_raw, table_norm, gt_codes, gt_len)
 
 
 # ------------------------------------------------------------------------------------------ CTC recognition head (kernels/ctc.h)

@@ -12,15 +12,14 @@ tot_i = logaddexp(pb_i, pnb_i):
     merge:           an extend candidate that spells the prefix of a live entry j is log-added into the pnb' of j's stay candidate and
                      disappears (prefixes are unique: j absorbs at most one, and no two extend candidates coincide);
     select:          the W best candidates of finite score logaddexp(pb', pnb') by (score descending, k = rank * C + class ascending).
-The gap returned is the smallest difference of neighbouring scores among the W + 1 best candidates of any frame: where it is far above
-the rounding error of an implementation (callers assert >= 1e-9), that implementation must reproduce the selection and its order
-exactly.  `ties=True` leaves exact ties (bit-identical scores, ordered by k) out of the gap."""
+The gap returned is the smallest one of any frame's selection (beam_np.select; callers assert >= MIN_GAP)."""
 import itertools
 
 import numpy as np
 
+from beam_np import MIN_GAP, log_softmax64, select      # noqa: F401  (MIN_GAP: for the callers)
+
 NEG = -np.inf
-MIN_GAP = 1e-9
 
 
 def _lae(a, b):
@@ -31,25 +30,18 @@ def _lae(a, b):
 
 
 def log_probs(x, normalized):
-    """x fp32 [T, C]: logits (normalized False: x - max - log sum exp(x - max)) or probabilities (True: log p - log sum p), computed in
-    fp64 from the fp32 values, the sum over the classes in ascending order.  A -inf logit / a zero probability gives -inf."""
+    """x fp32 [T, C]: logits (normalized False: beam_np.log_softmax64 of every frame) or probabilities (True: log p - log sum p,
+    computed in fp64 from the fp32 values, the sum over the classes in ascending order; a zero probability gives -inf)."""
     x = np.asarray(x, dtype=np.float32)
+    if not normalized:
+        return np.stack([log_softmax64(frame) for frame in x])
     x64 = x.astype(np.float64)
     out = np.full(x.shape, NEG)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        for t in range(x.shape[0]):
-            if normalized:
-                live = x[t] > 0
-                terms = np.where(live, x64[t], 0.0)
-                num = np.log(np.where(live, x64[t], 1.0))
-            else:
-                live = x[t] > NEG
-                m = np.float64(x[t].max())
-                num = np.where(live, x64[t] - m, 0.0)
-                terms = np.where(live, np.exp(num), 0.0)
-            total = np.cumsum(terms)[-1]                                       # ascending class order
-            if live.any():
-                out[t, live] = num[live] - np.log(total)
+    for t in range(x.shape[0]):
+        live = x[t] > 0
+        total = np.cumsum(np.where(live, x64[t], 0.0))[-1]                     # ascending class order
+        if live.any():
+            out[t, live] = np.log(x64[t, live]) - np.log(total)
     return out
 
 
@@ -79,19 +71,13 @@ def beam_search(x, W, normalized=False, ties=False):
                 score[i, p[-1]] = NEG
         for i in range(n):
             score[i, 0] = _lae(stay_pb[i], stay_pnb[i])
-        flat = score.ravel()
-        order = np.argsort(-flat, kind="stable")                              # score descending, k ascending among equals
-        order = order[flat[order] > NEG]
-        near = -np.diff(flat[order[:W + 1]])
-        if ties:
-            near = near[near > 0]
-        if near.size:
-            gap = min(gap, float(near.min()))
+        best, near = select(score, W, ties)
+        gap = min(gap, near)
         nxt = []
-        for k in order[:W]:
+        for k in best:
             i, c = divmod(int(k), C)
             p = entries[i][0]
-            nxt.append((p, stay_pb[i], stay_pnb[i]) if c == 0 else (p + (c,), NEG, float(flat[k])))
+            nxt.append((p, stay_pb[i], stay_pnb[i]) if c == 0 else (p + (c,), NEG, float(score[i, c])))
         entries = nxt
     return [(p, _lae(pb, pnb)) for p, pb, pnb in entries], gap
 

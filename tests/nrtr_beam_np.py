@@ -13,28 +13,14 @@ The rules ("Beam search over the NRTR decoder"):
   * after T steps: paths = the classes in front of the first end_idx, lengths (T if never finished, -1 unused), scores (-inf unused).
 
 `gap` is the oracle's own smallest distance between two neighbouring candidates of which at least one was kept (kept against
-dropped decides the set, kept against kept the ranks): a case is only compared where it is >= MIN_GAP, nine orders above the
-rounding of the fp64 arithmetic.  With ties=True a distance of exactly 0 (bit-identical candidates, decided by the flat index)
-does not count."""
+dropped decides the set, kept against kept the ranks; beam_np.select): a case is only compared where it is >= MIN_GAP."""
 import itertools
 
 import numpy as np
 
-MIN_GAP = 1e-9
+from beam_np import MIN_GAP, log_softmax64, select      # noqa: F401  (MIN_GAP: for the callers)
+
 UNUSED, LIVE, FINISHED = 0, 1, 2
-
-
-def log_softmax64(row):
-    x = np.asarray(row, dtype=np.float32).astype(np.float64)
-    m = x.max()
-    if m == -np.inf:
-        return np.full(x.shape, -np.inf)
-    e = np.exp(x - m)
-    total = 0.0
-    for v in e:                                                  # ascending class order, as the kernel adds
-        total += v
-    with np.errstate(divide="ignore"):
-        return (x - m) - np.log(total)
 
 
 class Sample:
@@ -50,26 +36,20 @@ class Sample:
     def step(self, logits, end_idx, pad_idx, ties=False):
         """logits [W, C] fp32 (rows of slots that are not live are not read) -> (parent [W], gap)."""
         W, C = self.W, logits.shape[1]
-        cands = []                                               # (score, flat index k, r, c)
+        cand = np.full((W, C), -np.inf)                          # candidate (r, c) at k = r * C + c
         for r in range(W):
             if self.state[r] == LIVE:
-                lp = log_softmax64(logits[r])
-                cands += [(self.score[r] + lp[c], r * C + c, r, c) for c in range(C) if lp[c] > -np.inf and self.score[r] + lp[c] > -np.inf]
+                cand[r] = self.score[r] + log_softmax64(logits[r])
             elif self.state[r] == FINISHED:
-                cands.append((self.score[r], r * C + end_idx, r, end_idx))
-        cands.sort(key=lambda t: (-t[0], t[1]))
-        gap = np.inf
-        for a, b in zip(cands[:W], cands[1:W + 1]):
-            d = a[0] - b[0]
-            if not (ties and d == 0.0):
-                gap = min(gap, d)
+                cand[r, end_idx] = self.score[r]
+        best, gap = select(cand, W, ties)
         seqs, score, state, parent = [], np.full(W, -np.inf), [UNUSED] * W, [-1] * W
         for n in range(W):
-            if n < len(cands):
-                sc, _, r, c = cands[n]
+            if n < len(best):
+                r, c = divmod(int(best[n]), C)
                 done = self.state[r] == FINISHED
                 seqs.append(self.seqs[r] + [pad_idx if done else c])
-                score[n], parent[n] = sc, r
+                score[n], parent[n] = cand[r, c], r
                 state[n] = FINISHED if done or c == end_idx else LIVE
             else:
                 seqs.append(self.seqs[n] + [pad_idx])            # an unused slot keeps its row and takes the padding token
