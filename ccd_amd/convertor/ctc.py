@@ -9,6 +9,12 @@ AttnConvertor's so that DINO_Finetune, TextAccuracy, train_finetune.py and test.
 `beam_width` > 0 asks for CTC prefix beam search (ops.ctc_beam_search) where words are scored (TextAccuracy) and in `tensor2nbest`,
 which returns an n-best list with the log-probability of each word summed over its alignments; 0, the default, is the greedy rule
 everywhere, and `tensor2idx` is the greedy rule whatever the width.
+
+A `lexicon` (a list of words, or the path of a UTF-8 file with one word per line) asks for lexicon-constrained decoding instead: where
+words are scored (TextAccuracy) and in `tensor2lexicon` the answer is the most probable word OF THE LEXICON, with the exact log of its
+probability summed over all alignments (ops.ctc_lexicon_score / ops.ctc_lexicon_best).  The words are encoded as targets are (`lower`,
+`<UKN>`); words of more than 31 classes and duplicates after encoding are dropped and counted in `lexicon_stats`.  A lexicon and a
+beam exclude each other.
 """
 from __future__ import annotations
 
@@ -25,12 +31,13 @@ def is_ctc(convertor):
 
 
 class CTCConvertor:
-    """CTCConvertor(dict_type='DICT90', with_unknown=True, max_seq_len=25, lower=False, beam_width=0) - see the module docstring."""
+    """CTCConvertor(dict_type='DICT90', with_unknown=True, max_seq_len=25, lower=False, beam_width=0, lexicon=None) - see the module
+    docstring."""
 
     dicts = {name: tuple(chars) for name, chars in ALPHABETS.items()}
 
     def __init__(self, dict_type="DICT90", dict_file=None, dict_list=None, with_unknown=True, max_seq_len=25, lower=False, beam_width=0,
-                 **_ignored):
+                 lexicon=None, **_ignored):
         if dict_file is not None:
             alphabet = _read_alphabet_file(dict_file)
         elif dict_list is not None:
@@ -56,6 +63,46 @@ class CTCConvertor:
         for cls, c in enumerate(alphabet, start=1):
             if len(c) == 1:
                 self._lut[ord(c)] = cls
+        self.lexicon, self.lexicon_words, self.lexicon_stats = None, None, None
+        if lexicon is not None:
+            self.set_lexicon(lexicon)
+
+    def set_lexicon(self, strings_or_path):
+        """The closed vocabulary of tensor2lexicon and TextAccuracy: a list of words, or the path of a UTF-8 file with one word per line
+        (empty lines skipped); None removes it.  Kept: `lexicon` (the ops.ctc_lexicon handle), `lexicon_words` (the kept strings, in
+        order: column v of the scores is lexicon_words[v]) and `lexicon_stats` = {'read', 'kept', 'too_long', 'duplicates'}."""
+        from .. import ops
+        if strings_or_path is None:
+            self.lexicon, self.lexicon_words, self.lexicon_stats = None, None, None
+            return None
+        if self.beam_width > 0:
+            raise ValueError(f"a lexicon and beam_width = {self.beam_width} exclude each other: lexicon decoding scores every word of "
+                             "the lexicon exactly, set beam_width to 0")
+        if isinstance(strings_or_path, (str, bytes)) or hasattr(strings_or_path, "__fspath__"):
+            with open(strings_or_path, encoding="utf-8") as f:
+                strings = [line.rstrip("\r\n") for line in f]
+            strings = [w for w in strings if w]
+        else:
+            strings = list(strings_or_path)
+            if not all(isinstance(w, str) for w in strings):
+                raise TypeError("set_lexicon expects a list of strings or the path of a word list")
+        kept, rows, seen, too_long, duplicates = [], [], set(), 0, 0
+        for word, cls in zip(strings, self.str2idx(strings)):
+            if len(cls) > ops.CTC_MAX_LABELS:
+                too_long += 1
+            elif tuple(cls) in seen:
+                duplicates += 1
+            else:
+                seen.add(tuple(cls))
+                kept.append(word)
+                rows.append(cls)
+        words = np.zeros((len(rows), max(1, max(map(len, rows), default=1))), dtype=np.int64)
+        for row, cls in zip(words, rows):
+            row[:len(cls)] = cls
+        self.lexicon = ops.ctc_lexicon(torch.from_numpy(words))
+        self.lexicon_words = kept
+        self.lexicon_stats = {"read": len(strings), "kept": len(kept), "too_long": too_long, "duplicates": duplicates}
+        return self.lexicon_stats
 
     def num_classes(self):
         return len(self.idx2char)
@@ -139,3 +186,26 @@ class CTCConvertor:
         if width < 1:
             raise ValueError("tensor2nbest: needs a beam_width >= 1 (the convertor's is 0: greedy decoding)")
         return nbest_lists("tensor2nbest", *ops.ctc_beam_search(outputs.float(), width, normalized=normalized), nbest)
+
+    @torch.no_grad()
+    def tensor2lexicon(self, outputs, nbest=1, normalized=True, subset=None):
+        """[N, T, C] frame scores on the device - probabilities (normalized=True: what CTCDecoder.forward_test returns) or logits
+        -> (indexes, log_probs, word_ids): the `nbest` most probable words of the lexicon, best first.  indexes[i] holds up to `nbest`
+        index lists (fewer where fewer words have an alignment of finite probability); log_probs is a float tensor [N, nbest], the
+        exact log of each word's probability summed over all alignments, -inf where a slot is empty; word_ids is an int64 tensor
+        [N, nbest] of positions in `lexicon_words`, -1 where a slot is empty.  subset int32 [N, K] on the device restricts sample i
+        to the words subset[i] (negative entries are padding)."""
+        from .. import ops
+        if self.lexicon is None:
+            raise ValueError("tensor2lexicon: the convertor has no lexicon (set_lexicon)")
+        scores = ops.ctc_lexicon_score(outputs.float(), self.lexicon, normalized=normalized, subset=subset)
+        if not 1 <= int(nbest) <= ops.CTC_LEXICON_MAX_NBEST:
+            raise ValueError(f"tensor2lexicon: nbest must lie in 1..{ops.CTC_LEXICON_MAX_NBEST}, got {nbest}")
+        index, best = ops.ctc_lexicon_best(scores, nbest)
+        ids = index.long()
+        if subset is not None and subset.shape[1]:
+            ids = torch.where(ids >= 0, subset.long().gather(1, ids.clamp(min=0)), ids)
+        ids = ids.cpu()
+        words, lengths = self.lexicon.words, self.lexicon.lengths
+        indexes = [[words[v, :lengths[v]].tolist() for v in row if v >= 0] for row in ids.tolist()]
+        return indexes, best.cpu(), ids

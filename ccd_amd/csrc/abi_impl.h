@@ -26,6 +26,7 @@
 #include "kernels/ctc.h"
 #include "kernels/ctc_beam.h"
 #include "kernels/nrtr_beam.h"
+#include "kernels/ctc_lexicon.h"
 #include "kernels/datapipe.h"
 #include "kernels/embed.h"
 #include "kernels/head.h"
@@ -340,7 +341,7 @@ static int ccd_seg_prepare(int images, long pixels, int* cm, int* status, int* c
 
 extern "C" {
 
-int ccd_abi_version(void) { return 22; }   // 22: ccd_nrtr_beam_step, ccd_nrtr_beam_reorder (beam search over the NRTR decoder); 21: ccd_ctc_beam_search, ccd_text_score_paths (CTC prefix beam search, n-best word scores); 20: ccd_ctc_pool_fwd / _bwd, ccd_ctc_loss_fwd / _bwd, ccd_ctc_greedy, ccd_text_score_ctc (the CTC recognition head); 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
+int ccd_abi_version(void) { return 23; }   // 23: ccd_ctc_lexicon_score, ccd_ctc_lexicon_best (lexicon-constrained decoding of the CTC head); 22: ccd_nrtr_beam_step, ccd_nrtr_beam_reorder (beam search over the NRTR decoder); 21: ccd_ctc_beam_search, ccd_text_score_paths (CTC prefix beam search, n-best word scores); 20: ccd_ctc_pool_fwd / _bwd, ccd_ctc_loss_fwd / _bwd, ccd_ctc_greedy, ccd_text_score_ctc (the CTC recognition head); 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
 const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi16"; }
 int ccd_policy_set(const char* key, int value) {
     CCD_CHECK(key, CCD_EINVAL);
@@ -1350,7 +1351,7 @@ int ccd_text_accumulate(const int* records, int batch, long* totals, double* tot
 
 // ------------------------------------------------------------------------------- CTC recognition head (kernels/ctc.h)
 static_assert(CCD_CTC_MAX_STEPS == ccd::CTC_MAX_T && CCD_CTC_MAX_CLASSES == ccd::CTC_MAX_C && CCD_CTC_MAX_LABELS == ccd::CTC_MAX_L &&
-              CCD_CTC_MAX_BEAM == ccd::CTC_MAX_BEAM, "");
+              CCD_CTC_MAX_BEAM == ccd::CTC_MAX_BEAM && CCD_CTC_LEXICON_MAX_NBEST == ccd::CTC_LEX_MAX_NBEST, "");
 static int ccd_ctc_pool_launch(bool bwd, const ccd_bf16* src, ccd_bf16* dst, int images, int rows, int cols, int E, void* stream) {
     CCD_CHECK(images >= 0 && rows >= 0 && cols >= 0 && E >= 0, CCD_EINVAL);
     if (images == 0) return CCD_OK;
@@ -1424,6 +1425,41 @@ int ccd_ctc_beam_search(const float* scores, long sample_stride, long step_strid
     CCD_CHECK(scores && paths && lengths && hyp_scores, CCD_EINVAL);
     CCD_LAUNCH(ccd::ctc_beam_kernel, dim3((unsigned)((batch + ccd::CTC_WAVES - 1) / ccd::CTC_WAVES)), dim3(ccd::CTC_THREADS), 0, stream,
                scores, sample_stride, step_stride, batch, steps, classes, normalized, beam, paths, lengths, hyp_scores);
+    return ccd_rt_last_error();
+}
+
+int ccd_ctc_lexicon_score(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
+                          const int64_t* words, int n_words, int max_len, const int* columns, const int* subset, int subset_cols,
+                          float* out, long ld_out, void* stream) {
+    CCD_CHECK(batch >= 0 && sample_stride >= 0 && step_stride >= 0 && n_words >= 0 && max_len >= 0 && subset_cols >= 0 && ld_out >= 0,
+              CCD_EINVAL);
+    CCD_CHECK(!(columns && subset), CCD_EINVAL);
+    const int cols = subset ? subset_cols : n_words;
+    CCD_CHECK(steps >= 1 && steps <= ccd::CTC_MAX_T && classes >= 2 && classes <= ccd::CTC_MAX_C && max_len >= 1 &&
+              max_len <= ccd::CTC_MAX_L && (normalized == 0 || normalized == 1) && (columns || ld_out >= cols), CCD_ESHAPE);
+    if (batch == 0 || n_words == 0 || cols == 0) return CCD_OK;
+    CCD_CHECK(scores && words && out, CCD_EINVAL);
+    const dim3 grid((unsigned)((cols + ccd::CTC_LEX_STRIP - 1) / ccd::CTC_LEX_STRIP), (unsigned)(batch < 65535 ? batch : 65535));
+    const size_t smem = (size_t)steps * classes * sizeof(ccd::ctc_real);
+    const long* const w = reinterpret_cast<const long*>(words);
+    if (2 * max_len + 1 <= 16)
+        CCD_LAUNCH(ccd::ctc_lexicon_score_kernel<16>, grid, dim3(ccd::CTC_THREADS), smem, stream, scores, sample_stride, step_stride, batch,
+                   steps, classes, normalized, w, n_words, max_len, columns, subset, cols, out, ld_out);
+    else if (2 * max_len + 1 <= 32)
+        CCD_LAUNCH(ccd::ctc_lexicon_score_kernel<32>, grid, dim3(ccd::CTC_THREADS), smem, stream, scores, sample_stride, step_stride, batch,
+                   steps, classes, normalized, w, n_words, max_len, columns, subset, cols, out, ld_out);
+    else
+        CCD_LAUNCH(ccd::ctc_lexicon_score_kernel<64>, grid, dim3(ccd::CTC_THREADS), smem, stream, scores, sample_stride, step_stride, batch,
+                   steps, classes, normalized, w, n_words, max_len, columns, subset, cols, out, ld_out);
+    return ccd_rt_last_error();
+}
+int ccd_ctc_lexicon_best(const float* word_scores, long ld, int batch, int cols, int nbest, int* index, float* best, void* stream) {
+    CCD_CHECK(batch >= 0 && ld >= 0 && cols >= 0, CCD_EINVAL);
+    CCD_CHECK(nbest >= 1 && nbest <= ccd::CTC_LEX_MAX_NBEST && ld >= cols, CCD_ESHAPE);
+    if (batch == 0) return CCD_OK;
+    CCD_CHECK((word_scores || cols == 0) && index && best, CCD_EINVAL);
+    CCD_LAUNCH(ccd::ctc_lexicon_best_kernel, dim3((unsigned)((batch + ccd::CTC_WAVES - 1) / ccd::CTC_WAVES)), dim3(ccd::CTC_THREADS), 0, stream,
+               word_scores, ld, batch, cols, nbest, index, best);
     return ccd_rt_last_error();
 }
 

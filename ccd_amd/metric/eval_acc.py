@@ -19,7 +19,9 @@ first maximum of the scores themselves where `tensor2idx` takes the maximum of t
 classes of a step are closer than the softmax resolves.  With a CTCConvertor the same path decodes by the greedy CTC rule
 (ops.text_score_ctc: repeats collapsed, blanks dropped); everything behind the decode step is shared.  A CTCConvertor with
 `beam_width` > 0 decodes by CTC prefix beam search instead (ops.ctc_beam_search on the head's probabilities) and scores the best
-word (ops.text_score_paths): three launches per batch, still no host synchronisation.  An AttnConvertor with `beam_width` > 0
+word (ops.text_score_paths): three launches per batch, still no host synchronisation.  A CTCConvertor with a lexicon scores the most
+probable word OF THE LEXICON instead: ops.ctc_lexicon_score on the probabilities, ops.ctc_lexicon_best, a gather of the winning rows of
+the word list into -1-padded paths, ops.text_score_paths - no host synchronisation either (host path: `tensor2lexicon`).  An AttnConvertor with `beam_width` > 0
 makes `compute` decode by beam search over the NRTR decoder (`DINO_Finetune.forward_beam`) and score the best word the same way
 (`update_paths`; on the host path: `idx2str` of `paths2nbest`); `forward_test` itself stays greedy.
 """
@@ -142,7 +144,9 @@ class TextAccuracy:
         self._refuse_case_sensitive()
         conv, _, raw, norm = self._device_tables("update_scores", "_tables", convertor, lambda c: c.score_table(), scores.device)
         gt, gt_len = self._upload_truth("update_scores", gt_text, scores.shape[0], scores.device)
-        if is_ctc(conv) and conv.beam_width > 0:                              # prefix beam search on the probabilities, rank 0 scored
+        if is_ctc(conv) and conv.lexicon is not None:                         # the most probable word of the lexicon
+            records = ops.text_score_paths(self._lexicon_paths(conv, scores), raw, norm, gt, gt_len)
+        elif is_ctc(conv) and conv.beam_width > 0:                            # prefix beam search on the probabilities, rank 0 scored
             paths, _, _ = ops.ctc_beam_search(scores, conv.beam_width, normalized=True)
             records = ops.text_score_paths(paths[:, 0], raw, norm, gt, gt_len)
         elif is_ctc(conv):                                                    # CTCConvertor: frames, not decoding steps
@@ -150,6 +154,19 @@ class TextAccuracy:
         else:
             records = ops.text_score(scores, raw, norm, conv.end_idx, conv.padding_idx, gt, gt_len)
         return self._accumulate(records)
+
+    @staticmethod
+    def _lexicon_paths(conv, scores):
+        """The best lexicon word of every sample as -1-padded int32 paths [B, max_len] (all -1 where no word has an alignment of finite
+        probability): two launches and plain indexing, nothing is read back."""
+        index, _ = ops.ctc_lexicon_best(ops.ctc_lexicon_score(scores, conv.lexicon, normalized=True), 1)
+        words = conv.lexicon.on(scores.device)[0]
+        if not words.shape[0]:
+            return torch.full((scores.shape[0], 1), -1, dtype=torch.int32, device=scores.device)
+        best = index[:, 0].long()
+        rows = words[best.clamp(min=0)]
+        ended = (rows == 0).cumsum(dim=1) > 0                                 # behind the word's first zero
+        return torch.where(ended | (best < 0)[:, None], -1, rows).to(torch.int32)
 
     def update_paths(self, paths, gt_text, convertor):
         """Score one batch of decoded words on the device: paths int32 [B, T] (any row stride: rank 0 of forward_beam's paths), the
@@ -200,6 +217,8 @@ class TextAccuracy:
                 out_dec = model(image_tensors, text=None, return_loss=False, test_speed=False)
                 # a CTC beam: the best word of the beam (the kernel, on any device)
                 nbest = convertor.tensor2nbest(out_dec, nbest=1)[0] if is_ctc(convertor) and convertor.beam_width > 0 else None
+                if is_ctc(convertor) and convertor.lexicon is not None:       # the best word of the lexicon (the kernels, on any device)
+                    nbest = convertor.tensor2lexicon(out_dec, nbest=1)[0]
             label_indexes = convertor.tensor2idx(out_dec)[0] if nbest is None else [words[0] if words else [] for words in nbest]
             pt_text = convertor.idx2str(label_indexes)
             self.inference_time += time.time() - start

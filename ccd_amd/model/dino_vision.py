@@ -144,7 +144,8 @@ class DINO_Finetune(ArenaModule):
     NRTR decoder -> TFLoss.  Same constructor (a config object), parameter names and init RNG order as the reference.
     `decoder.type: 'CTCDecoder'` builds the CTC head instead (no reference counterpart): backbone -> CTCDecoder (frame pooling + one
     linear layer) -> CTCLoss, with a CTCConvertor; there is no `encoder` Mlp then.  `decoder.beam_width` > 0 makes evaluation decode by
-    CTC prefix beam search of that width (absent or 0: the greedy rule).  Any other type builds the NRTR recogniser; there
+    CTC prefix beam search of that width (absent or 0: the greedy rule); `decoder.lexicon: <path>` makes it pick the most probable word
+    of that word list instead (CTC head only; the NRTR head refuses a lexicon).  Any other type builds the NRTR recogniser; there
     `decoder.beam_width` > 0 is the width of `forward_beam` (beam search over the attention decoder: n-best words with their
     log-probabilities), which TextAccuracy then scores the best word of.  `forward_test` and `forward_test_speed` return the greedy
     probabilities whatever the width: a beam has no per-step distribution to return."""
@@ -160,7 +161,8 @@ class DINO_Finetune(ArenaModule):
         from ..loss.ce_loss import TFLoss
         from ..modules import vision_transformer as vits
         self.label_convertor = AttnConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len, with_unknown=True,
-                                             beam_width=int(getattr(config, "decoder_beam_width", 0) or 0))    # absent or 0: greedy
+                                             beam_width=int(getattr(config, "decoder_beam_width", 0) or 0),     # absent or 0: greedy
+                                             lexicon=getattr(config, "decoder_lexicon", None) or None)          # (refused: CTC head only)
         config.arch = config.arch.replace("deit", "vit")
         if config.arch not in vits.__dict__:
             raise NotImplementedError(f"Unknow architecture: {config.arch} (HIP kernels cover vit_tiny / vit_small / vit_base)")
@@ -184,7 +186,8 @@ class DINO_Finetune(ArenaModule):
         from ..loss.ctc_loss import CTCLoss
         from ..modules import vision_transformer as vits
         self.label_convertor = CTCConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len or 25, with_unknown=True,
-                                            beam_width=int(getattr(config, "decoder_beam_width", 0) or 0))     # absent or 0: greedy
+                                            beam_width=int(getattr(config, "decoder_beam_width", 0) or 0),     # absent or 0: greedy
+                                            lexicon=getattr(config, "decoder_lexicon", None) or None)          # absent: no lexicon
         config.arch = config.arch.replace("deit", "vit")
         if config.arch not in vits.__dict__:
             raise NotImplementedError(f"Unknow architecture: {config.arch} (HIP kernels cover vit_tiny / vit_small / vit_base)")

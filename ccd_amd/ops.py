@@ -923,6 +923,99 @@ def ctc_beam_search(scores, beam_width, normalized=False):
     return paths, lengths, hyp_scores
 
 
+# ------------------------------------------------------------------------------------------ lexicon decoding (kernels/ctc_lexicon.h)
+CTC_LEXICON_MAX_NBEST = 16                                # ccd_hip.h: CCD_CTC_LEXICON_MAX_NBEST
+CTC_LEXICON_CLASSES = (7, 15, CTC_MAX_LABELS)             # longest word of a length class: 16 / 32 / 64 lanes per word
+
+
+class CTCLexicon:
+    """A word list for ctc_lexicon_score (build it with ctc_lexicon): `words` int64 [V, max_len] on the host, in the caller's order;
+    a device copy in that order and up to three length-class slices (L <= 7, <= 15, <= 31), each (words int64 [n, class width],
+    columns int32 [n]), are uploaded once per device."""
+
+    def __init__(self, words):
+        self.words = words
+        self.lengths = (words != 0).to(I64).cumprod(dim=1).sum(dim=1) if words.shape[0] else torch.zeros(0, dtype=I64)
+        self._device = {}
+
+    def __len__(self):
+        return self.words.shape[0]
+
+    def on(self, device):
+        """(words on `device`, [(slice words, columns)])"""
+        key = str(device)
+        if key not in self._device:
+            def up(t):                                               # no host synchronisation: through pinned memory, asynchronously
+                return t.pin_memory().to(device, non_blocking=True) if torch.device(device).type == "cuda" else t.to(device)
+            slices, lo = [], -1
+            for hi in CTC_LEXICON_CLASSES:
+                cols = torch.nonzero((self.lengths > lo) & (self.lengths <= hi)).flatten()
+                lo = hi
+                if cols.numel():
+                    width = min(hi, self.words.shape[1])
+                    slices.append((up(self.words[cols][:, :width].contiguous()), up(cols.to(I32))))
+            self._device[key] = (up(self.words), slices)
+        return self._device[key]
+
+
+def ctc_lexicon(words):
+    """A lexicon handle from a host int64 [V, max_len] tensor of zero-padded classes (CTCConvertor.str2tensor's layout; max_len in
+    1..CTC_MAX_LABELS), built once per lexicon.  An all-zero row is the empty word; a row's word ends at its first zero."""
+    if not isinstance(words, torch.Tensor) or words.dtype != I64 or words.dim() != 2 or words.device.type != "cpu":
+        got = f"{str(words.dtype)[6:]} {list(words.shape)} on {words.device.type}" if isinstance(words, torch.Tensor) else type(words).__name__
+        raise ValueError(f"ctc_lexicon: expects a host int64 tensor [V, max_len], got {got}")
+    if not 1 <= words.shape[1] <= CTC_MAX_LABELS:
+        raise ValueError(f"ctc_lexicon: max_len must lie in 1..{CTC_MAX_LABELS}, got {words.shape[1]}")
+    return CTCLexicon(words.contiguous())
+
+
+def ctc_lexicon_score(scores, lexicon, normalized=False, subset=None):
+    """log p(word | frames) of every word of a lexicon (kernels/ctc_lexicon.h): scores fp32 [B, T, C] (any sample / step stride), logits
+    or - normalized=True - probabilities; lexicon: a ctc_lexicon handle -> fp32 [B, V], the CTC forward log-likelihood summed over
+    all alignments, -inf for a word no alignment of finite probability spells (a class outside [1, C), more characters than frames, a
+    masked class).  subset int32 [B, K]: sample b scores only the words subset[b, k] -> fp32 [B, K], -inf where an entry is negative
+    (padding) or >= V."""
+    if scores.dim() != 3 or (scores.shape[2] > 1 and scores.stride(2) != 1):
+        raise ValueError(f"ctc_lexicon_score: expects scores [B, T, C] with contiguous classes, got {list(scores.shape)}, strides {scores.stride()}")
+    if not isinstance(lexicon, CTCLexicon):
+        raise TypeError(f"ctc_lexicon_score: lexicon must come from ctc_lexicon, got {type(lexicon).__name__}")
+    B, T, C = scores.shape
+    V = len(lexicon)
+    words, slices = lexicon.on(scores.device)
+    flag = 1 if normalized else 0
+    if subset is not None:
+        if subset.dim() != 2 or subset.shape[0] != B or not subset.is_contiguous():
+            raise ValueError(f"ctc_lexicon_score: expects a contiguous subset [{B}, K], got {list(subset.shape)}")
+        K = subset.shape[1]
+        out = torch.full((B, K), float("-inf"), dtype=F32, device=scores.device)
+        if V and K:
+            _call("ccd_ctc_lexicon_score", scores, scores.stride(0), scores.stride(1), B, T, C, flag, words, V, words.shape[1], None, subset,
+                  K, out, K)
+        return out
+    out = torch.empty((B, V), dtype=F32, device=scores.device)
+    for part, columns in slices:                                 # every column belongs to exactly one length class
+        _call("ccd_ctc_lexicon_score", scores, scores.stride(0), scores.stride(1), B, T, C, flag, part, part.shape[0], part.shape[1],
+              columns, None, 0, out, V)
+    return out
+
+
+def ctc_lexicon_best(word_scores, nbest=1):
+    """word_scores fp32 [B, V] (any row stride) -> (index int32 [B, nbest], score fp32 [B, nbest]): the best columns of every row by
+    (score descending, column ascending); -inf is never selected, a slot left over holds index -1 and score -inf."""
+    if word_scores.dim() != 2 or (word_scores.shape[1] > 1 and word_scores.stride(1) != 1):
+        raise ValueError(f"ctc_lexicon_best: expects word_scores [B, V] with contiguous columns, got {list(word_scores.shape)}, strides "
+                         f"{word_scores.stride()}")
+    n = int(nbest)
+    if not 1 <= n <= CTC_LEXICON_MAX_NBEST:
+        raise ValueError(f"ctc_lexicon_best: nbest must lie in 1..{CTC_LEXICON_MAX_NBEST}, got {nbest}")
+    B, V = word_scores.shape
+    index = torch.empty((B, n), dtype=I32, device=word_scores.device)
+    best = torch.empty((B, n), dtype=F32, device=word_scores.device)
+    ld = word_scores.stride(0) if B > 1 else V                  # (the stride of a single row says nothing)
+    _call("ccd_ctc_lexicon_best", word_scores if V else None, ld, B, V, n, index, best)
+    return index, best
+
+
 # ------------------------------------------------------------------------------------------ NRTR beam search (kernels/nrtr_beam.h)
 NRTR_MAX_BEAM = 16                                        # ccd_hip.h: CCD_NRTR_MAX_BEAM
 NRTR_UNUSED, NRTR_LIVE, NRTR_FINISHED = 0, 1, 2           # ccd_hip.h: CCD_NRTR_UNUSED ..

@@ -488,6 +488,36 @@ int ccd_ctc_greedy(const float* logits, long sample_stride, long step_stride, in
 int ccd_ctc_beam_search(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
                         int beam, int* paths, int* lengths, float* hyp_scores, void* stream);
 
+/* Lexicon-constrained decoding of the CTC head (ABI 23; kernels/ctc_lexicon.h, restated in numpy in tests/ctc_lexicon_np.py): of THESE
+ * words, which is the most probable given the frames, and how probable is each.
+ * ccd_ctc_lexicon_score, a workgroup per (sample, strip of 64 words), lane = CTC state with 4 / 2 / 1 words packed into a wave:
+ *   scores      fp32 [batch, steps, classes] with sample / step strides in elements, logits (normalized = 0) or probabilities
+ *               (normalized = 1): the frame log-probabilities are exactly those of ccd_ctc_beam_search, so a lexicon score and a beam
+ *               score of the same word are comparable numbers.
+ *   words       int64 [n_words, max_len], zero-padded (the layout of ccd_ctc_loss_fwd's targets): the label length L is the number of
+ *               leading non-zero entries, found on the device; an all-zero row is the empty word (the sum of the blanks).
+ *   out         fp32 [batch, ld_out]: out[b, v] = log p(words[v] | scores[b]), the log of the summed probability of all alignments of
+ *               the word over the frames - the alpha recursion of ccd_ctc_loss_fwd in fp64, rounded once.  -inf where that kernel calls
+ *               the target infeasible (a label outside [1, classes) - never used as an index -, L + adjacent equal labels > steps) and
+ *               where every alignment meets a masked class; never NaN.
+ *   columns     optional int32 [n_words]: word v writes out[b, columns[v]] instead (a column outside [0, ld_out) writes nothing) - a
+ *               lexicon split by length class still fills the caller's order.
+ *   subset      optional int32 [batch, subset_cols]: sample b scores only words[subset[b, k]] into out[b, k]; an entry < 0 (the
+ *               padding of a ragged per-image list) or >= n_words gives -inf.  columns and subset together: CCD_EINVAL.
+ *   Lanes per word: the smallest of 16 / 32 / 64 that holds 2 max_len + 1 states - chosen from max_len alone.
+ * ccd_ctc_lexicon_best, one wavefront per sample: word_scores fp32 [batch, ld], `cols` valid columns -> index int32 [batch, nbest],
+ *   best fp32 [batch, nbest]: the nbest best columns by score descending, then column ascending (a word that appears twice gives two
+ *   columns of identical bits, the lower one first).  -inf is never selected; an unused slot has index -1 and score -inf.
+ * No atomics: the same input gives the same bits.  No workspace.  batch == 0 or n_words == 0 is a no-op.  CCD_EINVAL: a missing
+ * pointer, a negative size or stride, columns with subset; CCD_ESHAPE: steps outside 1..CCD_CTC_MAX_STEPS, classes outside
+ * 2..CCD_CTC_MAX_CLASSES, max_len outside 1..CCD_CTC_MAX_LABELS, normalized not 0 or 1, nbest outside 1..CCD_CTC_LEXICON_MAX_NBEST,
+ * ld_out < n_words (< subset_cols with subset; not checked with columns), ld < cols.  Nothing is launched on an error. */
+#define CCD_CTC_LEXICON_MAX_NBEST 16
+int ccd_ctc_lexicon_score(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
+                          const int64_t* words, int n_words, int max_len, const int* columns, const int* subset, int subset_cols,
+                          float* out, long ld_out, void* stream);
+int ccd_ctc_lexicon_best(const float* word_scores, long ld, int batch, int cols, int nbest, int* index, float* best, void* stream);
+
 /* Beam search over the NRTR attention decoder (ABI 22; kernels/nrtr_beam.h, restated in numpy in tests/nrtr_beam_np.py).  The decode
  * loop (finetune_engine.beam_decode) runs the incremental decoder on batch * beam rows, row b * beam + r = slot r of sample b, and calls
  * these two at the end of every step.

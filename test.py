@@ -68,6 +68,8 @@ def main():
     ap.add_argument("--batch_size", type=int, default=None)
     ap.add_argument("--beam_width", type=int, default=None,
                     help="beam search of this width, 1..16, for either head (CTC: prefix beam search; NRTR: beam over the decoder); 0: greedy decoding")
+    ap.add_argument("--lexicon", type=str, default=None,
+                    help="evaluate the CTC head with lexicon-constrained decoding over this UTF-8 word list (one word per line); excludes a beam")
     a = ap.parse_args()
     config = Config(a.config)
     if a.checkpoint is not None:
@@ -78,6 +80,8 @@ def main():
         config.dataset_test_batch_size = a.batch_size
     if a.beam_width is not None:
         config.decoder_beam_width = a.beam_width
+    if a.lexicon is not None:
+        config.decoder_lexicon = a.lexicon
     Logger.init(config.global_workdir, config.global_name, "test")
     utils.fix_random_seeds(int(config.global_seed or 0))
     logging.info("Construct dataset.")
@@ -85,6 +89,8 @@ def main():
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
     torch.cuda.set_device(device)
     model = DINO_Finetune(config).to(device)
+    if getattr(model.label_convertor, "lexicon_stats", None):
+        logging.info(f"lexicon {config.decoder_lexicon}: {model.label_convertor.lexicon_stats}")
     model.ensure_arena()
     model = DataParallel(model)
     if config.model_checkpoint:

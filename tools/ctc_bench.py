@@ -14,6 +14,11 @@ default the first three):
   beam    ccd_ctc_beam_search (kernels/ctc_beam.h) on probabilities fp32 [512, 32, 92] read from a 128-wide buffer, beam widths
           1, 4, 8, 16, next to ccd_ctc_greedy on the same buffer; then evaluation images/s at B = 512, vit_small (forward +
           TextAccuracy.update_scores, what TextAccuracy.compute does per batch) with beam_width 8 against greedy decoding.
+  lexicon ccd_ctc_lexicon_score / ccd_ctc_lexicon_best (kernels/ctc_lexicon.h) on the same probabilities: scoring at V = 1000 and
+          V = 10 000 words drawn from LEXICON_LENGTHS, scoring with a 50-word subset per image, the selection at nbest 1 and 16; the
+          yardstick in the same process: ccd_ctc_loss_fwd on the pairs of a 64-word slice with replicated rows (a 537 MB buffer), as
+          time per pair; then evaluation images/s at B = 512, vit_small, greedy against a 1000-word lexicon.
+    python tools/ctc_bench.py --cases lexicon --out profiles/ctc_lexicon.json
 Warm-up first, HIP events around every timed call, a figure is the median of the round medians with the lowest and highest
 round.  No threshold is set; the file records what was measured.  `--case NAME` runs one case and prints its JSON line."""
 import argparse
@@ -27,7 +32,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 B, T, C = 512, 32, 92
-LIMITS = {"loss": 240, "step": 420, "infer": 300, "beam": 300}           # seconds per case
+LIMITS = {"loss": 240, "step": 420, "infer": 300, "beam": 300, "lexicon": 420}           # seconds per case
+# word length -> share in per cent of a lexicon of `lexicon`: the shape of an English word list (mode 5 - 7 characters, a tail to 15)
+LEXICON_LENGTHS = {2: 2, 3: 6, 4: 11, 5: 14, 6: 15, 7: 14, 8: 12, 9: 9, 10: 7, 11: 4, 12: 3, 13: 1, 14: 1, 15: 1}
 
 
 def event_ms(fn, iters):
@@ -199,7 +206,102 @@ def case_beam(a):
     return out
 
 
-CASES = {"loss": case_loss, "step": case_step, "infer": case_infer, "beam": case_beam}
+def _peaked_probs(seed):
+    """fp32 probabilities [B, T, C] on the GPU, a view of a 128-wide buffer: moderately peaked frames, as case_beam's."""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    logits = torch.randn(B, T, C, generator=g)
+    peak = torch.where(torch.rand(B, T, generator=g) < 0.6, torch.randint(0, C, (B, T), generator=g), torch.zeros(B, T, dtype=torch.long))
+    logits.scatter_add_(2, peak[..., None], 2.0 + 6.0 * torch.rand(B, T, 1, generator=g))
+    buf = torch.zeros(B * T, 128)
+    buf[:, :C] = logits.softmax(-1).reshape(B * T, C)
+    return buf.to("cuda").view(B, T, 128)[:, :, :C]
+
+
+def _lexicon_words(V, seed):
+    """int64 [V, 15]: V distinct words of classes 1..90 whose lengths follow LEXICON_LENGTHS."""
+    import numpy as np
+    import torch
+    rs = np.random.RandomState(seed)
+    lengths = rs.choice(list(LEXICON_LENGTHS), size=V, p=np.array(list(LEXICON_LENGTHS.values())) / 100.0)
+    words = np.zeros((V, max(LEXICON_LENGTHS)), dtype=np.int64)
+    seen = set()
+    for row, n in zip(words, lengths):
+        while True:
+            w = tuple(rs.randint(1, 91, size=n))
+            if w not in seen:
+                seen.add(w)
+                row[:n] = w
+                break
+    return torch.from_numpy(words)
+
+
+def case_lexicon(a):
+    import torch
+    from ccd_amd import finetune as ft, ops
+    from ccd_amd.metric.eval_acc import TextAccuracy
+    dev = torch.device("cuda")
+    probs = _peaked_probs(5)
+    out = {"shape": [B, T, C], "input": "fp32 probabilities, normalized = 1", "word_length_per_cent": LEXICON_LENGTHS}
+    lex = {V: ops.ctc_lexicon(_lexicon_words(V, 6)) for V in (1000, 10000)}
+    subset = torch.stack([torch.randperm(1000, generator=torch.Generator().manual_seed(b))[:50] for b in range(B)]).to(torch.int32).to(dev)
+    iters = max(3, a.iters // 3)
+    score = {V: [] for V in lex}
+    sub, pick1, pick16, yard = [], [], [], []
+    scores = ops.ctc_lexicon_score(probs, lex[1000], normalized=True)
+    # the yardstick: the loss kernel on the pairs (sample, word) of the lexicon's first 64 words, every pair with its own copy of the rows
+    logp = probs.log()
+    rows = torch.zeros(B * 64 * T, 128, device=dev)
+    rows.view(B, 64, T, 128)[..., :C] = logp[:, None]
+    targets = torch.zeros(B * 64, 31, dtype=torch.long, device=dev)
+    targets[:, :15] = lex[1000].words[:64].to(dev).repeat(B, 1)
+    nll = ops.ctc_loss_fwd(rows, C, targets, T)[0].view(B, 64)
+    out["largest_difference_to_the_loss_kernel"] = float((scores[:, :64] + nll).abs().max())
+    for _ in range(a.rounds):
+        for V in lex:
+            score[V].append(event_ms(lambda: ops.ctc_lexicon_score(probs, lex[V], normalized=True), iters))
+        sub.append(event_ms(lambda: ops.ctc_lexicon_score(probs, lex[1000], normalized=True, subset=subset), a.iters))
+        pick1.append(event_ms(lambda: ops.ctc_lexicon_best(scores, 1), a.iters))
+        pick16.append(event_ms(lambda: ops.ctc_lexicon_best(scores, 16), a.iters))
+        yard.append(event_ms(lambda: ops.ctc_loss_fwd(rows, C, targets, T), iters))
+    for V in lex:
+        r = summary(score[V])
+        out[f"ctc_lexicon_score_v{V}"] = {**r, "pairs_per_s": round(B * V / (r["median_ms"] * 1e-3)), "ns_per_pair": round(r["median_ms"] * 1e6 / (B * V), 2)}
+    out["ctc_lexicon_score_subset_50_of_1000"] = summary(sub)
+    out["ctc_lexicon_best_nbest1_v1000"], out["ctc_lexicon_best_nbest16_v1000"] = summary(pick1), summary(pick16)
+    y = summary(yard)
+    out["yardstick_ctc_loss_fwd_64_words_replicated"] = {**y, "buffer_bytes": rows.numel() * 4, "ns_per_pair": round(y["median_ms"] * 1e6 / (B * 64), 2)}
+    out["yardstick_over_lexicon_per_pair"] = round(out["yardstick_ctc_loss_fwd_64_words_replicated"]["ns_per_pair"] /
+                                                    out["ctc_lexicon_score_v1000"]["ns_per_pair"], 2)
+    del rows, targets, logp
+    # evaluation: forward + scoring, the body of TextAccuracy.compute
+    torch.manual_seed(0)
+    cfg = ft.FinetuneConfig()
+    cfg.decoder_type = "CTCDecoder"
+    model = ft.build_model(cfg, dev, dropout=0.0).eval()
+    conv = model.label_convertor
+    img = torch.randn(B, 3, 32, 128, generator=torch.Generator().manual_seed(4)).to(dev)
+    words = ["".join(conv.idx2char[1 + (i * 7 + j) % 90] for j in range(3 + i % 13)) for i in range(B)]
+    table = lex[1000].words
+    strings = conv.idx2str([row[row != 0].tolist() for row in table])
+    metric = TextAccuracy()
+
+    def evaluate():
+        metric.update_scores(model(img, text=None, return_loss=False, test_speed=False).float(), words, conv)
+
+    sides = {"greedy": [], "lexicon": []}
+    with torch.no_grad():
+        for _ in range(a.rounds):
+            for name in sides:
+                conv.set_lexicon(strings if name == "lexicon" else None)
+                sides[name].append(event_ms(evaluate, iters))
+    g0, l1 = summary(sides["greedy"]), summary(sides["lexicon"])
+    out.update({"batch": B, "arch": "vit_small", "evaluate_greedy": g0, "evaluate_lexicon_1000": l1,
+                "greedy_images_per_s": round(B / (g0["median_ms"] * 1e-3)), "lexicon_1000_images_per_s": round(B / (l1["median_ms"] * 1e-3))})
+    return out
+
+
+CASES = {"loss": case_loss, "step": case_step, "infer": case_infer, "beam": case_beam, "lexicon": case_lexicon}
 
 
 def main():

@@ -121,6 +121,8 @@ def main(config):
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
     utils.fix_random_seeds(int(config.global_seed or config.seed or 0))
     model = DINO_Finetune(config).to(device)
+    if getattr(model.label_convertor, "lexicon_stats", None):
+        logging.info(f"lexicon {config.decoder_lexicon}: {model.label_convertor.lexicon_stats}")
     model.ensure_arena()
     model = DataParallel(model)                          # `module.` key prefix like nn.DataParallel; reducer when world > 1
     model.train()
@@ -208,10 +210,14 @@ def _parse_arguments():
     parser.add_argument("--local_rank", "--local-rank", default=0, type=int, help="set by the launcher; ignored")
     parser.add_argument("--beam_width", type=int, default=None,
                         help="evaluate with beam search of this width, 1..16, for either head (CTC: prefix beam search; NRTR: beam over the decoder); 0: greedy")
+    parser.add_argument("--lexicon", type=str, default=None,
+                        help="evaluate the CTC head with lexicon-constrained decoding over this UTF-8 word list (one word per line); excludes a beam")
     args, _ = parser.parse_known_args()
     config = Config(args.config)
     if args.beam_width is not None:
         config.decoder_beam_width = args.beam_width
+    if args.lexicon is not None:
+        config.decoder_lexicon = args.lexicon
     return config
 
 
