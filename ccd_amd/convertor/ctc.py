@@ -15,6 +15,11 @@ words are scored (TextAccuracy) and in `tensor2lexicon` the answer is the most p
 probability summed over all alignments (ops.ctc_lexicon_score / ops.ctc_lexicon_best).  The words are encoded as targets are (`lower`,
 `<UKN>`); words of more than 31 classes and duplicates after encoding are dropped and counted in `lexicon_stats`.  A lexicon and a
 beam exclude each other.
+
+An `lm` (a char_lm.CharNGram, the path of an .npz it saved, or the path of a UTF-8 word list, which is estimated at `lm_order`) fuses a
+character n-gram language model into the beam search (ops.ctc_beam_search_lm): where words are scored (TextAccuracy) and in
+`tensor2nbest` every extension by a character adds lm_weight * log P(character | context) + lm_bonus, and with `lm_eos` the end of the
+word adds lm_weight * log P(end | context) behind the last frame.  An LM needs beam_width >= 1 and excludes a lexicon.
 """
 from __future__ import annotations
 
@@ -31,13 +36,13 @@ def is_ctc(convertor):
 
 
 class CTCConvertor:
-    """CTCConvertor(dict_type='DICT90', with_unknown=True, max_seq_len=25, lower=False, beam_width=0, lexicon=None) - see the module
-    docstring."""
+    """CTCConvertor(dict_type='DICT90', with_unknown=True, max_seq_len=25, lower=False, beam_width=0, lexicon=None, lm=None, lm_order=2,
+    lm_weight=1.0, lm_bonus=0.0, lm_eos=True) - see the module docstring."""
 
     dicts = {name: tuple(chars) for name, chars in ALPHABETS.items()}
 
     def __init__(self, dict_type="DICT90", dict_file=None, dict_list=None, with_unknown=True, max_seq_len=25, lower=False, beam_width=0,
-                 lexicon=None, **_ignored):
+                 lexicon=None, lm=None, lm_order=2, lm_weight=1.0, lm_bonus=0.0, lm_eos=True, **_ignored):
         if dict_file is not None:
             alphabet = _read_alphabet_file(dict_file)
         elif dict_list is not None:
@@ -66,6 +71,45 @@ class CTCConvertor:
         self.lexicon, self.lexicon_words, self.lexicon_stats = None, None, None
         if lexicon is not None:
             self.set_lexicon(lexicon)
+        self.lm, self.lm_model, self.lm_stats = None, None, None
+        self.lm_order, self.lm_weight, self.lm_bonus, self.lm_eos = int(lm_order), float(lm_weight), float(lm_bonus), bool(lm_eos)
+        if lm is not None:
+            self.set_lm(lm)
+
+    def set_lm(self, lm, order=None, weight=None, bonus=None, eos=None):
+        """The language model of tensor2nbest and TextAccuracy: a char_lm.CharNGram, the path of an .npz that CharNGram.save wrote, or
+        the path of a UTF-8 word list (one word per line), estimated at `order` (default: lm_order); None removes it.  weight / bonus /
+        eos replace lm_weight / lm_bonus / lm_eos where given.  Kept: `lm` (the ops.ctc_char_lm handle), `lm_model` (the CharNGram) and
+        `lm_stats` = {'order', 'classes', 'rows', 'bytes'}."""
+        from .. import ops
+        from .char_lm import CharNGram
+        if lm is None:
+            self.lm, self.lm_model, self.lm_stats = None, None, None
+            return None
+        if self.lexicon is not None:
+            raise ValueError("a language model and a lexicon exclude each other: lexicon decoding scores the words of a closed list "
+                             "exactly, remove the lexicon (set_lexicon(None)) or the language model")
+        if self.beam_width < 1:
+            raise ValueError("a language model needs beam_width >= 1: it is fused into the beam search, and the convertor's beam_width "
+                             "is 0 (greedy decoding)")
+        if order is not None:
+            self.lm_order = int(order)
+        if isinstance(lm, CharNGram):
+            model = lm
+        elif isinstance(lm, (str, bytes)) or hasattr(lm, "__fspath__"):
+            name = lm.decode() if isinstance(lm, bytes) else str(lm)
+            model = CharNGram.load(name) if name.endswith(".npz") else CharNGram.from_words(self, name, order=self.lm_order)
+        else:
+            raise TypeError(f"set_lm expects a CharNGram, the path of an .npz or the path of a word list, got {type(lm).__name__}")
+        model.check_alphabet(self)
+        handle = ops.ctc_char_lm(model.table, model.order)
+        for name, value, kind in (("lm_weight", weight, float), ("lm_bonus", bonus, float), ("lm_eos", eos, bool)):
+            if value is not None:
+                setattr(self, name, kind(value))
+        if not (np.isfinite(self.lm_weight) and np.isfinite(self.lm_bonus)):
+            raise ValueError(f"lm_weight and lm_bonus must be finite, got {self.lm_weight} and {self.lm_bonus}")
+        self.lm, self.lm_model, self.lm_order, self.lm_stats = handle, model, model.order, model.stats
+        return self.lm_stats
 
     def set_lexicon(self, strings_or_path):
         """The closed vocabulary of tensor2lexicon and TextAccuracy: a list of words, or the path of a UTF-8 file with one word per line
@@ -75,6 +119,8 @@ class CTCConvertor:
         if strings_or_path is None:
             self.lexicon, self.lexicon_words, self.lexicon_stats = None, None, None
             return None
+        if getattr(self, "lm", None) is not None:
+            raise ValueError("a lexicon and a language model exclude each other: remove the language model (set_lm(None)) first")
         if self.beam_width > 0:
             raise ValueError(f"a lexicon and beam_width = {self.beam_width} exclude each other: lexicon decoding scores every word of "
                              "the lexicon exactly, set beam_width to 0")
@@ -180,11 +226,16 @@ class CTCConvertor:
         """[N, T, C] frame scores on the device - probabilities (normalized=True: what CTCDecoder.forward_test returns) or logits
         -> (indexes, log_probs) by CTC prefix beam search of width `beam_width` (default: the convertor's own, which must then be
         > 0): indexes[i] holds up to `nbest` index lists, best first; log_probs is a float tensor [N, nbest], the log of each word's
-        probability summed over the alignments the beam kept, -inf where a slot is empty."""
+        probability summed over the alignments the beam kept, -inf where a slot is empty.  With a language model set (set_lm) the search
+        is the fused one and log_probs are the fused scores: log p_ctc(word) + lm_weight * sum log P_lm + lm_bonus * len(word), with
+        lm_eos the end-of-word term included - comparable with the plain beam's only after that sum is subtracted."""
         from .. import ops
         width = self.beam_width if beam_width is None else int(beam_width)
         if width < 1:
             raise ValueError("tensor2nbest: needs a beam_width >= 1 (the convertor's is 0: greedy decoding)")
+        if self.lm is not None:
+            return nbest_lists("tensor2nbest", *ops.ctc_beam_search_lm(outputs.float(), width, self.lm, self.lm_weight, self.lm_bonus,
+                                                                       self.lm_eos, normalized=normalized), nbest)
         return nbest_lists("tensor2nbest", *ops.ctc_beam_search(outputs.float(), width, normalized=normalized), nbest)
 
     @torch.no_grad()

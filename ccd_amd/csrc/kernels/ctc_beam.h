@@ -26,6 +26,24 @@
 // of a live wave leaves before the last shuffle.  Arithmetic is fp64 (ctc_real) throughout; probabilities (normalized) go through the
 // same ascending-order sum as logits.  What the software fp64 exp / log and the W-fold rescan cost on the device: tools/ctc_bench.py,
 // case `beam`.
+//
+// Language-model fusion (ccd_ctc_beam_search_lm, ctc_beam_kernel<true>; tests/ctc_beam_lm_np.py is the specification): the same kernel -
+// `template <bool kLm>`, whose `false` instance is the code above and nothing else - with one additive term per extension from a character
+// n-gram table lm fp32 [C^(order-1), C]: the row of an entry is its last order - 1 classes (most recent last, 0 where the prefix is
+// shorter), column c >= 1 the log-probability of character c behind that context, column 0 that of the word ending there.
+//     g(i, c) = lm[row_i, c] == -inf ? -inf : (double)weight * (double)lm[row_i, c] + (double)bonus      (the product, then the sum)
+//     extend (i, c)   pnb' = ((c == last_i ? pb_i : tot_i) + lp[c]) + g(i, c); a merge log-adds that same number
+// so pb and pnb of a prefix both carry the sum of g over its characters.  Stay candidates, the key and the tie rule are unchanged.
+// Where the table is read: when the entries of a frame are written, lane r derives the row of entry r from the last two prefix bytes
+// in LDS; every lane then requests lm[row_i * C + c] for its two classes of every live entry - coalesced 4-byte loads of a table that
+// stays in L2 - into registers, right behind the selection.  They are stored into a per-wave fp32 [16][128] LDS block behind the next
+// frame's fp64 log-softmax, which hides them; the scan reads its own two columns back (dynamic entry index), and the one cross-lane
+// read is the absorbed class of a merge, behind a wave_lds_fence.  g is formed where the candidate score is: one fp64 multiply and add.
+// eos: behind the last frame lane r adds (double)weight * lm[row_r, 0] to entry r (-inf where the table says so), counts the entries
+// that beat it by (score descending, previous rank ascending) and the results are written by that rank; a -inf entry is an unused slot.
+// LDS: 8 KB + 64 B per wave on top of the 4.2 KB above: 50 176 B = 49 KB per workgroup (17 152 B without a language model) - under the
+// 64 KB static limit, three workgroups per CU by LDS.  The 32 values in flight cost registers (176 VGPRs against 106: two waves per
+// SIMD), which a kernel of one wave per sample does not miss.
 #pragma once
 
 #include "beam_wave.h"
@@ -43,14 +61,52 @@ struct CtcBeamWave {
     unsigned char prefix[2][CTC_MAX_BEAM][CTC_MAX_T];            // extension this entry's stay candidate takes in, or -1
 };
 
-// grid = ceil(B / CTC_WAVES).  The launcher has checked 1 <= W <= CTC_MAX_BEAM, 1 <= T <= CTC_MAX_T, 2 <= C <= CTC_MAX_C.
+template <bool kLm>
+struct CtcBeamLmWave {};                                         // (nothing without a language model)
+template <>
+struct CtcBeamLmWave<true> {
+    float v[CTC_MAX_BEAM][CTC_MAX_C];                            // lm[row_i, c] of the live entries, as the table holds it
+    int row[CTC_MAX_BEAM];                                       // the table row of entry i
+};
+
+struct CtcBeamLm {                                               // the language model of a launch (unused without one)
+    const float* table;                                          // fp32 [C^(order-1), C]
+    int order, eos;
+    double weight, bonus;
+};
+
+// g of one table value: the fp64 product, then the fp64 sum; -inf stays -inf whatever the weight.
+__device__ __forceinline__ ctc_real ctc_lm_term(float v, double weight, double bonus) {
+    return v == -__builtin_inff() ? ctc_neg_inf() : weight * (double)v + bonus;
+}
+
+// All 64 lanes.  Requests lm[row_i, c] of the lane's two classes for every live entry into registers (consumed a frame later).
+__device__ __forceinline__ void ctc_lm_fetch(const CtcBeamLmWave<true>& w, const float* __restrict__ table, int C, int n, int c0, int c1,
+                                             bool has0, bool has1, float (&r)[2 * CTC_MAX_BEAM]) {
+#pragma unroll
+    for (int i = 0; i < CTC_MAX_BEAM; ++i) {
+        r[2 * i] = r[2 * i + 1] = 0.f;
+        if (i < n) {
+            const float* const p = table + (long)w.row[i] * C;
+            if (has0) r[2 * i] = p[c0];
+            if (has1) r[2 * i + 1] = p[c1];
+        }
+    }
+}
+
+// grid = ceil(B / CTC_WAVES).  The launcher has checked 1 <= W <= CTC_MAX_BEAM, 1 <= T <= CTC_MAX_T, 2 <= C <= CTC_MAX_C and, with a
+// language model (kLm; `lm` is not looked at without one), 1 <= order <= 3, eos in {0, 1}, weight and bonus finite; the table holds
+// C^(order-1) rows of C.  Every line the model adds sits behind `if constexpr (kLm)`: the `false` instance is the kernel as it was.
+template <bool kLm>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __restrict__ scores, long sample_stride, long step_stride, int B,
                                                                int T, int C, int normalized, int W, int* __restrict__ paths,
-                                                               int* __restrict__ lengths, float* __restrict__ hyp_scores) {
+                                                               int* __restrict__ lengths, float* __restrict__ hyp_scores, CtcBeamLm lm) {
     __shared__ CtcBeamWave waves[CTC_WAVES];
+    __shared__ CtcBeamLmWave<kLm> tables[CTC_WAVES];
     const int lane = lane_id(), b = blockIdx.x * CTC_WAVES + wave_id();
     if (b >= B) return;                                                    // (whole waves; no workgroup barrier below)
     CtcBeamWave& s = waves[wave_id()];
+    CtcBeamLmWave<kLm>& m = tables[wave_id()];
     const float* const x = scores + (long)b * sample_stride;
     const int c0 = lane, c1 = lane + 64;
     const bool has0 = c0 < C, has1 = c1 < C;
@@ -60,10 +116,13 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
         s.pnb[lane] = ctc_neg_inf();
         s.len[lane] = lane == 0 ? 0 : -1;
         s.last[lane] = 0;
+        if constexpr (kLm) m.row[lane] = 0;                                // the empty prefix: every position missing
     }
     wave_lds_fence();
     int n = 1, cur = 0;                                                    // live entries (wave-uniform), the prefix buffer that holds them
     float next0 = has0 ? x[c0] : 0.f, next1 = has1 ? x[c1] : 0.f;
+    float lmv[2 * CTC_MAX_BEAM];                                           // kLm: the table values requested for the next frame's entries
+    if constexpr (kLm) ctc_lm_fetch(m, lm.table, C, n, c0, c1, has0, has1, lmv);
     for (int t = 0; t < T; ++t) {
         const float v0 = next0, v1 = next1;
         if (t + 1 < T) {                                                   // the next frame is requested before this frame's arithmetic
@@ -76,6 +135,14 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
         const ctc_real lp0 = lp.c0, lp1 = lp.c1;
         if (has0) s.lp[c0] = lp0;
         if (has1) s.lp[c1] = lp1;
+        if constexpr (kLm) {                                               // requested behind the last selection: a log-softmax ago
+#pragma unroll
+            for (int i = 0; i < CTC_MAX_BEAM; ++i)
+                if (i < n) {
+                    m.v[i][c0] = lmv[2 * i];
+                    m.v[i][c1] = lmv[2 * i + 1];
+                }
+        }
         if (lane < n) {
             s.tot[lane] = ctc_lae(s.pb[lane], s.pnb[lane]);
             s.absorb[lane] = -1;
@@ -111,7 +178,11 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
             const int lj = s.last[lane], from = s.absorb[lane];
             const ctc_real lpl = s.lp[lj];
             ctc_real pnb = s.len[lane] > 0 ? s.pnb[lane] + lpl : ctc_neg_inf();
-            if (from >= 0) pnb = ctc_lae(pnb, (s.last[from] == lj ? s.pb[from] : s.tot[from]) + lpl);
+            if (from >= 0) {
+                ctc_real ext = (s.last[from] == lj ? s.pb[from] : s.tot[from]) + lpl;
+                if constexpr (kLm) ext = ext + ctc_lm_term(m.v[from][lj], lm.weight, lm.bonus);       // (another lane's column)
+                pnb = ctc_lae(pnb, ext);
+            }
             const ctc_real pb = s.tot[lane] + s.lp[0];
             s.stay_pb[lane] = pb;
             s.stay_pnb[lane] = pnb;
@@ -131,7 +202,9 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
                 const int lasti = s.last[i];
                 if (has0 && !((given >> (2 * i)) & 1u)) {
                     const bool gone = (s.merged[i][0] >> lane) & 1ull;
-                    const ctc_real sc = c0 == 0 ? s.stay_score[i] : (gone ? ctc_neg_inf() : (c0 == lasti ? pbi : toti) + lp0);
+                    ctc_real ext = (c0 == lasti ? pbi : toti) + lp0;
+                    if constexpr (kLm) ext = ext + ctc_lm_term(m.v[i][c0], lm.weight, lm.bonus);
+                    const ctc_real sc = c0 == 0 ? s.stay_score[i] : (gone ? ctc_neg_inf() : ext);
                     if (sc > best) {
                         best = sc;
                         best_k = i * C + c0;
@@ -139,7 +212,9 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
                 }
                 if (has1 && !((given >> (2 * i + 1)) & 1u)) {
                     const bool gone = (s.merged[i][1] >> lane) & 1ull;
-                    const ctc_real sc = gone ? ctc_neg_inf() : (c1 == lasti ? pbi : toti) + lp1;
+                    ctc_real ext = (c1 == lasti ? pbi : toti) + lp1;
+                    if constexpr (kLm) ext = ext + ctc_lm_term(m.v[i][c1], lm.weight, lm.bonus);
+                    const ctc_real sc = gone ? ctc_neg_inf() : ext;
                     if (sc > best) {
                         best = sc;
                         best_k = i * C + c1;
@@ -167,12 +242,51 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
             s.pnb[lane] = new_pnb;
             s.len[lane] = new_len;
             s.last[lane] = new_last;
+            if constexpr (kLm) {                                           // the row of the new entry from its last two prefix bytes
+                const int p1 = new_len >= 1 ? (int)s.prefix[cur ^ 1][lane][new_len - 1] : 0;
+                const int p2 = new_len >= 2 ? (int)s.prefix[cur ^ 1][lane][new_len - 2] : 0;
+                m.row[lane] = lm.order == 1 ? 0 : (lm.order == 2 ? p1 : p2 * C + p1);
+            }
         }
         n = uniform_i32(n_new);
         cur ^= 1;
         wave_lds_fence();
+        if constexpr (kLm)
+            if (t + 1 < T) ctc_lm_fetch(m, lm.table, C, n, c0, c1, has0, has1, lmv);
     }
 
+    if constexpr (kLm) {
+        if (lm.eos) {                                                      // (wave-uniform)
+            // ---- the end of the word: lane r re-scores entry r and counts the entries that beat it; absorb[rank] = the entry
+            ctc_real fs = ctc_neg_inf();
+            if (lane < n) {
+                const float v = lm.table[(long)m.row[lane] * C];
+                fs = v == -__builtin_inff() ? ctc_neg_inf() : ctc_lae(s.pb[lane], s.pnb[lane]) + lm.weight * (double)v;
+            }
+            if (lane < CTC_MAX_BEAM) s.stay_score[lane] = fs;
+            wave_lds_fence();
+            if (lane < CTC_MAX_BEAM) {
+                int rank = 0;
+                for (int q = 0; q < CTC_MAX_BEAM; ++q) {
+                    const ctc_real os = s.stay_score[q];
+                    rank += (os > fs || (os == fs && q < lane)) ? 1 : 0;
+                }
+                s.absorb[rank] = lane;
+            }
+            wave_lds_fence();
+            if (lane < W) {
+                const int src = s.absorb[lane];
+                const ctc_real sc = s.stay_score[src];
+                lengths[(long)b * W + lane] = sc > ctc_neg_inf() ? s.len[src] : -1;
+                hyp_scores[(long)b * W + lane] = (float)sc;
+            }
+            for (int r = 0; r < W; ++r) {
+                const int src = s.absorb[r], len = s.stay_score[src] > ctc_neg_inf() ? s.len[src] : -1;
+                if (lane < T) paths[((long)b * W + r) * T + lane] = lane < len ? (int)s.prefix[cur][src][lane] : -1;
+            }
+            return;
+        }
+    }
     // ---- the entries are in rank order: the selection of the last frame sorted them by logaddexp(pb, pnb)
     if (lane < W) {
         const int len = s.len[lane];

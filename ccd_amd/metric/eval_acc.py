@@ -146,6 +146,9 @@ class TextAccuracy:
         gt, gt_len = self._upload_truth("update_scores", gt_text, scores.shape[0], scores.device)
         if is_ctc(conv) and conv.lexicon is not None:                         # the most probable word of the lexicon
             records = ops.text_score_paths(self._lexicon_paths(conv, scores), raw, norm, gt, gt_len)
+        elif is_ctc(conv) and conv.beam_width > 0 and getattr(conv, "lm", None) is not None:     # the beam fused with the language model
+            paths, _, _ = ops.ctc_beam_search_lm(scores, conv.beam_width, conv.lm, conv.lm_weight, conv.lm_bonus, conv.lm_eos, normalized=True)
+            records = ops.text_score_paths(paths[:, 0], raw, norm, gt, gt_len)
         elif is_ctc(conv) and conv.beam_width > 0:                            # prefix beam search on the probabilities, rank 0 scored
             paths, _, _ = ops.ctc_beam_search(scores, conv.beam_width, normalized=True)
             records = ops.text_score_paths(paths[:, 0], raw, norm, gt, gt_len)

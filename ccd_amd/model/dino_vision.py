@@ -22,6 +22,11 @@ dbscan = DBSCAN_cluster(eps=1.5, min_samples=4)
 label = label_cluster()
 
 
+def _absent(value, default):
+    """A key the YAML leaves out reads as None: the default then; 0 and False are values."""
+    return default if value is None else value
+
+
 class ClusterMaps:
     """What the student hands to the teacher as `clusters=` (reference: a dense [2B,26,32,128] tensor)."""
 
@@ -162,7 +167,8 @@ class DINO_Finetune(ArenaModule):
         from ..modules import vision_transformer as vits
         self.label_convertor = AttnConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len, with_unknown=True,
                                              beam_width=int(getattr(config, "decoder_beam_width", 0) or 0),     # absent or 0: greedy
-                                             lexicon=getattr(config, "decoder_lexicon", None) or None)          # (refused: CTC head only)
+                                             lexicon=getattr(config, "decoder_lexicon", None) or None,          # (refused: CTC head only)
+                                             lm=getattr(config, "decoder_lm", None) or None)                    # (refused as well)
         config.arch = config.arch.replace("deit", "vit")
         if config.arch not in vits.__dict__:
             raise NotImplementedError(f"Unknow architecture: {config.arch} (HIP kernels cover vit_tiny / vit_small / vit_base)")
@@ -187,7 +193,12 @@ class DINO_Finetune(ArenaModule):
         from ..modules import vision_transformer as vits
         self.label_convertor = CTCConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len or 25, with_unknown=True,
                                             beam_width=int(getattr(config, "decoder_beam_width", 0) or 0),     # absent or 0: greedy
-                                            lexicon=getattr(config, "decoder_lexicon", None) or None)          # absent: no lexicon
+                                            lexicon=getattr(config, "decoder_lexicon", None) or None,          # absent: no lexicon
+                                            lm=getattr(config, "decoder_lm", None) or None,                    # absent: no language model
+                                            lm_order=_absent(getattr(config, "decoder_lm_order", None), 2),
+                                            lm_weight=_absent(getattr(config, "decoder_lm_weight", None), 1.0),
+                                            lm_bonus=_absent(getattr(config, "decoder_lm_bonus", None), 0.0),
+                                            lm_eos=_absent(getattr(config, "decoder_lm_eos", None), True))
         config.arch = config.arch.replace("deit", "vit")
         if config.arch not in vits.__dict__:
             raise NotImplementedError(f"Unknow architecture: {config.arch} (HIP kernels cover vit_tiny / vit_small / vit_base)")

@@ -923,6 +923,71 @@ def ctc_beam_search(scores, beam_width, normalized=False):
     return paths, lengths, hyp_scores
 
 
+# ------------------------------------------------------------------------------------------ language-model fusion (kernels/ctc_beam.h)
+CTC_LM_MAX_ORDER = 3                                      # ccd_hip.h: CCD_CTC_LM_MAX_ORDER
+
+
+class CTCCharLM:
+    """A character n-gram table for ctc_beam_search_lm (build it with ctc_char_lm): `table` fp32 [C^(order-1), C] on the host; a device
+    copy is uploaded once per device."""
+
+    def __init__(self, table, order):
+        self.table, self.order, self.classes = table, order, table.shape[1]
+        self._device = {}
+
+    def on(self, device):
+        key = str(device)
+        if key not in self._device:                                  # no host synchronisation: through pinned memory, asynchronously
+            cuda = torch.device(device).type == "cuda"
+            self._device[key] = self.table.pin_memory().to(device, non_blocking=True) if cuda else self.table.to(device)
+        return self._device[key]
+
+
+def ctc_char_lm(table, order):
+    """A language-model handle from a host fp32 tensor [C^(order-1), C] (CharNGram.table; order in 1..CTC_LM_MAX_ORDER), built once
+    per model.  Row: the last order - 1 classes of a prefix, most recent last, 0 where the prefix is shorter; column c >= 1: the
+    log-probability of character c behind that context, column 0: of the word ending there.  Values are finite or -inf; NaN is refused."""
+    if not isinstance(table, torch.Tensor) or table.dtype != F32 or table.dim() != 2 or table.device.type != "cpu":
+        got = f"{str(table.dtype)[6:]} {list(table.shape)} on {table.device.type}" if isinstance(table, torch.Tensor) else type(table).__name__
+        raise ValueError(f"ctc_char_lm: expects a host float32 tensor [C^(order-1), C], got {got}")
+    order = int(order)
+    if not 1 <= order <= CTC_LM_MAX_ORDER:
+        raise ValueError(f"ctc_char_lm: order must lie in 1..{CTC_LM_MAX_ORDER}, got {order}")
+    C = table.shape[1]
+    if not 2 <= C <= CTC_MAX_CLASSES or table.shape[0] != C ** (order - 1):
+        raise ValueError(f"ctc_char_lm: an order-{order} table over C classes (2..{CTC_MAX_CLASSES}) has shape [C^{order - 1}, C], "
+                         f"got {list(table.shape)}")
+    if bool(torch.isnan(table).any()) or bool((table == float("inf")).any()):
+        raise ValueError("ctc_char_lm: the table holds NaN or +inf (entries are log-probabilities: finite or -inf)")
+    return CTCCharLM(table.contiguous(), order)
+
+
+def ctc_beam_search_lm(scores, beam_width, lm, weight=1.0, bonus=0.0, eos=False, normalized=False):
+    """CTC prefix beam search fused with a character n-gram language model (kernels/ctc_beam.h: ctc_beam_kernel<true>): scores and
+    beam_width as ctc_beam_search, lm a ctc_char_lm handle -> (paths, lengths, hyp_scores) shaped as ctc_beam_search returns them.
+    Every extension of a prefix by character c adds weight * lm[row, c] + bonus to the candidate (-inf where the table says so), so a
+    hypothesis scores log p_ctc(word | kept alignments) + weight * sum lm + bonus * len(word); eos=True adds weight * lm[row, 0] behind
+    the last frame and ranks the hypotheses again (a -inf one becomes an unused slot).  weight = 0, bonus = 0 and a finite table give
+    ctc_beam_search's result bit for bit."""
+    if scores.dim() != 3 or (scores.shape[2] > 1 and scores.stride(2) != 1):
+        raise ValueError(f"ctc_beam_search_lm: expects scores [B, T, C] with contiguous classes, got {list(scores.shape)}, strides "
+                         f"{scores.stride()}")
+    if not isinstance(lm, CTCCharLM):
+        raise TypeError(f"ctc_beam_search_lm: lm must come from ctc_char_lm, got {type(lm).__name__}")
+    B, T, C = scores.shape
+    if lm.classes != C:
+        raise ValueError(f"ctc_beam_search_lm: the table was built for {lm.classes} classes, the scores have {C}")
+    W = int(beam_width)
+    if not 1 <= W <= CTC_MAX_BEAM:
+        raise ValueError(f"ctc_beam_search_lm: beam_width must lie in 1..{CTC_MAX_BEAM}, got {beam_width}")
+    paths = torch.empty((B, W, T), dtype=I32, device=scores.device)
+    lengths = torch.empty((B, W), dtype=I32, device=scores.device)
+    hyp_scores = torch.empty((B, W), dtype=F32, device=scores.device)
+    _call("ccd_ctc_beam_search_lm", scores, scores.stride(0), scores.stride(1), B, T, C, 1 if normalized else 0, W, lm.on(scores.device),
+          lm.order, float(weight), float(bonus), 1 if eos else 0, paths, lengths, hyp_scores)
+    return paths, lengths, hyp_scores
+
+
 # ------------------------------------------------------------------------------------------ lexicon decoding (kernels/ctc_lexicon.h)
 CTC_LEXICON_MAX_NBEST = 16                                # ccd_hip.h: CCD_CTC_LEXICON_MAX_NBEST
 CTC_LEXICON_CLASSES = (7, 15, CTC_MAX_LABELS)             # longest word of a length class: 16 / 32 / 64 lanes per word

@@ -487,6 +487,34 @@ int ccd_ctc_greedy(const float* logits, long sample_stride, long step_stride, in
 #define CCD_CTC_MAX_BEAM 16
 int ccd_ctc_beam_search(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
                         int beam, int* paths, int* lengths, float* hyp_scores, void* stream);
+/* CTC prefix beam search fused with a character n-gram language model (ABI 24; kernels/ctc_beam.h: ctc_beam_kernel<true>, restated in
+ * numpy in tests/ctc_beam_lm_np.py): the open-vocabulary decoder that prefers plausible spellings.  scores, beam and the outputs as
+ * ccd_ctc_beam_search; one wavefront per sample.
+ *   lm          fp32 [classes^(order-1), classes], row-major, order in 1..CCD_CTC_LM_MAX_ORDER.  The row of a prefix p is built from its
+ *               last order - 1 classes, the most recent last, a missing position being 0 (the blank's number: "start of word"):
+ *               order 1: row 0; order 2: row p[-1]; order 3: row p[-2] * classes + p[-1].  Column c >= 1: the log-probability of
+ *               character c behind that context; column 0: that of the word ending there, read only with eos.  Values are finite or
+ *               -inf (NaN is outside the specification); rows need not be normalised.
+ *   weight, bonus   fp32.  The term of extending a prefix by c is
+ *                   g = lm[row, c] == -inf ? -inf : (double)weight * (double)lm[row, c] + (double)bonus     (the product, then the sum).
+ *   Per frame everything is as ccd_ctc_beam_search states it, with one exception: an extend candidate (i, c) has
+ *               pnb' = ((c == last_i ? pb_i : tot_i) + lp[c]) + g(i, c), and that same number is what a merge log-adds into entry j's
+ *               stay candidate.  Stay candidates, the selection key and the tie rule are unchanged.  pb and pnb of a prefix both carry
+ *               Lambda(prefix) = the sum of g over its characters, so a word's score is
+ *               log p_ctc(word | kept alignments) + weight * sum lm + bonus * |word|.
+ *   eos = 1     behind the last frame every entry's score gets (double)weight * lm[row, 0] (no bonus), -inf where the table entry is
+ *               -inf; the entries are ranked again by (score descending, previous rank ascending), and a -inf entry becomes an unused
+ *               slot (length -1, score -inf, path all -1).  The term does not steer the pruning.  eos = 0: the last selection's order.
+ *   weight 0, bonus 0 and a table without -inf reproduce ccd_ctc_beam_search bit for bit; weight 0 with -inf entries is a hard
+ *   character-set constraint.  A score is comparable with ccd_ctc_beam_search's and ccd_ctc_lexicon_score's only after Lambda (and the
+ *   eos term) is subtracted.
+ * No atomics, no workspace: the same input gives the same bits.  batch == 0 is a no-op.  CCD_EINVAL: a missing pointer (lm included), a
+ * negative size or stride; CCD_ESHAPE: everything ccd_ctc_beam_search refuses, order outside 1..CCD_CTC_LM_MAX_ORDER, eos not 0 or 1, a
+ * weight or bonus that is not finite.  Nothing is launched on an error. */
+#define CCD_CTC_LM_MAX_ORDER 3
+int ccd_ctc_beam_search_lm(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
+                           int beam, const float* lm, int order, float weight, float bonus, int eos,
+                           int* paths, int* lengths, float* hyp_scores, void* stream);
 
 /* Lexicon-constrained decoding of the CTC head (ABI 23; kernels/ctc_lexicon.h, restated in numpy in tests/ctc_lexicon_np.py): of THESE
  * words, which is the most probable given the frames, and how probable is each.

@@ -70,6 +70,11 @@ def main():
                     help="beam search of this width, 1..16, for either head (CTC: prefix beam search; NRTR: beam over the decoder); 0: greedy decoding")
     ap.add_argument("--lexicon", type=str, default=None,
                     help="evaluate the CTC head with lexicon-constrained decoding over this UTF-8 word list (one word per line); excludes a beam")
+    ap.add_argument("--lm", type=str, default=None,
+                    help="fuse a character n-gram language model into the CTC beam search: an .npz of CharNGram.save, or a UTF-8 word list "
+                         "(estimated at decoder.lm_order); needs a beam, excludes a lexicon")
+    ap.add_argument("--lm_weight", type=float, default=None, help="weight of the language model's log-probabilities (default 1.0)")
+    ap.add_argument("--lm_bonus", type=float, default=None, help="added per decoded character (default 0.0)")
     a = ap.parse_args()
     config = Config(a.config)
     if a.checkpoint is not None:
@@ -82,6 +87,9 @@ def main():
         config.decoder_beam_width = a.beam_width
     if a.lexicon is not None:
         config.decoder_lexicon = a.lexicon
+    for key in ("lm", "lm_weight", "lm_bonus"):
+        if getattr(a, key) is not None:
+            setattr(config, f"decoder_{key}", getattr(a, key))
     Logger.init(config.global_workdir, config.global_name, "test")
     utils.fix_random_seeds(int(config.global_seed or 0))
     logging.info("Construct dataset.")
@@ -91,6 +99,9 @@ def main():
     model = DINO_Finetune(config).to(device)
     if getattr(model.label_convertor, "lexicon_stats", None):
         logging.info(f"lexicon {config.decoder_lexicon}: {model.label_convertor.lexicon_stats}")
+    if getattr(model.label_convertor, "lm_stats", None):
+        conv = model.label_convertor
+        logging.info(f"language model {config.decoder_lm}: {conv.lm_stats}, weight {conv.lm_weight}, bonus {conv.lm_bonus}, eos {conv.lm_eos}")
     model.ensure_arena()
     model = DataParallel(model)
     if config.model_checkpoint:

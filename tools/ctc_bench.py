@@ -19,6 +19,10 @@ default the first three):
           yardstick in the same process: ccd_ctc_loss_fwd on the pairs of a 64-word slice with replicated rows (a 537 MB buffer), as
           time per pair; then evaluation images/s at B = 512, vit_small, greedy against a 1000-word lexicon.
     python tools/ctc_bench.py --cases lexicon --out profiles/ctc_lexicon.json
+  lm      ccd_ctc_beam_search_lm (kernels/ctc_beam.h: ctc_beam_kernel<true>) on the same probabilities with random normalised tables of
+          order 2 (34 KB) and 3 (3.1 MB), weight 0.5, bonus 0.8, eos on, beam widths 1, 4, 8, 16; ccd_ctc_beam_search at the same
+          widths in the same process and the same rounds is the thing to compare with.
+    python tools/ctc_bench.py --cases lm --out profiles/ctc_beam_lm.json
 Warm-up first, HIP events around every timed call, a figure is the median of the round medians with the lowest and highest
 round.  No threshold is set; the file records what was measured.  `--case NAME` runs one case and prints its JSON line."""
 import argparse
@@ -32,7 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 B, T, C = 512, 32, 92
-LIMITS = {"loss": 240, "step": 420, "infer": 300, "beam": 300, "lexicon": 420}           # seconds per case
+LIMITS = {"loss": 240, "step": 420, "infer": 300, "beam": 300, "lexicon": 420, "lm": 240}           # seconds per case
 # word length -> share in per cent of a lexicon of `lexicon`: the shape of an English word list (mode 5 - 7 characters, a tail to 15)
 LEXICON_LENGTHS = {2: 2, 3: 6, 4: 11, 5: 14, 6: 15, 7: 14, 8: 12, 9: 9, 10: 7, 11: 4, 12: 3, 13: 1, 14: 1, 15: 1}
 
@@ -301,7 +305,36 @@ def case_lexicon(a):
     return out
 
 
-CASES = {"loss": case_loss, "step": case_step, "infer": case_infer, "beam": case_beam, "lexicon": case_lexicon}
+def case_lm(a):
+    import torch
+    from ccd_amd import ops
+    probs = _peaked_probs(5)
+    g = torch.Generator().manual_seed(9)
+    lms = {order: ops.ctc_char_lm((1.5 * torch.randn(C ** (order - 1), C, generator=g)).log_softmax(-1), order) for order in (2, 3)}
+    widths = (1, 4, 8, 16)
+    out = {"shape": [B, T, C], "input": "fp32 probabilities, normalized = 1", "weight": 0.5, "bonus": 0.8, "eos": 1,
+           "table_bytes": {f"order{o}": int(lm.table.numel() * 4) for o, lm in lms.items()}}
+    plain = {w: [] for w in widths}
+    fused = {(o, w): [] for o in lms for w in widths}
+    for _ in range(a.rounds):
+        for w in widths:
+            plain[w].append(event_ms(lambda: ops.ctc_beam_search(probs, w, normalized=True), a.iters))
+            for o, lm in lms.items():
+                fused[o, w].append(event_ms(lambda: ops.ctc_beam_search_lm(probs, w, lm, 0.5, 0.8, True, normalized=True), a.iters))
+    for w in widths:
+        out[f"ctc_beam_search_w{w}"] = summary(plain[w])
+        for o in lms:
+            r = summary(fused[o, w])
+            out[f"ctc_beam_search_lm_order{o}_w{w}"] = {**r, "over_plain": round(r["median_ms"] / out[f"ctc_beam_search_w{w}"]["median_ms"], 3)}
+    best = ops.ctc_beam_search(probs, 16, normalized=True)
+    for o, lm in lms.items():
+        with_lm = ops.ctc_beam_search_lm(probs, 16, lm, 0.5, 0.8, True, normalized=True)
+        same = ((best[0][:, 0] == with_lm[0][:, 0]).all(1) & (best[1][:, 0] == with_lm[1][:, 0])).sum()
+        out[f"samples_whose_best_word_at_w16_changes_with_the_order{o}_table"] = int(B - same)
+    return out
+
+
+CASES = {"loss": case_loss, "step": case_step, "infer": case_infer, "beam": case_beam, "lexicon": case_lexicon, "lm": case_lm}
 
 
 def main():

@@ -123,6 +123,9 @@ def main(config):
     model = DINO_Finetune(config).to(device)
     if getattr(model.label_convertor, "lexicon_stats", None):
         logging.info(f"lexicon {config.decoder_lexicon}: {model.label_convertor.lexicon_stats}")
+    if getattr(model.label_convertor, "lm_stats", None):
+        conv = model.label_convertor
+        logging.info(f"language model {config.decoder_lm}: {conv.lm_stats}, weight {conv.lm_weight}, bonus {conv.lm_bonus}, eos {conv.lm_eos}")
     model.ensure_arena()
     model = DataParallel(model)                          # `module.` key prefix like nn.DataParallel; reducer when world > 1
     model.train()
@@ -212,12 +215,20 @@ def _parse_arguments():
                         help="evaluate with beam search of this width, 1..16, for either head (CTC: prefix beam search; NRTR: beam over the decoder); 0: greedy")
     parser.add_argument("--lexicon", type=str, default=None,
                         help="evaluate the CTC head with lexicon-constrained decoding over this UTF-8 word list (one word per line); excludes a beam")
+    parser.add_argument("--lm", type=str, default=None,
+                        help="evaluate the CTC head with a character n-gram language model fused into the beam search: an .npz of CharNGram.save, "
+                             "or a UTF-8 word list (estimated at decoder.lm_order); needs a beam, excludes a lexicon")
+    parser.add_argument("--lm_weight", type=float, default=None, help="weight of the language model's log-probabilities (default 1.0)")
+    parser.add_argument("--lm_bonus", type=float, default=None, help="added per decoded character (default 0.0)")
     args, _ = parser.parse_known_args()
     config = Config(args.config)
     if args.beam_width is not None:
         config.decoder_beam_width = args.beam_width
     if args.lexicon is not None:
         config.decoder_lexicon = args.lexicon
+    for key in ("lm", "lm_weight", "lm_bonus"):
+        if getattr(args, key) is not None:
+            setattr(config, f"decoder_{key}", getattr(args, key))
     return config
 
 
