@@ -161,6 +161,12 @@ class AttnConvertor:
                 np.concatenate([np.full((1, t.shape[1]), -1, dtype=np.int32), t]) for t in tables)
         return self._path_score_table
 
+    def tensor2align(self, *args, **kwargs):
+        raise NotImplementedError("AttnConvertor: forced alignment (tensor2align / tensor2chars) is for the CTC head only - the NRTR "
+                                  "decoder has no frame axis to align a word against (use decoder.type: 'CTCDecoder')")
+
+    tensor2chars = tensor2align
+
     @torch.no_grad()
     def tensor2idx(self, outputs, img_metas=None):
         """[N, T, C] class scores -> (class indices, softmax confidences) per sample: positions up to the first <EOS>,

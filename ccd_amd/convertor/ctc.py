@@ -20,8 +20,14 @@ An `lm` (a char_lm.CharNGram, the path of an .npz it saved, or the path of a UTF
 character n-gram language model into the beam search (ops.ctc_beam_search_lm): where words are scored (TextAccuracy) and in
 `tensor2nbest` every extension by a character adds lm_weight * log P(character | context) + lm_bonus, and with `lm_eos` the end of the
 word adds lm_weight * log P(end | context) behind the last frame.  An LM needs beam_width >= 1 and excludes a lexicon.
+
+`tensor2align` / `tensor2chars` say WHERE the characters of a word sit and how sure the network is of each: the best single alignment
+(ops.ctc_align) of given transcriptions, or of the word(s) the convertor's own configuration decodes - greedy, beam, LM-fused beam or
+lexicon alike, so the per-character confidences of the four decoders are comparable numbers.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -260,3 +266,98 @@ class CTCConvertor:
         words, lengths = self.lexicon.words, self.lexicon.lengths
         indexes = [[words[v, :lengths[v]].tolist() for v in row if v >= 0] for row in ids.tolist()]
         return indexes, best.cpu(), ids
+
+    # ------------------------------------------------------------------ alignment
+    @torch.no_grad()
+    def tensor2align(self, outputs, words=None, nbest=1, normalized=True):
+        """[N, T, C] frame scores on the device - probabilities (normalized=True: what CTCDecoder.forward_test returns) or logits -> the
+        best single alignment (ops.ctc_align) of `nbest` words per sample, a dict of device tensors with N * nbest rows, row
+        i * nbest + r = rank r of sample i: 'targets' int64 [rows, Lmax] zero-padded, 'frame_char' int32 [rows, T], 'spans' int32
+        [rows, Lmax, 2], 'char_logp' fp32 [rows, Lmax], 'score' fp32 [rows], 'rows' int32 [rows] (the sample of every row; -1 where a
+        slot holds no word - fewer hypotheses than nbest, a word of more than 31 classes - and the row is padding with score -inf).
+        words: a list of N strings, encoded as targets are - the forced alignment of those transcriptions (nbest must be 1).
+        words=None: the word(s) the convertor's configuration decodes - the greedy word at beam_width 0, the beam's `nbest` best
+        otherwise (LM-fused if an LM is set), the lexicon's `nbest` best if a lexicon is set - aligned against one copy of the scores;
+        nothing in this case synchronises with the host."""
+        from .. import ops
+        scores = outputs.float()
+        N, T = scores.shape[0], scores.shape[1]
+        k = int(nbest)
+        sample = torch.arange(N, dtype=torch.int32, device=scores.device)
+        if words is not None:
+            if k != 1 or not isinstance(words, list) or len(words) != N:
+                raise ValueError(f"tensor2align: words must be a list of one string per sample ({N}) and nbest 1, got "
+                                 f"{len(words) if isinstance(words, list) else type(words).__name__} and nbest {nbest}")
+            targets = self.str2tensor(words)[:, :ops.CTC_MAX_LABELS].contiguous().to(scores.device)
+            rows = sample
+        elif self.lexicon is not None:
+            if not 1 <= k <= ops.CTC_LEXICON_MAX_NBEST:
+                raise ValueError(f"tensor2align: nbest must lie in 1..{ops.CTC_LEXICON_MAX_NBEST}, got {nbest}")
+            index, _ = ops.ctc_lexicon_best(ops.ctc_lexicon_score(scores, self.lexicon, normalized=normalized), k)
+            table = self.lexicon.on(scores.device)[0]
+            if table.shape[0]:
+                targets = table[index.long().clamp(min=0).flatten()]
+            else:
+                targets = torch.zeros((N * k, 1), dtype=torch.int64, device=scores.device)
+            rows = torch.where(index >= 0, sample[:, None], -1).flatten()
+        elif self.beam_width > 0:
+            if not 1 <= k <= self.beam_width:
+                raise ValueError(f"tensor2align: nbest must lie in 1..beam_width = {self.beam_width}, got {nbest}")
+            if self.lm is not None:
+                paths, lengths, _ = ops.ctc_beam_search_lm(scores, self.beam_width, self.lm, self.lm_weight, self.lm_bonus, self.lm_eos,
+                                                           normalized=normalized)
+            else:
+                paths, lengths, _ = ops.ctc_beam_search(scores, self.beam_width, normalized=normalized)
+            lengths = lengths[:, :k]
+            targets = ops.ctc_paths_to_targets(paths[:, :k]).flatten(0, 1)
+            rows = torch.where((lengths >= 0) & (lengths <= ops.CTC_MAX_LABELS), sample[:, None], -1).flatten()
+        else:
+            if k != 1:
+                raise ValueError(f"tensor2align: greedy decoding (beam_width 0, no lexicon) has one word per sample, got nbest {nbest}")
+            path, length, _ = ops.ctc_greedy(scores)
+            targets = ops.ctc_paths_to_targets(path)
+            rows = torch.where(length <= ops.CTC_MAX_LABELS, sample, -1)
+        rows = rows.to(torch.int32).contiguous()
+        frame_char, spans, char_logp, score = ops.ctc_align(scores, targets.contiguous(), normalized=normalized, rows=rows)
+        return {"targets": targets, "frame_char": frame_char, "spans": spans, "char_logp": char_logp, "score": score, "rows": rows}
+
+    @torch.no_grad()
+    def tensor2chars(self, outputs, words=None, nbest=1, normalized=True, image_width=128, boxes="emission"):
+        """The host-side view of tensor2align (same arguments): per sample a list of up to `nbest` entries (word, log_prob, chars), best
+        first, where log_prob is the log-probability of the word's best alignment and chars holds one (char, x0, x1, first_frame,
+        last_frame, conf) per character: x0 = first * image_width / T, x1 = (last + 1) * image_width / T, and conf = exp(char_logp /
+        n_frames), the geometric mean of the frame probabilities of the character.  A slot without a word or without an alignment
+        gives no entry.
+        boxes='emission' (the default): the span is where the network EMITS the character.  CTC is peaky - a character is often
+        emitted on a single frame, somewhere inside its glyph - so this is NOT the character's inked extent.
+        boxes='cells': every span is widened to the midpoints of the blank gaps to its neighbours, and to the image edges at the ends
+        of the word; the cells tile the width (a segmentation of the line into characters, still no ink boxes)."""
+        if boxes not in ("emission", "cells"):
+            raise ValueError(f"tensor2chars: boxes must be 'emission' or 'cells', got {boxes!r}")
+        res = self.tensor2align(outputs, words=words, nbest=nbest, normalized=normalized)
+        N, T = outputs.shape[0], outputs.shape[1]
+        packed = torch.cat([res["targets"].float(), res["spans"].flatten(1).float(), res["char_logp"], res["score"][:, None],
+                            res["rows"][:, None].float()], dim=1).cpu().numpy()              # ONE device-to-host copy
+        return self.chars_of(packed, N, T, res["targets"].shape[1], image_width=image_width, boxes=boxes)
+
+    def chars_of(self, packed, N, T, Lmax, image_width=128, boxes="emission"):
+        """The host half of tensor2chars: `packed` is the numpy array [rows, 4 * Lmax + 2] of (targets, spans, char_logp, score, rows)."""
+        k = packed.shape[0] // max(N, 1)
+        out = [[] for _ in range(N)]
+        scale, table = float(image_width) / float(T), self.idx2char
+        for n, rec in enumerate(packed.tolist()):                              # plain lists: no numpy call per row
+            score, row = rec[4 * Lmax], int(rec[4 * Lmax + 1])
+            if row < 0 or score == float("-inf"):
+                continue
+            cls = [int(c) for c in rec[:Lmax]]
+            L = cls.index(0) if 0 in cls else Lmax
+            first = [int(rec[Lmax + 2 * j]) for j in range(L)]
+            last = [int(rec[Lmax + 2 * j + 1]) for j in range(L)]
+            lo, hi = [float(f) for f in first], [float(e + 1) for e in last]
+            if boxes == "cells" and L:
+                cuts = [(hi[j] + lo[j + 1]) / 2.0 for j in range(L - 1)]
+                lo, hi = [0.0] + cuts, cuts + [float(T)]
+            chars = [(table[cls[j]], lo[j] * scale, hi[j] * scale, first[j], last[j],
+                      math.exp(rec[3 * Lmax + j] / (last[j] - first[j] + 1))) for j in range(L)]
+            out[n // k].append(("".join(c[0] for c in chars), score, chars))
+        return out

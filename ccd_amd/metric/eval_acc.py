@@ -193,7 +193,9 @@ class TextAccuracy:
         return dict(zip(self._names, mets))
 
     @torch.no_grad()
-    def compute(self, model, dataloader):
+    def compute(self, model, dataloader, on_batch=None):
+        """on_batch(out_dec, gt_strings): called behind the scoring of every batch of a head whose decoder output is scored directly
+        (test.py --alignments); what it does is outside the timed span and changes nothing that is scored."""
         net = model.module if hasattr(model, "module") else model
         device = next(net.parameters()).device
         convertor = net.label_convertor
@@ -210,6 +212,8 @@ class TextAccuracy:
                     self.update_scores(out_dec.float(), list(label_tensors[0]), convertor)
                 span[1].record()
                 self._spans.append(span)                                      # read in result(), behind its copy
+                if on_batch is not None and not attn_beam:
+                    on_batch(out_dec.float(), list(label_tensors[0]))
             return self.result()
         for image_tensors, label_tensors in dataloader:
             image_tensors = image_tensors.to(device)
@@ -226,4 +230,6 @@ class TextAccuracy:
             pt_text = convertor.idx2str(label_indexes)
             self.inference_time += time.time() - start
             self.update(list(label_tensors[0]), pt_text)
+            if on_batch is not None and not attn_beam:
+                on_batch(out_dec.float(), list(label_tensors[0]))
         return self.result()

@@ -266,6 +266,17 @@ class DINO_Finetune(ArenaModule):
         feat = self.extract_feat(img)
         return self.decoder.forward_beam(feat, self.encoder(feat), beam_width)
 
+    @torch.no_grad()
+    def forward_chars(self, img, words=None, nbest=1):
+        """img [N,3,32,128] -> CTCConvertor.tensor2align of the CTC head's frame probabilities: the best single alignment - character
+        spans, per-character log-probabilities, the alignment's score - of `words` (a list of N transcriptions) or, words=None, of the
+        `nbest` word(s) the convertor's configuration decodes (greedy, beam, LM-fused beam, lexicon).  A dict of device tensors;
+        CTCConvertor.tensor2chars is the host-side view."""
+        if not self.ctc:
+            raise NotImplementedError("forward_chars is the CTC head's: the NRTR decoder has no frame axis to align a word against "
+                                      "(use decoder.type: 'CTCDecoder')")
+        return self.label_convertor.tensor2align(self.forward_test(img), words=words, nbest=nbest, normalized=True)
+
     def forward_test_speed(self, img):
         feat = self.extract_feat(img)
         if self.ctc:                                       # (one pass either way: nothing to stop early)

@@ -1081,6 +1081,46 @@ def ctc_lexicon_best(word_scores, nbest=1):
     return index, best
 
 
+# ------------------------------------------------------------------------------------------ forced alignment (kernels/ctc_align.h)
+def ctc_align(scores, targets, normalized=False, rows=None):
+    """The best single alignment of every target (kernels/ctc_align.h): scores fp32 [B, T, C] (any sample / step stride), logits or -
+    normalized=True - probabilities; targets int64 [N, Lmax] zero-padded (CTCConvertor.str2tensor's layout, Lmax in 1..CTC_MAX_LABELS);
+    rows int32 [N]: target n is aligned against sample rows[n] (None: N == B, target n against sample n)
+    -> (frame_char int32 [N, T]: the character index emitted at every frame, -1 for a blank frame; spans int32 [N, Lmax, 2]: first and
+    last frame of every character, -1 behind the word; char_logp fp32 [N, Lmax]: the summed frame log-probability of every character;
+    score fp32 [N]: the log-probability of the alignment).  An infeasible row (a class outside [1, C), more characters than frames, no
+    alignment of finite probability, a rows entry outside [0, B)) has score -inf and padding everywhere else."""
+    if scores.dim() != 3 or (scores.shape[2] > 1 and scores.stride(2) != 1):
+        raise ValueError(f"ctc_align: expects scores [B, T, C] with contiguous classes, got {list(scores.shape)}, strides {scores.stride()}")
+    B, T, C = scores.shape
+    if targets.dim() != 2 or not targets.is_contiguous():
+        raise ValueError(f"ctc_align: expects contiguous targets [N, Lmax], got {list(targets.shape)}")
+    N, Lmax = targets.shape
+    if not 1 <= Lmax <= CTC_MAX_LABELS:
+        raise ValueError(f"ctc_align: Lmax must lie in 1..{CTC_MAX_LABELS}, got {Lmax}")
+    if rows is None:
+        if N != B:
+            raise ValueError(f"ctc_align: without rows there is one target per sample, got {N} targets for {B} samples")
+    elif rows.dim() != 1 or rows.shape[0] != N or not rows.is_contiguous():
+        raise ValueError(f"ctc_align: expects contiguous rows [{N}], got {list(rows.shape)}")
+    frame_char = torch.empty((N, T), dtype=I32, device=scores.device)
+    spans = torch.empty((N, Lmax, 2), dtype=I32, device=scores.device)
+    char_logp = torch.empty((N, Lmax), dtype=F32, device=scores.device)
+    score = torch.empty(N, dtype=F32, device=scores.device)
+    _call("ccd_ctc_align", scores if B else None, scores.stride(0), scores.stride(1), B, T, C, 1 if normalized else 0, targets, N, Lmax, rows,
+          frame_char, spans, char_logp, score)
+    return frame_char, spans, char_logp, score
+
+
+def ctc_paths_to_targets(paths):
+    """The -1-padded int32 paths [..., T] that ctc_greedy, ctc_beam_search(_lm) and a lexicon gather return -> zero-padded int64 targets
+    [..., min(T, CTC_MAX_LABELS)] for ctc_align (a longer word is cut: it has no alignment anyway).  Tensor operations on the device,
+    no synchronisation."""
+    if paths.dim() < 1 or paths.dtype != I32:
+        raise ValueError(f"ctc_paths_to_targets: expects int32 paths [..., T], got {str(paths.dtype)[6:]} {list(paths.shape)}")
+    return paths[..., :CTC_MAX_LABELS].clamp(min=0).to(I64).contiguous()
+
+
 # ------------------------------------------------------------------------------------------ NRTR beam search (kernels/nrtr_beam.h)
 NRTR_MAX_BEAM = 16                                        # ccd_hip.h: CCD_NRTR_MAX_BEAM
 NRTR_UNUSED, NRTR_LIVE, NRTR_FINISHED = 0, 1, 2           # ccd_hip.h: CCD_NRTR_UNUSED ..

@@ -546,6 +546,40 @@ int ccd_ctc_lexicon_score(const float* scores, long sample_stride, long step_str
                           float* out, long ld_out, void* stream);
 int ccd_ctc_lexicon_best(const float* word_scores, long ld, int batch, int cols, int nbest, int* index, float* best, void* stream);
 
+/* CTC forced alignment (ABI 25; kernels/ctc_align.h, restated in numpy in tests/ctc_align_np.py): the best SINGLE alignment of a given
+ * word over the frames - the Viterbi / max-plus twin of ccd_ctc_loss_fwd's sum - WHERE its characters sit and how sure the network is of
+ * each.  One wavefront per target row, lane s = state s of (blank, l_1, blank, ..., l_L, blank), S = 2 L + 1 <= 63.
+ *   scores      fp32 [batch, steps, classes] with sample / step strides in elements, class 0 the blank; logits (normalized = 0) or
+ *               probabilities (normalized = 1).  The frame log-probabilities lp are exactly those of ccd_ctc_beam_search (fp64 over the
+ *               fp32 row, the sum over the classes in ascending order; a zero probability or a -inf logit masks a class): an alignment
+ *               score is comparable with a beam, a lexicon and a loss number of the same word, and never above them.
+ *   targets     int64 [n_rows, max_len], zero-padded (ccd_ctc_loss_fwd's layout): the length L is the number of leading non-zero
+ *               entries, found on the device.  An all-zero row is the empty word: every frame blank, score = sum lp[t, 0].
+ *   rows        optional int32 [n_rows]: row n is aligned against sample rows[n] - the W hypotheses of a beam or the k best words of a
+ *               lexicon against one copy of the scores.  NULL: n_rows == batch (CCD_EINVAL otherwise), row n goes with sample n.  An
+ *               entry outside [0, batch) makes its row infeasible; it is never used as an index.
+ *   Recursion   v_0(s) = lp[0, l'_s] for s < 2, -inf behind; v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2) where the loss allows
+ *               that skip) + lp[t, l'_s], in fp64.
+ *   Tie rule    (part of the contract: it makes the integers reproducible) the candidates are taken in the order s, s - 1, s - 2 and a
+ *               later one replaces the current one only if it is STRICTLY greater; the path ends in state S - 1 unless v(S - 2) is
+ *               strictly greater.  With all frames uniform the word `ab` over five frames aligns as a b _ _ _.
+ *   frame_char  int32 [n_rows, steps]: the index j of the character emitted at frame t, -1 for a blank frame.
+ *   spans       int32 [n_rows, max_len, 2]: first and last frame (inclusive) of character j; -1, -1 for j >= L.  A span is where the
+ *               network EMITS the character - CTC is peaky, often one frame -, not the character's inked extent.
+ *   char_logp   fp32 [n_rows, max_len]: the sum of lp over the character's frames, added in ascending frame order in fp64; 0 for j >= L.
+ *   score       fp32 [n_rows]: the log-probability of the best alignment = the sum of lp over all frames of that path, in frame order.
+ *   Infeasible  a label outside [1, classes) (never used as an index), L + adjacent equal labels > steps, no alignment of finite
+ *               probability, a bad rows entry: score = -inf, frame_char and spans -1, char_logp 0.
+ * No exp or log inside the recursion (logits; the emission of a probability takes its own log, off the dependent chain); backpointers
+ * are 2 bits per state and frame in two 64-bit registers of the state's lane: no workspace, no LDS.  No atomics: the same input gives
+ * the same bits.  n_rows == 0 is a no-op.  CCD_EINVAL: a missing pointer (scores may be
+ * NULL only with batch == 0), a negative size or stride, rows == NULL with n_rows != batch; CCD_ESHAPE: steps outside
+ * 1..CCD_CTC_MAX_STEPS, classes outside 1..CCD_CTC_MAX_CLASSES, max_len outside 1..CCD_CTC_MAX_LABELS, normalized not 0 or 1.  Nothing
+ * is launched on an error. */
+int ccd_ctc_align(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
+                  const int64_t* targets, int n_rows, int max_len, const int* rows, int* frame_char, int* spans, float* char_logp,
+                  float* score, void* stream);
+
 /* Beam search over the NRTR attention decoder (ABI 22; kernels/nrtr_beam.h, restated in numpy in tests/nrtr_beam_np.py).  The decode
  * loop (finetune_engine.beam_decode) runs the incremental decoder on batch * beam rows, row b * beam + r = slot r of sample b, and calls
  * these two at the end of every step.

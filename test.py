@@ -8,6 +8,7 @@ published ARD / STD files store them), evaluates every entry of `dataset.test.ro
 reference's report: one line per dataset (word_num, accuracy = cwr) and the word-weighted total.
 """
 import argparse
+import json
 import logging
 import os
 
@@ -41,7 +42,26 @@ def get_test_loaders(config):
     return loaders
 
 
-def evaluate(model, loaders, config, names=None):
+def alignment_writer(convertor, out, name, image_width=128):
+    """The per-batch hook of --alignments: one JSON line per image - ground truth, the predicted word (what the convertor's
+    configuration decodes: greedy, beam, LM-fused beam or lexicon), the log-probability of its best alignment and its characters with
+    x0, x1 (pixels of the crop), first and last frame and conf.  A character's span is where the network EMITS it, not its inked
+    extent.  One device-to-host copy per batch (CTCConvertor.tensor2chars); `pred` is null where the decoder returned no word that
+    can be aligned."""
+    count = [0]
+
+    def write(probs, gts):
+        for gt, entries in zip(gts, convertor.tensor2chars(probs, nbest=1, normalized=True, image_width=image_width)):
+            word, log_prob, chars = entries[0] if entries else (None, None, [])
+            out.write(json.dumps({"dataset": name, "index": count[0], "gt": gt, "pred": word, "log_prob": log_prob,
+                                  "chars": [dict(zip(("char", "x0", "x1", "first", "last", "conf"), c)) for c in chars]},
+                                 ensure_ascii=False) + "\n")
+            count[0] += 1
+    return write
+
+
+def evaluate(model, loaders, config, names=None, alignments=None):
+    """alignments: a text file open for writing (--alignments); None: nothing but the accuracy run."""
     names = names or EVAL_DATA_NAMES
     words = acc = 0.0
     report, results = "", []
@@ -50,11 +70,16 @@ def evaluate(model, loaders, config, names=None):
         for i, loader in enumerate(loaders):
             metric = TextAccuracy(charset_path=config.dataset_charset_path, case_sensitive=bool(config.dataset_eval_case_sensitive),
                                   model_eval="vision")
-            res = metric.compute(model, loader)
+            name = names[i] if i < len(names) else f"dataset{i}"
+            if alignments is None:
+                res = metric.compute(model, loader)
+            else:
+                net = model.module if hasattr(model, "module") else model
+                res = metric.compute(model, loader, on_batch=alignment_writer(
+                    net.label_convertor, alignments, name, image_width=int(config.dataset_image_width or 128)))
             results.append(res)
             acc += res["cwr"] * res["words"]
             words += res["words"]
-            name = names[i] if i < len(names) else f"dataset{i}"
             report += f"dataset: {name} --> word_num: {res['words']} --> accuracy: {res['cwr']:0.3f}\n"
     report += f"total_accuracy: {acc / max(words, 1.0):0.3f}"
     return report, results
@@ -75,6 +100,9 @@ def main():
                          "(estimated at decoder.lm_order); needs a beam, excludes a lexicon")
     ap.add_argument("--lm_weight", type=float, default=None, help="weight of the language model's log-probabilities (default 1.0)")
     ap.add_argument("--lm_bonus", type=float, default=None, help="added per decoded character (default 0.0)")
+    ap.add_argument("--alignments", type=str, default=None, metavar="PATH",
+                    help="next to the accuracy run write one JSON line per image to PATH - ground truth, predicted word, the log-probability of "
+                         "its best alignment, and per character x0, x1, first / last frame and confidence (the CTC head only)")
     a = ap.parse_args()
     config = Config(a.config)
     if a.checkpoint is not None:
@@ -110,7 +138,13 @@ def main():
         model.load_state_dict(sd["net"])
         model.module.ensure_arena()
     logging.info("eval model")
-    report, _ = evaluate(model, loaders, config)
+    if a.alignments is not None:
+        if not model.module.ctc:
+            raise NotImplementedError("--alignments is for the CTC head only: the NRTR decoder has no frame axis to align a word against")
+        with open(a.alignments, "w", encoding="utf-8") as f:
+            report, _ = evaluate(model, loaders, config, alignments=f)
+    else:
+        report, _ = evaluate(model, loaders, config)
     print("-" * 80)
     print(report + "\n")
 

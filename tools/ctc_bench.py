@@ -23,6 +23,12 @@ default the first three):
           order 2 (34 KB) and 3 (3.1 MB), weight 0.5, bonus 0.8, eos on, beam widths 1, 4, 8, 16; ccd_ctc_beam_search at the same
           widths in the same process and the same rounds is the thing to compare with.
     python tools/ctc_bench.py --cases lm --out profiles/ctc_beam_lm.json
+  align   ccd_ctc_align (kernels/ctc_align.h) at B = 512, T = 32, C = 92, words of 2..15 characters, on logits in a 128-wide buffer;
+          ccd_ctc_loss_fwd (the yardstick: the same lane mapping, a strictly heavier recursion) and ccd_ctc_greedy in the same process
+          on the same buffer; the same kernel on the fp32 softmax (normalized = 1) and with `rows` mapping 8 targets to every sample;
+          then evaluation images/s at B = 512, vit_small: forward + TextAccuracy.update_scores, without and with what test.py
+          --alignments adds per batch (CTCConvertor.tensor2chars: decode, align, one copy to the host, the host-side records).
+    python tools/ctc_bench.py --cases align --out profiles/ctc_align.json
 Warm-up first, HIP events around every timed call, a figure is the median of the round medians with the lowest and highest
 round.  No threshold is set; the file records what was measured.  `--case NAME` runs one case and prints its JSON line."""
 import argparse
@@ -36,7 +42,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 B, T, C = 512, 32, 92
-LIMITS = {"loss": 240, "step": 420, "infer": 300, "beam": 300, "lexicon": 420, "lm": 240}           # seconds per case
+LIMITS = {"loss": 240, "step": 420, "infer": 300, "beam": 300, "lexicon": 420, "lm": 240, "align": 300}           # seconds per case
 # word length -> share in per cent of a lexicon of `lexicon`: the shape of an English word list (mode 5 - 7 characters, a tail to 15)
 LEXICON_LENGTHS = {2: 2, 3: 6, 4: 11, 5: 14, 6: 15, 7: 14, 8: 12, 9: 9, 10: 7, 11: 4, 12: 3, 13: 1, 14: 1, 15: 1}
 
@@ -334,7 +340,77 @@ def case_lm(a):
     return out
 
 
-CASES = {"loss": case_loss, "step": case_step, "infer": case_infer, "beam": case_beam, "lexicon": case_lexicon, "lm": case_lm}
+def case_align(a):
+    import numpy as np
+    import torch
+    from ccd_amd import finetune as ft, ops
+    from ccd_amd.convertor.ctc import CTCConvertor
+    from ccd_amd.metric.eval_acc import TextAccuracy
+    dev = torch.device("cuda")
+    conv = CTCConvertor()
+    rs = np.random.RandomState(1)
+    K = 8
+    strings = ["".join(conv.idx2char[1 + c] for c in rs.randint(0, 90, size=int(rs.randint(2, 16)))) for _ in range(B * K)]
+    many = conv.str2tensor(strings)[:, :15].contiguous().to(dev)               # 8 targets per sample
+    targets = many[::K].contiguous()                                           # one per sample
+    rows = torch.arange(B, dtype=torch.int32).repeat_interleave(K).to(dev)
+    g = torch.Generator().manual_seed(2)
+    buf = torch.zeros(B * T, 128)
+    buf[:, :C] = torch.randn(B * T, C, generator=g) * 2.0
+    pbuf = torch.zeros(B * T, 128)
+    pbuf[:, :C] = buf[:, :C].softmax(-1)
+    buf, pbuf = buf.to(dev), pbuf.to(dev)
+    logits, probs = buf.view(B, T, 128)[:, :, :C], pbuf.view(B, T, 128)[:, :, :C]
+    # max <= sum before anything is timed
+    score = ops.ctc_align(logits, targets)[3]
+    nll = ops.ctc_loss_fwd(buf, C, targets, T)[0]
+    out = {"shape": [B, T, C], "words": "2..15 characters", "largest_score_plus_nll": float((score + nll).max()),
+           "rows_equal_replicated": bool(torch.equal(ops.ctc_align(logits, many, rows=rows)[3][::K], score))}
+    assert out["largest_score_plus_nll"] <= 1e-4 and out["rows_equal_replicated"]
+    sides = {"ctc_align_logits": lambda: ops.ctc_align(logits, targets),
+             "ctc_loss_fwd_same_rows": lambda: ops.ctc_loss_fwd(buf, C, targets, T),
+             "ctc_greedy_same_buffer": lambda: ops.ctc_greedy(logits),
+             "ctc_align_probabilities": lambda: ops.ctc_align(probs, targets, normalized=True),
+             "ctc_align_rows_8_per_sample": lambda: ops.ctc_align(probs, many, normalized=True, rows=rows)}
+    rounds = {name: [] for name in sides}
+    for _ in range(a.rounds):
+        for name, fn in sides.items():
+            rounds[name].append(event_ms(fn, a.iters))
+    for name in sides:
+        out[name] = summary(rounds[name])
+    out["loss_fwd_over_align"] = round(out["ctc_loss_fwd_same_rows"]["median_ms"] / out["ctc_align_logits"]["median_ms"], 2)
+    out["align_faster_than_loss_fwd_beyond_spread"] = out["ctc_align_logits"]["highest_ms"] < out["ctc_loss_fwd_same_rows"]["lowest_ms"]
+    out["rows_8_ns_per_target"] = round(out["ctc_align_rows_8_per_sample"]["median_ms"] * 1e6 / (B * K), 1)
+    # evaluation: forward + scoring, the body of TextAccuracy.compute, without and with the hook of test.py --alignments
+    torch.manual_seed(0)
+    cfg = ft.FinetuneConfig()
+    cfg.decoder_type = "CTCDecoder"
+    model = ft.build_model(cfg, dev, dropout=0.0).eval()
+    conv = model.label_convertor
+    img = torch.randn(B, 3, 32, 128, generator=torch.Generator().manual_seed(4)).to(dev)
+    words = ["".join(conv.idx2char[1 + (i * 7 + j) % 90] for j in range(3 + i % 13)) for i in range(B)]
+    metric = TextAccuracy()
+
+    def evaluate(alignments):
+        probs = model(img, text=None, return_loss=False, test_speed=False).float()
+        metric.update_scores(probs, words, conv)
+        if alignments:
+            conv.tensor2chars(probs, nbest=1, normalized=True)
+
+    ev = {False: [], True: []}
+    iters = max(3, a.iters // 3)
+    with torch.no_grad():
+        for _ in range(a.rounds):
+            for flag in ev:
+                ev[flag].append(event_ms(lambda: evaluate(flag), iters))
+    e0, e1 = summary(ev[False]), summary(ev[True])
+    out.update({"batch": B, "arch": "vit_small", "evaluate_greedy": e0, "evaluate_greedy_with_alignments": e1,
+                "greedy_images_per_s": round(B / (e0["median_ms"] * 1e-3)),
+                "with_alignments_images_per_s": round(B / (e1["median_ms"] * 1e-3))})
+    return out
+
+
+CASES = {"align": case_align, "loss": case_loss, "step": case_step, "infer": case_infer, "beam": case_beam, "lexicon": case_lexicon, "lm": case_lm}
 
 
 def main():
