@@ -47,12 +47,12 @@ class AttnConvertor:
     dicts = {name: tuple(chars) for name, chars in ALPHABETS.items()}      # same table name as the reference exposes
 
     def __init__(self, dict_type="DICT90", dict_file=None, dict_list=None, with_unknown=True, max_seq_len=40, lower=False,
-                 start_end_same=True, beam_width=0, lexicon=None, lm=None, **_ignored):
+                 start_end_same=True, beam_width=0, lexicon=None, lm=None, lexicon_beam=0, **_ignored):
         if lm is not None:
             raise NotImplementedError("AttnConvertor: language-model fusion is for the CTC head only - the NRTR decoder conditions every "
                                       "character on the ones before it already, and its beam takes no additive table term (use "
                                       "decoder.type: 'CTCDecoder')")
-        if lexicon is not None:
+        if lexicon is not None or lexicon_beam:
             raise NotImplementedError("AttnConvertor: lexicon-constrained decoding is for the CTC head only - the probability of a word "
                                       "under the NRTR decoder takes one teacher-forced decoder pass per word, not a closed-form "
                                       "recursion over the frames (use decoder.type: 'CTCDecoder')")

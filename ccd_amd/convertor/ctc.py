@@ -16,6 +16,11 @@ probability summed over all alignments (ops.ctc_lexicon_score / ops.ctc_lexicon_
 `<UKN>`); words of more than 31 classes and duplicates after encoding are dropped and counted in `lexicon_stats`.  A lexicon and a
 beam exclude each other.
 
+`lexicon_beam` = W in 1..16 makes the lexicon path a two-stage search instead of scoring every word: a beam of width W walks the
+lexicon's prefix tree (ops.ctc_lexicon_trie, built with the lexicon), and the handful of words it proposes are scored exactly
+(ops.ctc_lexicon_search).  The cost is a beam's whatever the size of the lexicon; the log-probabilities are the same exact numbers,
+and the answer is the exhaustive path's whenever its best word is among the proposals.  0, the default, scores every word.
+
 An `lm` (a char_lm.CharNGram, the path of an .npz it saved, or the path of a UTF-8 word list, which is estimated at `lm_order`) fuses a
 character n-gram language model into the beam search (ops.ctc_beam_search_lm): where words are scored (TextAccuracy) and in
 `tensor2nbest` every extension by a character adds lm_weight * log P(character | context) + lm_bonus, and with `lm_eos` the end of the
@@ -42,13 +47,13 @@ def is_ctc(convertor):
 
 
 class CTCConvertor:
-    """CTCConvertor(dict_type='DICT90', with_unknown=True, max_seq_len=25, lower=False, beam_width=0, lexicon=None, lm=None, lm_order=2,
-    lm_weight=1.0, lm_bonus=0.0, lm_eos=True) - see the module docstring."""
+    """CTCConvertor(dict_type='DICT90', with_unknown=True, max_seq_len=25, lower=False, beam_width=0, lexicon=None, lexicon_beam=0,
+    lm=None, lm_order=2, lm_weight=1.0, lm_bonus=0.0, lm_eos=True) - see the module docstring."""
 
     dicts = {name: tuple(chars) for name, chars in ALPHABETS.items()}
 
     def __init__(self, dict_type="DICT90", dict_file=None, dict_list=None, with_unknown=True, max_seq_len=25, lower=False, beam_width=0,
-                 lexicon=None, lm=None, lm_order=2, lm_weight=1.0, lm_bonus=0.0, lm_eos=True, **_ignored):
+                 lexicon=None, lexicon_beam=0, lm=None, lm_order=2, lm_weight=1.0, lm_bonus=0.0, lm_eos=True, **_ignored):
         if dict_file is not None:
             alphabet = _read_alphabet_file(dict_file)
         elif dict_list is not None:
@@ -74,9 +79,12 @@ class CTCConvertor:
         for cls, c in enumerate(alphabet, start=1):
             if len(c) == 1:
                 self._lut[ord(c)] = cls
-        self.lexicon, self.lexicon_words, self.lexicon_stats = None, None, None
+        self.lexicon, self.lexicon_words, self.lexicon_stats, self.lexicon_trie = None, None, None, None
+        self.lexicon_beam = self._checked_lexicon_beam(lexicon_beam)
         if lexicon is not None:
             self.set_lexicon(lexicon)
+        elif self.lexicon_beam > 0:
+            raise ValueError(f"lexicon_beam = {self.lexicon_beam} needs a lexicon: it is the width of the search over the lexicon's trie")
         self.lm, self.lm_model, self.lm_stats = None, None, None
         self.lm_order, self.lm_weight, self.lm_bonus, self.lm_eos = int(lm_order), float(lm_weight), float(lm_bonus), bool(lm_eos)
         if lm is not None:
@@ -117,13 +125,27 @@ class CTCConvertor:
         self.lm, self.lm_model, self.lm_order, self.lm_stats = handle, model, model.order, model.stats
         return self.lm_stats
 
-    def set_lexicon(self, strings_or_path):
+    @staticmethod
+    def _checked_lexicon_beam(beam):
+        from ..ops import CTC_MAX_BEAM
+        if isinstance(beam, bool) or int(beam) != beam or not 0 <= int(beam) <= CTC_MAX_BEAM:
+            raise ValueError(f"lexicon_beam must lie in 0..{CTC_MAX_BEAM} (0: every word of the lexicon is scored), got {beam!r}")
+        return int(beam)
+
+    def set_lexicon(self, strings_or_path, beam=None):
         """The closed vocabulary of tensor2lexicon and TextAccuracy: a list of words, or the path of a UTF-8 file with one word per line
         (empty lines skipped); None removes it.  Kept: `lexicon` (the ops.ctc_lexicon handle), `lexicon_words` (the kept strings, in
-        order: column v of the scores is lexicon_words[v]) and `lexicon_stats` = {'read', 'kept', 'too_long', 'duplicates'}."""
+        order: column v of the scores is lexicon_words[v]) and `lexicon_stats` = {'read', 'kept', 'too_long', 'duplicates'}.  beam
+        replaces lexicon_beam where given; with lexicon_beam > 0 the prefix tree is built here (`lexicon_trie`, the
+        ops.ctc_lexicon_trie handle) and lexicon_stats gains 'nodes'."""
         from .. import ops
+        if beam is not None:
+            beam = self._checked_lexicon_beam(beam)
         if strings_or_path is None:
-            self.lexicon, self.lexicon_words, self.lexicon_stats = None, None, None
+            if beam:
+                raise ValueError(f"lexicon_beam = {beam} needs a lexicon: it is the width of the search over the lexicon's trie")
+            self.lexicon, self.lexicon_words, self.lexicon_stats, self.lexicon_trie = None, None, None, None
+            self.lexicon_beam = 0
             return None
         if getattr(self, "lm", None) is not None:
             raise ValueError("a lexicon and a language model exclude each other: remove the language model (set_lm(None)) first")
@@ -154,6 +176,12 @@ class CTCConvertor:
         self.lexicon = ops.ctc_lexicon(torch.from_numpy(words))
         self.lexicon_words = kept
         self.lexicon_stats = {"read": len(strings), "kept": len(kept), "too_long": too_long, "duplicates": duplicates}
+        if beam is not None:
+            self.lexicon_beam = beam
+        self.lexicon_trie = None
+        if self.lexicon_beam > 0:
+            self.lexicon_trie = ops.ctc_lexicon_trie(self.lexicon)
+            self.lexicon_stats["nodes"] = self.lexicon_trie.n_nodes
         return self.lexicon_stats
 
     def num_classes(self):
@@ -245,27 +273,46 @@ class CTCConvertor:
         return nbest_lists("tensor2nbest", *ops.ctc_beam_search(outputs.float(), width, normalized=normalized), nbest)
 
     @torch.no_grad()
-    def tensor2lexicon(self, outputs, nbest=1, normalized=True, subset=None):
+    def tensor2lexicon(self, outputs, nbest=1, normalized=True, subset=None, beam=None):
         """[N, T, C] frame scores on the device - probabilities (normalized=True: what CTCDecoder.forward_test returns) or logits
         -> (indexes, log_probs, word_ids): the `nbest` most probable words of the lexicon, best first.  indexes[i] holds up to `nbest`
         index lists (fewer where fewer words have an alignment of finite probability); log_probs is a float tensor [N, nbest], the
         exact log of each word's probability summed over all alignments, -inf where a slot is empty; word_ids is an int64 tensor
         [N, nbest] of positions in `lexicon_words`, -1 where a slot is empty.  subset int32 [N, K] on the device restricts sample i
-        to the words subset[i] (negative entries are padding)."""
+        to the words subset[i] (negative entries are padding).  beam (default: lexicon_beam) > 0 searches the lexicon's trie with a
+        beam of that width and scores only the words it proposes (ops.ctc_lexicon_search; nbest <= beam) - the same exact
+        log-probabilities at a cost that does not grow with the lexicon; it excludes a subset."""
         from .. import ops
         if self.lexicon is None:
             raise ValueError("tensor2lexicon: the convertor has no lexicon (set_lexicon)")
-        scores = ops.ctc_lexicon_score(outputs.float(), self.lexicon, normalized=normalized, subset=subset)
-        if not 1 <= int(nbest) <= ops.CTC_LEXICON_MAX_NBEST:
-            raise ValueError(f"tensor2lexicon: nbest must lie in 1..{ops.CTC_LEXICON_MAX_NBEST}, got {nbest}")
-        index, best = ops.ctc_lexicon_best(scores, nbest)
-        ids = index.long()
-        if subset is not None and subset.shape[1]:
-            ids = torch.where(ids >= 0, subset.long().gather(1, ids.clamp(min=0)), ids)
-        ids = ids.cpu()
+        width = self.lexicon_beam if beam is None else self._checked_lexicon_beam(beam)
+        if width > 0:
+            if subset is not None:
+                raise ValueError("tensor2lexicon: a subset and a beam exclude each other - a per-image subset is small already, it is "
+                                 "scored exhaustively (pass beam=0)")
+            if not 1 <= int(nbest) <= width:
+                raise ValueError(f"tensor2lexicon: nbest must lie in 1..beam = {width}, got {nbest}")
+            ids, best = ops.ctc_lexicon_search(outputs.float(), self._trie(), width, nbest=nbest, normalized=normalized)
+            ids = ids.long().cpu()
+        else:
+            scores = ops.ctc_lexicon_score(outputs.float(), self.lexicon, normalized=normalized, subset=subset)
+            if not 1 <= int(nbest) <= ops.CTC_LEXICON_MAX_NBEST:
+                raise ValueError(f"tensor2lexicon: nbest must lie in 1..{ops.CTC_LEXICON_MAX_NBEST}, got {nbest}")
+            index, best = ops.ctc_lexicon_best(scores, nbest)
+            ids = index.long()
+            if subset is not None and subset.shape[1]:
+                ids = torch.where(ids >= 0, subset.long().gather(1, ids.clamp(min=0)), ids)
+            ids = ids.cpu()
         words, lengths = self.lexicon.words, self.lexicon.lengths
         indexes = [[words[v, :lengths[v]].tolist() for v in row if v >= 0] for row in ids.tolist()]
         return indexes, best.cpu(), ids
+
+    def _trie(self):
+        """The lexicon's prefix tree, built on first use where the convertor was configured without a lexicon_beam."""
+        from .. import ops
+        if self.lexicon_trie is None:
+            self.lexicon_trie = ops.ctc_lexicon_trie(self.lexicon)
+        return self.lexicon_trie
 
     # ------------------------------------------------------------------ alignment
     @torch.no_grad()
@@ -277,7 +324,8 @@ class CTCConvertor:
         slot holds no word - fewer hypotheses than nbest, a word of more than 31 classes - and the row is padding with score -inf).
         words: a list of N strings, encoded as targets are - the forced alignment of those transcriptions (nbest must be 1).
         words=None: the word(s) the convertor's configuration decodes - the greedy word at beam_width 0, the beam's `nbest` best
-        otherwise (LM-fused if an LM is set), the lexicon's `nbest` best if a lexicon is set - aligned against one copy of the scores;
+        otherwise (LM-fused if an LM is set), the lexicon's `nbest` best if a lexicon is set (those of the trie search with lexicon_beam
+        > 0) - aligned against one copy of the scores;
         nothing in this case synchronises with the host."""
         from .. import ops
         scores = outputs.float()
@@ -293,7 +341,12 @@ class CTCConvertor:
         elif self.lexicon is not None:
             if not 1 <= k <= ops.CTC_LEXICON_MAX_NBEST:
                 raise ValueError(f"tensor2align: nbest must lie in 1..{ops.CTC_LEXICON_MAX_NBEST}, got {nbest}")
-            index, _ = ops.ctc_lexicon_best(ops.ctc_lexicon_score(scores, self.lexicon, normalized=normalized), k)
+            if self.lexicon_beam > 0:                                        # the words the trie search picks
+                if k > self.lexicon_beam:
+                    raise ValueError(f"tensor2align: nbest must lie in 1..lexicon_beam = {self.lexicon_beam}, got {nbest}")
+                index, _ = ops.ctc_lexicon_search(scores, self._trie(), self.lexicon_beam, nbest=k, normalized=normalized)
+            else:
+                index, _ = ops.ctc_lexicon_best(ops.ctc_lexicon_score(scores, self.lexicon, normalized=normalized), k)
             table = self.lexicon.on(scores.device)[0]
             if table.shape[0]:
                 targets = table[index.long().clamp(min=0).flatten()]

@@ -27,8 +27,8 @@
 // same ascending-order sum as logits.  What the software fp64 exp / log and the W-fold rescan cost on the device: tools/ctc_bench.py,
 // case `beam`.
 //
-// Language-model fusion (ccd_ctc_beam_search_lm, ctc_beam_kernel<true>; tests/ctc_beam_lm_np.py is the specification): the same kernel -
-// `template <bool kLm>`, whose `false` instance is the code above and nothing else - with one additive term per extension from a character
+// Language-model fusion (ccd_ctc_beam_search_lm, ctc_beam_kernel<CTC_BEAM_LM>; tests/ctc_beam_lm_np.py is the specification): the same kernel -
+// `template <int kMode>`, whose CTC_BEAM_PLAIN instance is the code above and nothing else - with one additive term per extension from a character
 // n-gram table lm fp32 [C^(order-1), C]: the row of an entry is its last order - 1 classes (most recent last, 0 where the prefix is
 // shorter), column c >= 1 the log-probability of character c behind that context, column 0 that of the word ending there.
 //     g(i, c) = lm[row_i, c] == -inf ? -inf : (double)weight * (double)lm[row_i, c] + (double)bonus      (the product, then the sum)
@@ -44,6 +44,23 @@
 // LDS: 8 KB + 64 B per wave on top of the 4.2 KB above: 50 176 B = 49 KB per workgroup (17 152 B without a language model) - under the
 // 64 KB static limit, three workgroups per CU by LDS.  The 32 values in flight cost registers (176 VGPRs against 106: two waves per
 // SIMD), which a kernel of one wave per sample does not miss.
+//
+// Trie search over a lexicon (ccd_ctc_beam_search_trie, ctc_beam_kernel<CTC_BEAM_TRIE>; tests/ctc_trie_np.py is the specification): the
+// third instance.  The lexicon is a prefix tree, nodes int32 [n_nodes, 8] in breadth-first order (ccd_hip.h has the layout): every entry
+// carries the node of its prefix (the empty prefix: node 0), an extend candidate (i, c) exists iff bit c of the 128-bit child mask of
+// node_i is set - otherwise it is -inf: never selected, never merged - and scores exactly what the plain instance gives it.  Behind the
+// last frame an entry whose node ends no word is -inf, the entries are ranked again as the eos re-rank does (the code is shared), and
+// word_ids int32 [B, W] names the lexicon row of every hypothesis.  The cost is a beam's, whatever the size of the lexicon.
+// Where the table is read: the record of entry i - the mask as two 64-bit words, first_child, word_id, the node id - lives in LDS, 28 B
+// per entry, 448 B per wave.  The allowed test costs the scan nothing: `merged` of a frame starts as the complement of the mask instead
+// of zero, so an extension without an edge is `gone` like one that was merged away (bit 0, the stay, is not looked at).  The lane
+// that keeps the entry of rank r derives its node while the old entries still stand: the parent's node for a stay, first_child +
+// popcount(mask bits below c) for an extension, clamped to [0, n_nodes) so that no table, however malformed, makes an address
+// outside it.  It then requests the six words of that node's record into registers - one 24-byte load per entry and frame -
+// and stores them into LDS behind the next frame's log-softmax, as the language model's values are.  Mask bits of classes >= C are
+// never scanned (has0 / has1): such a word is unreachable, as it is -inf for ccd_ctc_lexicon_score.  The record of the last frame's
+// entries stays in registers: lane r reads the word id of entry r from there.
+// What it costs next to the plain instance and to scoring every word of the lexicon: tools/ctc_bench.py, case `trie`.
 #pragma once
 
 #include "beam_wave.h"
@@ -61,6 +78,8 @@ struct CtcBeamWave {
     unsigned char prefix[2][CTC_MAX_BEAM][CTC_MAX_T];            // extension this entry's stay candidate takes in, or -1
 };
 
+enum CtcBeamMode { CTC_BEAM_PLAIN = 0, CTC_BEAM_LM = 1, CTC_BEAM_TRIE = 2 };
+
 template <bool kLm>
 struct CtcBeamLmWave {};                                         // (nothing without a language model)
 template <>
@@ -74,6 +93,35 @@ struct CtcBeamLm {                                               // the language
     int order, eos;
     double weight, bonus;
 };
+
+template <bool kTrie>
+struct CtcBeamTrieWave {};                                       // (nothing without a lexicon trie)
+template <>
+struct CtcBeamTrieWave<true> {
+    unsigned long long allow[CTC_MAX_BEAM][2];                   // bit c & 63 of [i][c >> 6]: the node of entry i has a child by class c
+    int node[CTC_MAX_BEAM], first[CTC_MAX_BEAM], word[CTC_MAX_BEAM];     // the node of entry i, its first child, the word that ends there
+};
+
+struct CtcBeamTrie {                                             // the lexicon trie of a launch (unused without one)
+    const int* nodes;                                            // int32 [n_nodes, 8]: mask[4], first_child, word_id, parent, class
+    int n_nodes;
+    int* word_ids;                                               // int32 [B, W]
+};
+constexpr int CTC_TRIE_NODE_WORDS = 8, CTC_TRIE_RECORD = 6;      // words per node; those the kernel reads: the mask, first_child, word_id
+
+// The lanes below CTC_MAX_BEAM.  Requests the record of `node` (in [0, n_nodes)) into registers (consumed a frame later).
+__device__ __forceinline__ void ctc_trie_fetch(const int* __restrict__ nodes, int node, int (&r)[CTC_TRIE_RECORD]) {
+    const int* const p = nodes + (long)node * CTC_TRIE_NODE_WORDS;
+#pragma unroll
+    for (int k = 0; k < CTC_TRIE_RECORD; ++k) r[k] = p[k];
+}
+
+// The child of a node by class c (1 <= c < 128, its mask bit set): the children are contiguous in ascending class order.
+__device__ __forceinline__ int ctc_trie_child(int first, unsigned long long m0, unsigned long long m1, int c) {
+    const int below = c < 64 ? __builtin_popcountll(m0 & ((1ull << c) - 1ull))
+                             : __builtin_popcountll(m0) + __builtin_popcountll(m1 & ((1ull << (c - 64)) - 1ull));
+    return first + below;
+}
 
 // g of one table value: the fp64 product, then the fp64 sum; -inf stays -inf whatever the weight.
 __device__ __forceinline__ ctc_real ctc_lm_term(float v, double weight, double bonus) {
@@ -96,17 +144,23 @@ __device__ __forceinline__ void ctc_lm_fetch(const CtcBeamLmWave<true>& w, const
 
 // grid = ceil(B / CTC_WAVES).  The launcher has checked 1 <= W <= CTC_MAX_BEAM, 1 <= T <= CTC_MAX_T, 2 <= C <= CTC_MAX_C and, with a
 // language model (kLm; `lm` is not looked at without one), 1 <= order <= 3, eos in {0, 1}, weight and bonus finite; the table holds
-// C^(order-1) rows of C.  Every line the model adds sits behind `if constexpr (kLm)`: the `false` instance is the kernel as it was.
-template <bool kLm>
+// C^(order-1) rows of C.  Every line the model adds sits behind `if constexpr (kLm)`, every line the trie adds behind `if constexpr
+// (kTrie)` (`trie` is not looked at without one; with one the launcher has checked n_nodes >= 1): the CTC_BEAM_PLAIN instance is the
+// kernel as it was.
+template <int kMode>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __restrict__ scores, long sample_stride, long step_stride, int B,
                                                                int T, int C, int normalized, int W, int* __restrict__ paths,
-                                                               int* __restrict__ lengths, float* __restrict__ hyp_scores, CtcBeamLm lm) {
+                                                               int* __restrict__ lengths, float* __restrict__ hyp_scores, CtcBeamLm lm,
+                                                               CtcBeamTrie trie) {
+    constexpr bool kLm = kMode == CTC_BEAM_LM, kTrie = kMode == CTC_BEAM_TRIE;
     __shared__ CtcBeamWave waves[CTC_WAVES];
     __shared__ CtcBeamLmWave<kLm> tables[CTC_WAVES];
+    __shared__ CtcBeamTrieWave<kTrie> tries[CTC_WAVES];
     const int lane = lane_id(), b = blockIdx.x * CTC_WAVES + wave_id();
     if (b >= B) return;                                                    // (whole waves; no workgroup barrier below)
     CtcBeamWave& s = waves[wave_id()];
     CtcBeamLmWave<kLm>& m = tables[wave_id()];
+    CtcBeamTrieWave<kTrie>& tr = tries[wave_id()];
     const float* const x = scores + (long)b * sample_stride;
     const int c0 = lane, c1 = lane + 64;
     const bool has0 = c0 < C, has1 = c1 < C;
@@ -123,6 +177,10 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
     float next0 = has0 ? x[c0] : 0.f, next1 = has1 ? x[c1] : 0.f;
     float lmv[2 * CTC_MAX_BEAM];                                           // kLm: the table values requested for the next frame's entries
     if constexpr (kLm) ctc_lm_fetch(m, lm.table, C, n, c0, c1, has0, has1, lmv);
+    int rec[CTC_TRIE_RECORD] = {0, 0, 0, 0, 0, -1};                        // kTrie: the record requested for the next frame's entry `lane`
+    int rec_node = 0;                                                      // and its node: the root
+    if constexpr (kTrie)
+        if (lane < CTC_MAX_BEAM) ctc_trie_fetch(trie.nodes, 0, rec);
     for (int t = 0; t < T; ++t) {
         const float v0 = next0, v1 = next1;
         if (t + 1 < T) {                                                   // the next frame is requested before this frame's arithmetic
@@ -143,11 +201,27 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
                     m.v[i][c1] = lmv[2 * i + 1];
                 }
         }
+        if constexpr (kTrie) {                                             // likewise
+            if (lane < CTC_MAX_BEAM) {
+                tr.allow[lane][0] = (unsigned long long)(unsigned)rec[0] | ((unsigned long long)(unsigned)rec[1] << 32);
+                tr.allow[lane][1] = (unsigned long long)(unsigned)rec[2] | ((unsigned long long)(unsigned)rec[3] << 32);
+                tr.first[lane] = rec[4];
+                tr.word[lane] = rec[5];
+                tr.node[lane] = rec_node;
+            }
+        }
         if (lane < n) {
             s.tot[lane] = ctc_lae(s.pb[lane], s.pnb[lane]);
             s.absorb[lane] = -1;
         }
-        if (lane < 2 * CTC_MAX_BEAM) s.merged[lane >> 1][lane & 1] = 0ull;
+        if constexpr (kTrie) {                                             // an extension the trie has no edge for is gone from the start
+            if (lane < CTC_MAX_BEAM) {
+                s.merged[lane][0] = ~((unsigned long long)(unsigned)rec[0] | ((unsigned long long)(unsigned)rec[1] << 32));
+                s.merged[lane][1] = ~((unsigned long long)(unsigned)rec[2] | ((unsigned long long)(unsigned)rec[3] << 32));
+            }
+        } else {
+            if (lane < 2 * CTC_MAX_BEAM) s.merged[lane >> 1][lane & 1] = 0ull;
+        }
         wave_lds_fence();
 
         // ---- merges: extend candidate (i, last_j) spells live entry j where prefix_j = prefix_i + last_j
@@ -193,7 +267,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
         // ---- the W best candidates, one per round; lane r keeps the entry of rank r
         unsigned given = 0u;                                               // bit 2 i + h: this lane's candidate (i, lane + 64 h) is taken
         ctc_real new_pb = ctc_neg_inf(), new_pnb = ctc_neg_inf();
-        int new_len = -1, new_last = 0, n_new = 0;
+        int new_len = -1, new_last = 0, n_new = 0, new_node = 0;
         for (int r = 0; r < W; ++r) {
             ctc_real best = ctc_neg_inf();
             int best_k = 0x7fffffff;
@@ -232,6 +306,10 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
                     new_pnb = c > 0 ? best : s.stay_pnb[i];
                     new_len = li + (c > 0 ? 1 : 0);
                     new_last = c > 0 ? c : s.last[i];
+                    if constexpr (kTrie) {                                 // the parent's record, while it stands
+                        const int child = c > 0 ? ctc_trie_child(tr.first[i], tr.allow[i][0], tr.allow[i][1], c) : tr.node[i];
+                        new_node = child < 0 ? 0 : (child >= trie.n_nodes ? trie.n_nodes - 1 : child);
+                    }
                 }
                 ++n_new;
             }
@@ -253,15 +331,24 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
         wave_lds_fence();
         if constexpr (kLm)
             if (t + 1 < T) ctc_lm_fetch(m, lm.table, C, n, c0, c1, has0, has1, lmv);
+        if constexpr (kTrie) {                                             // (behind the last frame too: the word ids)
+            rec_node = new_node;
+            if (lane < CTC_MAX_BEAM) ctc_trie_fetch(trie.nodes, new_node, rec);
+        }
     }
 
-    if constexpr (kLm) {
-        if (lm.eos) {                                                      // (wave-uniform)
+    if constexpr (kLm || kTrie) {
+        if (kTrie || lm.eos) {                                             // (wave-uniform)
             // ---- the end of the word: lane r re-scores entry r and counts the entries that beat it; absorb[rank] = the entry
             ctc_real fs = ctc_neg_inf();
-            if (lane < n) {
-                const float v = lm.table[(long)m.row[lane] * C];
-                fs = v == -__builtin_inff() ? ctc_neg_inf() : ctc_lae(s.pb[lane], s.pnb[lane]) + lm.weight * (double)v;
+            if constexpr (kLm) {
+                if (lane < n) {
+                    const float v = lm.table[(long)m.row[lane] * C];
+                    fs = v == -__builtin_inff() ? ctc_neg_inf() : ctc_lae(s.pb[lane], s.pnb[lane]) + lm.weight * (double)v;
+                }
+            } else {                                                       // a word only where the node ends one
+                if (lane < n && rec[5] >= 0) fs = ctc_lae(s.pb[lane], s.pnb[lane]);
+                if (lane < CTC_MAX_BEAM) tr.word[lane] = rec[5];
             }
             if (lane < CTC_MAX_BEAM) s.stay_score[lane] = fs;
             wave_lds_fence();
@@ -279,6 +366,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_beam_kernel(const float* __re
                 const ctc_real sc = s.stay_score[src];
                 lengths[(long)b * W + lane] = sc > ctc_neg_inf() ? s.len[src] : -1;
                 hyp_scores[(long)b * W + lane] = (float)sc;
+                if constexpr (kTrie) trie.word_ids[(long)b * W + lane] = sc > ctc_neg_inf() ? tr.word[src] : -1;
             }
             for (int r = 0; r < W; ++r) {
                 const int src = s.absorb[r], len = s.stay_score[src] > ctc_neg_inf() ? s.len[src] : -1;

@@ -161,8 +161,12 @@ class TextAccuracy:
     @staticmethod
     def _lexicon_paths(conv, scores):
         """The best lexicon word of every sample as -1-padded int32 paths [B, max_len] (all -1 where no word has an alignment of finite
-        probability): two launches and plain indexing, nothing is read back."""
-        index, _ = ops.ctc_lexicon_best(ops.ctc_lexicon_score(scores, conv.lexicon, normalized=True), 1)
+        probability): two launches and plain indexing, nothing is read back.  With lexicon_beam > 0 the word is the trie search's
+        (ops.ctc_lexicon_search: three launches and a sort, nothing read back either)."""
+        if getattr(conv, "lexicon_beam", 0) > 0:
+            index, _ = ops.ctc_lexicon_search(scores, conv._trie(), conv.lexicon_beam, nbest=1, normalized=True)
+        else:
+            index, _ = ops.ctc_lexicon_best(ops.ctc_lexicon_score(scores, conv.lexicon, normalized=True), 1)
         words = conv.lexicon.on(scores.device)[0]
         if not words.shape[0]:
             return torch.full((scores.shape[0], 1), -1, dtype=torch.int32, device=scores.device)

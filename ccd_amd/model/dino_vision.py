@@ -168,6 +168,7 @@ class DINO_Finetune(ArenaModule):
         self.label_convertor = AttnConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len, with_unknown=True,
                                              beam_width=int(getattr(config, "decoder_beam_width", 0) or 0),     # absent or 0: greedy
                                              lexicon=getattr(config, "decoder_lexicon", None) or None,          # (refused: CTC head only)
+                                             lexicon_beam=int(getattr(config, "decoder_lexicon_beam", 0) or 0),  # (refused as well)
                                              lm=getattr(config, "decoder_lm", None) or None)                    # (refused as well)
         config.arch = config.arch.replace("deit", "vit")
         if config.arch not in vits.__dict__:
@@ -194,6 +195,7 @@ class DINO_Finetune(ArenaModule):
         self.label_convertor = CTCConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len or 25, with_unknown=True,
                                             beam_width=int(getattr(config, "decoder_beam_width", 0) or 0),     # absent or 0: greedy
                                             lexicon=getattr(config, "decoder_lexicon", None) or None,          # absent: no lexicon
+                                            lexicon_beam=int(getattr(config, "decoder_lexicon_beam", 0) or 0), # absent or 0: every word
                                             lm=getattr(config, "decoder_lm", None) or None,                    # absent: no language model
                                             lm_order=_absent(getattr(config, "decoder_lm_order", None), 2),
                                             lm_weight=_absent(getattr(config, "decoder_lm_weight", None), 1.0),

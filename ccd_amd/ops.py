@@ -5,6 +5,7 @@ from __future__ import annotations
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -963,7 +964,7 @@ def ctc_char_lm(table, order):
 
 
 def ctc_beam_search_lm(scores, beam_width, lm, weight=1.0, bonus=0.0, eos=False, normalized=False):
-    """CTC prefix beam search fused with a character n-gram language model (kernels/ctc_beam.h: ctc_beam_kernel<true>): scores and
+    """CTC prefix beam search fused with a character n-gram language model (kernels/ctc_beam.h: ctc_beam_kernel<CTC_BEAM_LM>): scores and
     beam_width as ctc_beam_search, lm a ctc_char_lm handle -> (paths, lengths, hyp_scores) shaped as ctc_beam_search returns them.
     Every extension of a prefix by character c adds weight * lm[row, c] + bonus to the candidate (-inf where the table says so), so a
     hypothesis scores log p_ctc(word | kept alignments) + weight * sum lm + bonus * len(word); eos=True adds weight * lm[row, 0] behind
@@ -1079,6 +1080,137 @@ def ctc_lexicon_best(word_scores, nbest=1):
     ld = word_scores.stride(0) if B > 1 else V                  # (the stride of a single row says nothing)
     _call("ccd_ctc_lexicon_best", word_scores if V else None, ld, B, V, n, index, best)
     return index, best
+
+
+# ------------------------------------------------------------------------------------------ trie search over a lexicon (kernels/ctc_beam.h)
+CTC_TRIE_NODE_WORDS = 8                                   # ccd_hip.h: int32 words per node of ccd_ctc_beam_search_trie's table
+
+
+class CTCLexiconTrie:
+    """The prefix tree of a lexicon for ctc_beam_search_trie / ctc_lexicon_search (build it with ctc_lexicon_trie): `nodes` int32
+    [n_nodes, 8] on the host (the layout: ctc_lexicon_trie), `lexicon` the CTCLexicon it was built from, `stats` = {'nodes', 'bytes',
+    'terminals'}; a device copy is uploaded once per device."""
+
+    def __init__(self, lexicon, nodes):
+        self.lexicon, self.nodes, self.n_nodes = lexicon, nodes, nodes.shape[0]
+        self.stats = {"nodes": self.n_nodes, "bytes": self.n_nodes * CTC_TRIE_NODE_WORDS * 4, "terminals": int((nodes[:, 5] >= 0).sum())}
+        self._device = {}
+
+    def on(self, device):
+        key = str(device)
+        if key not in self._device:                                  # no host synchronisation: through pinned memory, asynchronously
+            cuda = torch.device(device).type == "cuda"
+            self._device[key] = self.nodes.pin_memory().to(device, non_blocking=True) if cuda else self.nodes.to(device)
+        return self._device[key]
+
+
+def _trie_nodes(words):
+    """words int64 numpy [V, max_len], zero-padded -> int32 numpy [n_nodes, 8], breadth-first.  Vectorised: the distinct words are
+    sorted once (a prefix sorts in front of its extensions, the padding being 0), so the nodes of a depth are the rows at which the
+    first `depth` columns change, in breadth-first order already; one pass per depth."""
+    V, L = words.shape
+    ended = np.cumsum(words == 0, axis=1) > 0
+    w = np.where(ended, 0, words)                                    # a word ends at its first zero
+    inside = ((w >= 0) & (w < 128)).all(axis=1)                      # a class outside 1..127 has no mask bit: the word is unreachable
+    rows = np.flatnonzero(inside)
+    uniq, first_row = np.unique(w[rows], axis=0, return_index=True) if rows.size else (np.zeros((0, L), np.int64), np.zeros(0, np.int64))
+    word_row = rows[first_row] if rows.size else first_row           # of duplicate rows the lowest (np.unique: the first occurrence)
+    N = uniq.shape[0]
+    length = (uniq != 0).sum(axis=1)
+    differs = np.ones(N, dtype=np.int64) * 0                         # the first column in which a row differs from the row before it
+    if N > 1:
+        differs[1:] = np.argmax(uniq[1:] != uniq[:-1], axis=1)
+    mask, first, word, parent, edge = [np.zeros((1, 4), np.uint32)], [np.zeros(1, np.int64)], [np.full(1, -1, np.int64)], \
+        [np.full(1, -1, np.int64)], [np.zeros(1, np.int64)]
+    if N and length[0] == 0:
+        word[0][0] = word_row[0]                                     # the empty word: the root is terminal
+    above = np.zeros(N, dtype=np.int64)                              # the node of every row's prefix one level up: the root
+    base = 1
+    for depth in range(1, L + 1):
+        new = (length >= depth) & (differs < depth)
+        count = int(new.sum())
+        if not count:
+            break
+        node = base + np.cumsum(new) - 1                             # of the row's prefix of `depth` classes (where length >= depth)
+        at = np.flatnonzero(new)
+        p, c = above[at], uniq[at, depth - 1]
+        m = np.zeros((count, 4), np.uint32)
+        f = np.zeros(count, np.int64)
+        wd = np.full(count, -1, np.int64)
+        ends = np.flatnonzero(length == depth)                       # (such a row opens its node: it sorts in front of its extensions)
+        wd[node[ends] - base] = word_row[ends]
+        mask.append(m), first.append(f), word.append(wd), parent.append(p), edge.append(c)
+        # the parents' side: their mask bits and first children (parents ascend along `at`: the first occurrence is the lowest class)
+        level = len(mask) - 2
+        start = base - mask[level].shape[0]
+        np.bitwise_or.at(mask[level], (p - start, c >> 5), (np.uint32(1) << (c & 31).astype(np.uint32)))
+        which, where = np.unique(p, return_index=True)
+        first[level][which - start] = base + where
+        above = np.where(length >= depth, node, 0)
+        base += count
+    nodes = np.zeros((base, CTC_TRIE_NODE_WORDS), dtype=np.int32)
+    nodes[:, :4] = np.concatenate(mask).view(np.int32)
+    nodes[:, 4], nodes[:, 5], nodes[:, 6], nodes[:, 7] = np.concatenate(first), np.concatenate(word), np.concatenate(parent), np.concatenate(edge)
+    return nodes
+
+
+def ctc_lexicon_trie(lexicon):
+    """The prefix tree of a ctc_lexicon handle, built once per lexicon on the host -> CTCLexiconTrie.  nodes int32 [n_nodes, 8], 32
+    bytes per node: words 0..3 the 128-bit child mask (bit c & 31 of word c >> 5 is set iff the node has a child by class c; bit 0
+    never), 4 first_child (the node of the child with the lowest class), 5 word_id (the row of lexicon.words that ends here - of
+    duplicate rows the lowest - or -1), 6 the parent (-1 for the root), 7 the class on the edge from the parent (0 for the root).
+    Breadth-first: the root is node 0, the children of a node are contiguous in ascending class order, so the child by class c is
+    first_child + popcount(mask bits below c).  An all-zero row makes the root terminal; an empty lexicon is the root alone.  A word
+    with a class outside 1..127 is left out: no scores have such a class."""
+    if not isinstance(lexicon, CTCLexicon):
+        raise TypeError(f"ctc_lexicon_trie: lexicon must come from ctc_lexicon, got {type(lexicon).__name__}")
+    return CTCLexiconTrie(lexicon, torch.from_numpy(_trie_nodes(lexicon.words.numpy())))
+
+
+def ctc_beam_search_trie(scores, beam_width, trie, normalized=False):
+    """CTC prefix beam search along the prefix tree of a lexicon (kernels/ctc_beam.h: ctc_beam_kernel<CTC_BEAM_TRIE>): scores and
+    beam_width as ctc_beam_search, trie a ctc_lexicon_trie handle -> (paths, lengths, hyp_scores) shaped as ctc_beam_search returns
+    them, and word_ids int32 [B, W]: the row of the lexicon every hypothesis is, -1 for an unused slot.  A prefix grows only along an
+    edge of the trie and is a hypothesis only where a word ends; prefixes that end no word compete for the beam's slots during the
+    search, so a narrow beam may end with no word at all.  hyp_scores is a lower bound of ctc_lexicon_score's number for that word: the
+    sum over the alignments the beam kept.  The cost does not depend on the size of the lexicon."""
+    if scores.dim() != 3 or (scores.shape[2] > 1 and scores.stride(2) != 1):
+        raise ValueError(f"ctc_beam_search_trie: expects scores [B, T, C] with contiguous classes, got {list(scores.shape)}, strides "
+                         f"{scores.stride()}")
+    if not isinstance(trie, CTCLexiconTrie):
+        raise TypeError(f"ctc_beam_search_trie: trie must come from ctc_lexicon_trie, got {type(trie).__name__}")
+    B, T, C = scores.shape
+    W = int(beam_width)
+    if not 1 <= W <= CTC_MAX_BEAM:
+        raise ValueError(f"ctc_beam_search_trie: beam_width must lie in 1..{CTC_MAX_BEAM}, got {beam_width}")
+    paths = torch.empty((B, W, T), dtype=I32, device=scores.device)
+    lengths = torch.empty((B, W), dtype=I32, device=scores.device)
+    hyp_scores = torch.empty((B, W), dtype=F32, device=scores.device)
+    word_ids = torch.empty((B, W), dtype=I32, device=scores.device)
+    _call("ccd_ctc_beam_search_trie", scores, scores.stride(0), scores.stride(1), B, T, C, 1 if normalized else 0, W, trie.on(scores.device),
+          trie.n_nodes, paths, lengths, hyp_scores, word_ids)
+    return paths, lengths, hyp_scores, word_ids
+
+
+def ctc_lexicon_search(scores, trie, beam_width, nbest=1, normalized=False):
+    """The two-stage closed-vocabulary decoder, on the device with no host synchronisation: ctc_beam_search_trie proposes up to
+    beam_width words per sample, ctc_lexicon_score(subset=) scores those exactly and ctc_lexicon_best picks
+    -> (word_ids int32 [B, nbest], log_probs fp32 [B, nbest]), best first; an empty slot is (-1, -inf).  The log-probabilities are the
+    exact ones - the numbers ctc_lexicon_score gives those words - and the proposals are sorted by word id before they are scored, so a
+    tie in the exact score falls to the lower word id, as on the exhaustive path.  The answer is the exhaustive path's whenever its
+    best word is among the beam's proposals."""
+    W, n = int(beam_width), int(nbest)
+    if not 1 <= n <= max(W, 1):
+        raise ValueError(f"ctc_lexicon_search: nbest must lie in 1..beam_width = {beam_width}, got {nbest}")
+    _, _, _, ids = ctc_beam_search_trie(scores, W, trie, normalized=normalized)
+    if not ids.shape[0]:                                                 # no sample: nothing to score
+        return ids[:, :n], torch.empty((0, n), dtype=F32, device=scores.device)
+    last = torch.iinfo(I32).max
+    ids = torch.where(ids < 0, last, ids).sort(dim=1).values             # ascending, the empty slots last
+    ids = torch.where(ids == last, -1, ids).contiguous()                 # ... as the negative padding of a subset
+    index, best = ctc_lexicon_best(ctc_lexicon_score(scores, trie.lexicon, normalized=normalized, subset=ids), n)
+    picked = ids.gather(1, index.clamp(min=0).long())
+    return torch.where(index >= 0, picked, -1).to(I32), best
 
 
 # ------------------------------------------------------------------------------------------ forced alignment (kernels/ctc_align.h)

@@ -487,7 +487,7 @@ int ccd_ctc_greedy(const float* logits, long sample_stride, long step_stride, in
 #define CCD_CTC_MAX_BEAM 16
 int ccd_ctc_beam_search(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
                         int beam, int* paths, int* lengths, float* hyp_scores, void* stream);
-/* CTC prefix beam search fused with a character n-gram language model (ABI 24; kernels/ctc_beam.h: ctc_beam_kernel<true>, restated in
+/* CTC prefix beam search fused with a character n-gram language model (ABI 24; kernels/ctc_beam.h: ctc_beam_kernel<CTC_BEAM_LM>, restated in
  * numpy in tests/ctc_beam_lm_np.py): the open-vocabulary decoder that prefers plausible spellings.  scores, beam and the outputs as
  * ccd_ctc_beam_search; one wavefront per sample.
  *   lm          fp32 [classes^(order-1), classes], row-major, order in 1..CCD_CTC_LM_MAX_ORDER.  The row of a prefix p is built from its
@@ -515,6 +515,32 @@ int ccd_ctc_beam_search(const float* scores, long sample_stride, long step_strid
 int ccd_ctc_beam_search_lm(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
                            int beam, const float* lm, int order, float weight, float bonus, int eos,
                            int* paths, int* lengths, float* hyp_scores, void* stream);
+/* CTC prefix beam search along a lexicon's prefix tree (ABI 26; kernels/ctc_beam.h: ctc_beam_kernel<CTC_BEAM_TRIE>, restated in numpy in
+ * tests/ctc_trie_np.py): the closed-vocabulary proposer whose cost does not grow with the lexicon.  scores, beam, paths, lengths and
+ * hyp_scores as ccd_ctc_beam_search; one wavefront per sample.
+ *   nodes       int32 [n_nodes, 8], 32 bytes per node, breadth-first: the root is node 0, the children of a node are contiguous in
+ *               ascending class order.  Words 0..3: the 128-bit child mask, bit c & 31 of word c >> 5 set iff the node has a child by
+ *               class c (bit 0 never); word 4: first_child, the node of the child with the lowest class - the child by class c is
+ *               first_child + popcount(mask bits below c); word 5: word_id, the lexicon row that ends here (the lowest of duplicate
+ *               rows) or -1; word 6: the parent, -1 for the root; word 7: the class on the edge from the parent, 0 for the root.  The
+ *               kernel reads words 0..5.  An empty lexicon is the root alone.
+ *   Every beam entry carries a node; the empty prefix carries node 0.  An extend candidate (i, c) exists iff bit c of mask[node_i] is
+ *               set - otherwise it is -inf: never selected, never merged - and scores what ccd_ctc_beam_search gives it, with no added
+ *               term; the selected extension carries child(node_i, c), a stay keeps the node.  Merges, the selection key and the tie rule
+ *               are unchanged.  Prefixes that end no word compete for the beam's slots during the search.
+ *   Behind the last frame the score of an entry is logaddexp(pb, pnb) where word_id[node] >= 0 and -inf otherwise; the entries are
+ *               ranked again by (score descending, previous rank ascending), and a -inf entry becomes an unused slot (length -1, score
+ *               -inf, path all -1, word id -1).  With a narrow beam a sample may end with no word at all.
+ *   word_ids    int32 [batch, beam]: word_id of every hypothesis, -1 for an unused slot.  hyp_scores is a lower bound of the word's
+ *               ccd_ctc_lexicon_score: the sum over the alignments the beam kept.
+ *   Every node id the kernel derives is clamped to [0, n_nodes) before it addresses the table, and mask bits of classes >= `classes`
+ *   are never scanned: a malformed table gives wrong words, never an access outside it; a word with a class outside the scores is
+ *   unreachable, as it is -inf for ccd_ctc_lexicon_score.
+ * No atomics, no workspace: the same input gives the same bits.  batch == 0 is a no-op.  CCD_EINVAL: a missing pointer (nodes and word_ids
+ * included), a negative size or stride; CCD_ESHAPE: everything ccd_ctc_beam_search refuses, n_nodes < 1.  Nothing is launched on an error. */
+int ccd_ctc_beam_search_trie(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
+                             int beam, const int* nodes, int n_nodes, int* paths, int* lengths, float* hyp_scores, int* word_ids,
+                             void* stream);
 
 /* Lexicon-constrained decoding of the CTC head (ABI 23; kernels/ctc_lexicon.h, restated in numpy in tests/ctc_lexicon_np.py): of THESE
  * words, which is the most probable given the frames, and how probable is each.

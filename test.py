@@ -95,6 +95,9 @@ def main():
                     help="beam search of this width, 1..16, for either head (CTC: prefix beam search; NRTR: beam over the decoder); 0: greedy decoding")
     ap.add_argument("--lexicon", type=str, default=None,
                     help="evaluate the CTC head with lexicon-constrained decoding over this UTF-8 word list (one word per line); excludes a beam")
+    ap.add_argument("--lexicon_beam", type=int, default=None,
+                    help="with a lexicon: search its prefix tree with a beam of this width, 1..16, and score only the proposed words "
+                         "exactly - the cost no longer grows with the lexicon; 0: score every word")
     ap.add_argument("--lm", type=str, default=None,
                     help="fuse a character n-gram language model into the CTC beam search: an .npz of CharNGram.save, or a UTF-8 word list "
                          "(estimated at decoder.lm_order); needs a beam, excludes a lexicon")
@@ -115,6 +118,8 @@ def main():
         config.decoder_beam_width = a.beam_width
     if a.lexicon is not None:
         config.decoder_lexicon = a.lexicon
+    if a.lexicon_beam is not None:
+        config.decoder_lexicon_beam = a.lexicon_beam
     for key in ("lm", "lm_weight", "lm_bonus"):
         if getattr(a, key) is not None:
             setattr(config, f"decoder_{key}", getattr(a, key))

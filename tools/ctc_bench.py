@@ -19,7 +19,7 @@ default the first three):
           yardstick in the same process: ccd_ctc_loss_fwd on the pairs of a 64-word slice with replicated rows (a 537 MB buffer), as
           time per pair; then evaluation images/s at B = 512, vit_small, greedy against a 1000-word lexicon.
     python tools/ctc_bench.py --cases lexicon --out profiles/ctc_lexicon.json
-  lm      ccd_ctc_beam_search_lm (kernels/ctc_beam.h: ctc_beam_kernel<true>) on the same probabilities with random normalised tables of
+  lm      ccd_ctc_beam_search_lm (kernels/ctc_beam.h: ctc_beam_kernel<CTC_BEAM_LM>) on the same probabilities with random normalised tables of
           order 2 (34 KB) and 3 (3.1 MB), weight 0.5, bonus 0.8, eos on, beam widths 1, 4, 8, 16; ccd_ctc_beam_search at the same
           widths in the same process and the same rounds is the thing to compare with.
     python tools/ctc_bench.py --cases lm --out profiles/ctc_beam_lm.json
@@ -29,6 +29,14 @@ default the first three):
           then evaluation images/s at B = 512, vit_small: forward + TextAccuracy.update_scores, without and with what test.py
           --alignments adds per batch (CTCConvertor.tensor2chars: decode, align, one copy to the host, the host-side records).
     python tools/ctc_bench.py --cases align --out profiles/ctc_align.json
+  trie    ccd_ctc_beam_search_trie (kernels/ctc_beam.h: ctc_beam_kernel<CTC_BEAM_TRIE>) and the two-stage ops.ctc_lexicon_search on the same
+          probabilities with synthetic lexicons of 1 000 / 10 000 / 90 000 words of 2..15 characters: the trie kernel at beam widths 4,
+          8, 16; the sort + subset rescoring + selection behind it; the whole search; in the same process and the same rounds the
+          exhaustive ccd_ctc_lexicon_score + ccd_ctc_lexicon_best on the same inputs and ccd_ctc_beam_search at the same widths; the host
+          build time and the size of each trie; the share of samples whose searched best word is the exhaustive best (recorded, not
+          gated: synthetic frames are not a recogniser's); then evaluation images/s at B = 512, vit_small, with a 10 000-word lexicon,
+          exhaustive against lexicon_beam 16.
+    python tools/ctc_bench.py --cases trie --out profiles/ctc_lexicon_trie.json
 Warm-up first, HIP events around every timed call, a figure is the median of the round medians with the lowest and highest
 round.  No threshold is set; the file records what was measured.  `--case NAME` runs one case and prints its JSON line."""
 import argparse
@@ -42,7 +50,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 B, T, C = 512, 32, 92
-LIMITS = {"loss": 240, "step": 420, "infer": 300, "beam": 300, "lexicon": 420, "lm": 240, "align": 300}           # seconds per case
+LIMITS = {"loss": 240, "step": 420, "infer": 300, "beam": 300, "lexicon": 420, "lm": 240, "align": 300, "trie": 540}           # seconds per case
 # word length -> share in per cent of a lexicon of `lexicon`: the shape of an English word list (mode 5 - 7 characters, a tail to 15)
 LEXICON_LENGTHS = {2: 2, 3: 6, 4: 11, 5: 14, 6: 15, 7: 14, 8: 12, 9: 9, 10: 7, 11: 4, 12: 3, 13: 1, 14: 1, 15: 1}
 
@@ -410,7 +418,95 @@ def case_align(a):
     return out
 
 
-CASES = {"align": case_align, "loss": case_loss, "step": case_step, "infer": case_infer, "beam": case_beam, "lexicon": case_lexicon, "lm": case_lm}
+def case_trie(a):
+    import time
+    import torch
+    from ccd_amd import finetune as ft, ops
+    from ccd_amd.metric.eval_acc import TextAccuracy
+    dev = torch.device("cuda")
+    probs = _peaked_probs(5)
+    out = {"shape": [B, T, C], "input": "fp32 probabilities, normalized = 1", "word_length_per_cent": LEXICON_LENGTHS}
+    widths = (4, 8, 16)
+    sizes = (1000, 10000, 90000)
+    last = torch.iinfo(torch.int32).max
+
+    def rescore(ids, lexicon):
+        ids = torch.where(ids < 0, last, ids).sort(dim=1).values
+        ids = torch.where(ids == last, -1, ids).contiguous()
+        return ops.ctc_lexicon_best(ops.ctc_lexicon_score(probs, lexicon, normalized=True, subset=ids), 1)
+
+    def exhaustive(lexicon):
+        return ops.ctc_lexicon_best(ops.ctc_lexicon_score(probs, lexicon, normalized=True), 1)
+
+    plain = {w: [] for w in widths}
+    tables = {}
+    for V in sizes:
+        lexicon = ops.ctc_lexicon(_lexicon_words(V, 6))
+        build = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            trie = ops.ctc_lexicon_trie(lexicon)
+            build.append((time.perf_counter() - t0) * 1e3)
+        tables[V] = trie
+        trie.on(dev)
+        iters = max(3, a.iters // (3 if V < 90000 else 6))
+        kernel, behind, whole = ({w: [] for w in widths} for _ in range(3))
+        full = []
+        proposals = {w: ops.ctc_beam_search_trie(probs, w, trie, normalized=True)[3] for w in widths}
+        for _ in range(a.rounds):
+            for w in widths:
+                kernel[w].append(event_ms(lambda: ops.ctc_beam_search_trie(probs, w, trie, normalized=True), a.iters))
+                behind[w].append(event_ms(lambda: rescore(proposals[w], lexicon), a.iters))
+                whole[w].append(event_ms(lambda: ops.ctc_lexicon_search(probs, trie, w, normalized=True), a.iters))
+                if V == sizes[0]:
+                    plain[w].append(event_ms(lambda: ops.ctc_beam_search(probs, w, normalized=True), a.iters))
+            full.append(event_ms(lambda: exhaustive(lexicon), iters))
+        rec = {"trie": {**trie.stats, "host_build_ms": round(statistics.median(build), 1)},
+               "exhaustive_ctc_lexicon_score_plus_best": summary(full)}
+        want = exhaustive(lexicon)[0][:, 0]
+        for w in widths:
+            ids, _ = ops.ctc_lexicon_search(probs, trie, w, normalized=True)
+            rec[f"w{w}"] = {"ctc_beam_search_trie": summary(kernel[w]), "sort_subset_rescoring_selection": summary(behind[w]),
+                            "ctc_lexicon_search": summary(whole[w]),
+                            "exhaustive_over_search": round(rec["exhaustive_ctc_lexicon_score_plus_best"]["median_ms"] /
+                                                            statistics.median(whole[w]), 2),
+                            "search_faster_than_exhaustive_beyond_spread": max(whole[w]) < min(full),
+                            "share_of_samples_whose_best_is_the_exhaustive_best": round(float((ids[:, 0] == want).float().mean()), 4),
+                            "share_of_samples_with_a_word": round(float((ids[:, 0] >= 0).float().mean()), 4)}
+        out[f"v{V}"] = rec
+        del want
+    for w in widths:
+        out[f"ctc_beam_search_w{w}"] = summary(plain[w])
+    # evaluation: forward + scoring, the body of TextAccuracy.compute, with the 10 000-word lexicon
+    torch.manual_seed(0)
+    cfg = ft.FinetuneConfig()
+    cfg.decoder_type = "CTCDecoder"
+    model = ft.build_model(cfg, dev, dropout=0.0).eval()
+    conv = model.label_convertor
+    img = torch.randn(B, 3, 32, 128, generator=torch.Generator().manual_seed(4)).to(dev)
+    words = ["".join(conv.idx2char[1 + (i * 7 + j) % 90] for j in range(3 + i % 13)) for i in range(B)]
+    strings = conv.idx2str([row[row != 0].tolist() for row in tables[10000].lexicon.words])
+    metric = TextAccuracy()
+
+    def evaluate():
+        metric.update_scores(model(img, text=None, return_loss=False, test_speed=False).float(), words, conv)
+
+    sides = {0: [], 16: []}
+    iters = max(3, a.iters // 3)
+    conv.set_lexicon(strings, beam=16)                                         # (builds the trie; the width is switched per side)
+    with torch.no_grad():
+        for _ in range(a.rounds):
+            for beam in sides:
+                conv.lexicon_beam = beam
+                sides[beam].append(event_ms(evaluate, iters))
+    e0, e16 = summary(sides[0]), summary(sides[16])
+    out.update({"batch": B, "arch": "vit_small", "evaluate_lexicon_10000_exhaustive": e0, "evaluate_lexicon_10000_lexicon_beam_16": e16,
+                "exhaustive_images_per_s": round(B / (e0["median_ms"] * 1e-3)),
+                "lexicon_beam_16_images_per_s": round(B / (e16["median_ms"] * 1e-3))})
+    return out
+
+
+CASES = {"trie": case_trie, "align": case_align, "loss": case_loss, "step": case_step, "infer": case_infer, "beam": case_beam, "lexicon": case_lexicon, "lm": case_lm}
 
 
 def main():

@@ -215,6 +215,9 @@ def _parse_arguments():
                         help="evaluate with beam search of this width, 1..16, for either head (CTC: prefix beam search; NRTR: beam over the decoder); 0: greedy")
     parser.add_argument("--lexicon", type=str, default=None,
                         help="evaluate the CTC head with lexicon-constrained decoding over this UTF-8 word list (one word per line); excludes a beam")
+    parser.add_argument("--lexicon_beam", type=int, default=None,
+                        help="with a lexicon: search its prefix tree with a beam of this width, 1..16, and score only the proposed words "
+                             "exactly - the cost no longer grows with the lexicon; 0: score every word")
     parser.add_argument("--lm", type=str, default=None,
                         help="evaluate the CTC head with a character n-gram language model fused into the beam search: an .npz of CharNGram.save, "
                              "or a UTF-8 word list (estimated at decoder.lm_order); needs a beam, excludes a lexicon")
@@ -226,6 +229,8 @@ def _parse_arguments():
         config.decoder_beam_width = args.beam_width
     if args.lexicon is not None:
         config.decoder_lexicon = args.lexicon
+    if args.lexicon_beam is not None:
+        config.decoder_lexicon_beam = args.lexicon_beam
     for key in ("lm", "lm_weight", "lm_bonus"):
         if getattr(args, key) is not None:
             setattr(config, f"decoder_{key}", getattr(args, key))
