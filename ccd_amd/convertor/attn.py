@@ -42,7 +42,11 @@ def _read_alphabet_file(path):
 class AttnConvertor:
     """AttnConvertor(dict_type='DICT90', max_seq_len=40, with_unknown=True, beam_width=0) - see the module docstring.  `beam_width` > 0
     asks for beam search over the decoder (DINO_Finetune.forward_beam) where words are scored (TextAccuracy.compute); 0, the default,
-    is greedy decoding everywhere, and `tensor2idx` is the greedy rule whatever the width."""
+    is greedy decoding everywhere, and `tensor2idx` is the greedy rule whatever the width.  `lexicon` (a list of words or the path of
+    a word list) TOGETHER WITH `lexicon_beam` in 1..16 asks for the closed vocabulary instead: a beam of that width over the decoder
+    that walks the lexicon's prefix tree (DINO_Finetune.forward_lexicon); a finished hypothesis is a word of the lexicon and its score
+    the exact log p(word <EOS> | image).  Either of the two alone is refused: exhaustive scoring of a lexicon exists for the CTC head
+    only."""
 
     dicts = {name: tuple(chars) for name, chars in ALPHABETS.items()}      # same table name as the reference exposes
 
@@ -52,10 +56,11 @@ class AttnConvertor:
             raise NotImplementedError("AttnConvertor: language-model fusion is for the CTC head only - the NRTR decoder conditions every "
                                       "character on the ones before it already, and its beam takes no additive table term (use "
                                       "decoder.type: 'CTCDecoder')")
-        if lexicon is not None or lexicon_beam:
-            raise NotImplementedError("AttnConvertor: lexicon-constrained decoding is for the CTC head only - the probability of a word "
+        if (lexicon is not None) != bool(lexicon_beam):
+            raise NotImplementedError("AttnConvertor: scoring every word of a lexicon is for the CTC head only - the probability of a word "
                                       "under the NRTR decoder takes one teacher-forced decoder pass per word, not a closed-form "
-                                      "recursion over the frames (use decoder.type: 'CTCDecoder')")
+                                      "recursion over the frames (use decoder.type: 'CTCDecoder').  The NRTR head takes `lexicon` "
+                                      "together with `lexicon_beam: N` (1..16): a beam of width N over the lexicon's prefix tree")
         if dict_file is not None:
             alphabet = _read_alphabet_file(dict_file)
         elif dict_list is not None:
@@ -83,6 +88,64 @@ class AttnConvertor:
         for cls, c in enumerate(self.idx2char[:len(alphabet)]):
             if len(c) == 1:
                 self._lut[ord(c)] = cls
+        self.lexicon, self.lexicon_words, self.lexicon_stats, self.lexicon_trie, self.lexicon_beam = None, None, None, None, 0
+        if lexicon is not None:
+            self.set_lexicon(lexicon, beam=lexicon_beam)
+
+    @staticmethod
+    def _checked_lexicon_beam(beam):
+        from ..ops import NRTR_MAX_BEAM
+        if isinstance(beam, bool) or int(beam) != beam or not 1 <= int(beam) <= NRTR_MAX_BEAM:
+            raise ValueError(f"lexicon_beam must lie in 1..{NRTR_MAX_BEAM} (the width of the beam over the lexicon's prefix tree), got {beam!r}")
+        return int(beam)
+
+    def set_lexicon(self, strings_or_path, beam=None):
+        """The closed vocabulary of DINO_Finetune.forward_lexicon and TextAccuracy: a list of words, or the path of a UTF-8 file with
+        one word per line (empty lines skipped); None removes it.  beam replaces lexicon_beam where given (a first lexicon needs one).
+        Kept: `lexicon_words` (the kept strings: word id v is lexicon_words[v]), `lexicon` (the ops.ctc_lexicon handle whose rows are
+        class + 1, zero-padded: class 0 is the character '0', and a row ends at its first zero), `lexicon_trie` (the
+        ops.ctc_lexicon_trie handle of those rows) and `lexicon_stats` = {'read', 'kept', 'too_long', 'duplicates', 'nodes'}.  too_long
+        counts the words of more than max_seq_len - 1 characters, which could never write their <EOS> (and of more than
+        ops.CTC_MAX_LABELS, the widest row a lexicon handle takes): with finite logits and a lexicon that is not empty every slot that
+        is still alive at the last step is then finished."""
+        from .. import ops
+        if strings_or_path is None:
+            if beam:
+                raise ValueError(f"lexicon_beam = {beam} needs a lexicon: it is the width of the search over the lexicon's trie")
+            self.lexicon, self.lexicon_words, self.lexicon_stats, self.lexicon_trie, self.lexicon_beam = None, None, None, None, 0
+            return None
+        width = self._checked_lexicon_beam(self.lexicon_beam if beam is None else beam)
+        if self.beam_width > 0:
+            raise ValueError(f"a lexicon and beam_width = {self.beam_width} exclude each other: the lexicon's beam is lexicon_beam, set "
+                             "beam_width to 0")
+        if isinstance(strings_or_path, (str, bytes)) or hasattr(strings_or_path, "__fspath__"):
+            with open(strings_or_path, encoding="utf-8") as f:
+                strings = [line.rstrip("\r\n") for line in f]
+            strings = [w for w in strings if w]
+        else:
+            strings = list(strings_or_path)
+            if not all(isinstance(w, str) for w in strings):
+                raise TypeError("set_lexicon expects a list of strings or the path of a word list")
+        longest = min(self.max_seq_len - 1, ops.CTC_MAX_LABELS)
+        kept, rows, seen, too_long, duplicates = [], [], set(), 0, 0
+        for word, cls in zip(strings, self.str2idx(strings)):
+            if len(cls) > longest:
+                too_long += 1
+            elif tuple(cls) in seen:
+                duplicates += 1
+            else:
+                seen.add(tuple(cls))
+                kept.append(word)
+                rows.append(cls)
+        words = np.zeros((len(rows), max(1, max(map(len, rows), default=1))), dtype=np.int64)
+        for row, cls in zip(words, rows):
+            row[:len(cls)] = np.asarray(cls, dtype=np.int64) + 1
+        self.lexicon = ops.ctc_lexicon(torch.from_numpy(words))
+        self.lexicon_words, self.lexicon_beam = kept, width
+        self.lexicon_trie = ops.ctc_lexicon_trie(self.lexicon)
+        self.lexicon_stats = {"read": len(strings), "kept": len(kept), "too_long": too_long, "duplicates": duplicates,
+                              "nodes": self.lexicon_trie.n_nodes}
+        return self.lexicon_stats
 
     def _append(self, token):
         self.idx2char.append(token)
@@ -190,3 +253,21 @@ class AttnConvertor:
             raise ValueError(f"paths2nbest: expects paths [N, W, T], lengths [N, W] and scores [N, W], got {list(paths.shape)}, "
                              f"{list(lengths.shape)}, {list(scores.shape)}")
         return nbest_lists("paths2nbest", paths, lengths, scores, nbest)
+
+    @torch.no_grad()
+    def paths2lexicon(self, word_ids, log_probs, nbest=1):
+        """What DINO_Finetune.forward_lexicon returns - word_ids int32 [N, W] and log_probs fp32 [N, W], best first - -> (indexes,
+        log_probs, word_ids) as CTCConvertor.tensor2lexicon returns them on the host: indexes[i] holds up to `nbest` index lists (the
+        classes of lexicon_words[v]; fewer where the beam ended with fewer words), log_probs a float tensor [N, nbest], the exact
+        log-probability of each word with its <EOS>, -inf where a slot is empty; word_ids an int64 tensor [N, nbest], -1 likewise."""
+        if self.lexicon is None:
+            raise ValueError("paths2lexicon: the convertor has no lexicon (set_lexicon)")
+        if word_ids.dim() != 2 or tuple(log_probs.shape) != tuple(word_ids.shape):
+            raise ValueError(f"paths2lexicon: expects word_ids [N, W] and log_probs [N, W], got {list(word_ids.shape)} and "
+                             f"{list(log_probs.shape)}")
+        if not 1 <= int(nbest) <= word_ids.shape[1]:
+            raise ValueError(f"paths2lexicon: nbest must lie in 1..{word_ids.shape[1]}, got {nbest}")
+        ids = word_ids[:, :int(nbest)].long().cpu()
+        words, lengths = self.lexicon.words, self.lexicon.lengths
+        indexes = [[(words[v, :lengths[v]] - 1).tolist() for v in row if v >= 0] for row in ids.tolist()]
+        return indexes, log_probs[:, :int(nbest)].float().cpu(), ids

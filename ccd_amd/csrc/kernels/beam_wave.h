@@ -9,6 +9,8 @@
 //                ctc_beam_kernel the compiler trades 10 VGPRs for an occupancy nobody uses, and the kernel runs 1 - 2.5 % slower.
 //   selection    W rounds of a wave arg-max on the key (score descending, k = rank * C + class ascending): each lane folds its own
 //                candidates (k ascends along its scan, `>` keeps the lowest k of equals), six xor-shuffle steps fold the lanes.
+//   trie walk    the record of a node of a lexicon's prefix tree and the child by a mask bit (ctc_trie_fetch, ctc_trie_child: lane-local,
+//                the exceptions to the rule below), for the trie instances of both kernels.
 // EVERY FUNCTION BELOW IS CALLED BY ALL 64 LANES OF THE WAVE (they shuffle, or fence LDS that other lanes read): the caller's
 // branch around a call must be wave-uniform.  No atomics: the same input gives the same bits.
 // Arithmetic is fp64 (ctc_real): the selection compares scores whose neighbours lie 1e-5 nats apart at |score| ~ 100 .. 150, which
@@ -92,6 +94,23 @@ __device__ __forceinline__ CtcReal2 beam_wave_log_probs(float v0, float v1, bool
     }
     const ctc_real lsum = beam_wave_log_sum(row, C, e0, e1);
     return {live0 ? num0 - lsum : ctc_neg_inf(), live1 ? num1 - lsum : ctc_neg_inf()};
+}
+
+// ---- a lexicon's prefix tree (ccd_hip.h has the node layout), walked by ctc_beam_kernel<CTC_BEAM_TRIE> and nrtr_beam_step_kernel<true>
+constexpr int CTC_TRIE_NODE_WORDS = 8, CTC_TRIE_RECORD = 6;      // words per node; those the kernel reads: the mask, first_child, word_id
+
+// The lanes below CTC_MAX_BEAM.  Requests the record of `node` (in [0, n_nodes)) into registers (consumed a frame later).
+__device__ __forceinline__ void ctc_trie_fetch(const int* __restrict__ nodes, int node, int (&r)[CTC_TRIE_RECORD]) {
+    const int* const p = nodes + (long)node * CTC_TRIE_NODE_WORDS;
+#pragma unroll
+    for (int k = 0; k < CTC_TRIE_RECORD; ++k) r[k] = p[k];
+}
+
+// The child of a node by class c (1 <= c < 128, its mask bit set): the children are contiguous in ascending class order.
+__device__ __forceinline__ int ctc_trie_child(int first, unsigned long long m0, unsigned long long m1, int c) {
+    const int below = c < 64 ? __builtin_popcountll(m0 & ((1ull << c) - 1ull))
+                             : __builtin_popcountll(m0) + __builtin_popcountll(m1 & ((1ull << (c - 64)) - 1ull));
+    return first + below;
 }
 
 }  // namespace ccd

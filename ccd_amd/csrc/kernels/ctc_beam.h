@@ -106,22 +106,7 @@ struct CtcBeamTrie {                                             // the lexicon 
     const int* nodes;                                            // int32 [n_nodes, 8]: mask[4], first_child, word_id, parent, class
     int n_nodes;
     int* word_ids;                                               // int32 [B, W]
-};
-constexpr int CTC_TRIE_NODE_WORDS = 8, CTC_TRIE_RECORD = 6;      // words per node; those the kernel reads: the mask, first_child, word_id
-
-// The lanes below CTC_MAX_BEAM.  Requests the record of `node` (in [0, n_nodes)) into registers (consumed a frame later).
-__device__ __forceinline__ void ctc_trie_fetch(const int* __restrict__ nodes, int node, int (&r)[CTC_TRIE_RECORD]) {
-    const int* const p = nodes + (long)node * CTC_TRIE_NODE_WORDS;
-#pragma unroll
-    for (int k = 0; k < CTC_TRIE_RECORD; ++k) r[k] = p[k];
-}
-
-// The child of a node by class c (1 <= c < 128, its mask bit set): the children are contiguous in ascending class order.
-__device__ __forceinline__ int ctc_trie_child(int first, unsigned long long m0, unsigned long long m1, int c) {
-    const int below = c < 64 ? __builtin_popcountll(m0 & ((1ull << c) - 1ull))
-                             : __builtin_popcountll(m0) + __builtin_popcountll(m1 & ((1ull << (c - 64)) - 1ull));
-    return first + below;
-}
+};                                                               // (ctc_trie_fetch / ctc_trie_child: beam_wave.h)
 
 // g of one table value: the fp64 product, then the fp64 sum; -inf stays -inf whatever the weight.
 __device__ __forceinline__ ctc_real ctc_lm_term(float v, double weight, double bonus) {

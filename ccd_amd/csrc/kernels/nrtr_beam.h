@@ -22,6 +22,25 @@
 //   4. the new rows: positions 0..step from the parent's row in LDS, position step + 1 the new token; score, state, parent by lane r.
 // Every loop that shuffles has a wave-uniform trip count (W, the slots).  fp64 throughout (ctc_real).
 //
+// Beam search over a lexicon's prefix tree (ccd_nrtr_beam_step_trie, nrtr_beam_step_kernel<true>; tests/nrtr_trie_np.py is the
+// specification): the same kernel - `template <bool kTrie>`, whose `false` instance is the code above and nothing else - with a trie
+// node per slot, node int32 [B, W], in and out like score and state (the caller starts every slot at the root, node 0).  The table is
+// ctc_beam_kernel<CTC_BEAM_TRIE>'s (ccd_hip.h has the layout), its mask bit for decoder class c is bit c + class_offset: the lexicon
+// rows of an AttnConvertor are class + 1, because its class 0 is a character and the trie never sets bit 0.
+//   live slot r at node n  (r, c), c != end_idx, exists iff c + class_offset <= 127 and that bit of mask[n] is set; (r, end_idx) iff
+//                          word_id[n] >= 0.  Everything else is -inf: no candidate.  An allowed candidate scores what the plain
+//                          instance gives it - the log-softmax runs over ALL C classes, nothing is renormalised - so the score of
+//                          a finished slot is the exact log p(word <EOS> | image), comparable across words: no second stage.
+//   nodes                  a selected extension carries first_child[n] + popcount(mask[n] bits below c + class_offset), clamped to
+//                          [0, n_nodes) as the CTC instance clamps; end_idx and a carried finished slot keep the node; unused: 0.
+//   final                  word_ids int32 [B, W]: word_id[node] of a finished slot, -1 for a live or unused one.
+// Where the table is read: in phase 1 lane r < W loads node[r] (clamped: whatever the caller left there addresses the table) and the
+// six-word record of that node (ctc_trie_fetch: one 24-byte request per slot and step, next to the score and the state) and parks
+// the mask as two 64-bit words, first_child, word_id and the node in LDS - 28 B per slot, 448 B beside the 20.2 KB above.  Phase 2
+// reads the two mask words of slot r at a wave-uniform address (a broadcast) and writes -inf instead of the sum where the lane's bit
+// is clear.  In phase 3 lane r derives its new node from the winner's record, which still stands; a slot that finishes takes the word
+// id from there too, so the last step needs no second fetch.  The cost is a beam step's, whatever the size of the lexicon.
+//
 // Reorder kernel: pure data movement.  One thread owns the same 16-byte piece of the K | V columns of one (layer, sample, position)
 // in all W rows: it loads the piece of row parent[r] for every r whose parent differs (compile-time register index r, the gather is
 // in the address: nothing goes to scratch), waits for all loads, then stores row r.  Cycles (0 <-> 1) and shared parents are safe
@@ -44,13 +63,37 @@ struct NrtrBeamWave {
     unsigned short tok[NRTR_MAX_BEAM][NRTR_MAX_LEN];
 };
 
+template <bool kTrie>
+struct NrtrBeamTrieWave {};                                        // (nothing without a lexicon trie)
+template <>
+struct NrtrBeamTrieWave<true> {
+    unsigned long long allow[NRTR_MAX_BEAM][2];                    // bit k & 63 of [r][k >> 6]: the node of slot r has a child by bit k
+    int node[NRTR_MAX_BEAM], first[NRTR_MAX_BEAM], word[NRTR_MAX_BEAM];    // the node of slot r, its first child, the word that ends there
+};
+
+struct NrtrBeamTrie {                                              // the lexicon trie of a launch (unused without one)
+    const int* nodes;                                              // int32 [n_nodes, 8]: ccd_ctc_beam_search_trie's table
+    int n_nodes, class_offset;                                     // class c of the decoder is bit c + class_offset of a mask
+    int* node;                                                     // int32 [B, W], in and out: the node of every slot
+    int* word_ids;                                                 // int32 [B, W], written with the paths
+};
+
+// Bit k of the 128-bit mask (m0 the low half); a k above 127 has no bit.
+__device__ __forceinline__ bool nrtr_trie_bit(unsigned long long m0, unsigned long long m1, int k) {
+    return k <= 127 && (((k < 64 ? m0 >> k : m1 >> (k - 64)) & 1ull) != 0ull);
+}
+
 // grid = B, block = 64.  The launcher has checked 1 <= W <= 16, 1 <= C <= 128, 0 <= step, step + 2 <= seq_len <= 128, end_idx in
-// [0, C), pad_idx in [0, 65536).  paths / lengths / hyp_scores: all three or none.
+// [0, C), pad_idx in [0, 65536).  paths / lengths / hyp_scores: all three or none.  Every line the trie adds sits behind `if constexpr
+// (kTrie)` (`trie` is not looked at without one; with one the launcher has checked n_nodes >= 1, class_offset in {0, 1}, and word_ids
+// comes with the paths): the `false` instance is the kernel as it was.
+template <bool kTrie>
 __global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restrict__ logits, long ldl, int W, int C, int step, int end_idx,
                                                             int pad_idx, long long* seq, int seq_len, ctc_real* score, int* state,
                                                             int* __restrict__ parent, int* __restrict__ paths, int* __restrict__ lengths,
-                                                            float* __restrict__ hyp_scores) {
+                                                            float* __restrict__ hyp_scores, NrtrBeamTrie trie) {
     __shared__ NrtrBeamWave s;
+    __shared__ NrtrBeamTrieWave<kTrie> tr;
     const int lane = lane_id(), b = blockIdx.x;
     const int c0 = lane, c1 = lane + 64;
     const bool has0 = c0 < C, has1 = c1 < C;
@@ -68,6 +111,21 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restr
         s.score[lane] = my_score;
         s.state[lane] = my_state;
     }
+    if constexpr (kTrie) {
+        int rec[CTC_TRIE_RECORD] = {0, 0, 0, 0, 0, -1}, my_node = 0;       // (a slot behind W: no edge, no word)
+        if (lane < W) {
+            const int n = trie.node[row0 + lane];
+            my_node = n < 0 ? 0 : (n >= trie.n_nodes ? trie.n_nodes - 1 : n);
+            ctc_trie_fetch(trie.nodes, my_node, rec);
+        }
+        if (lane < NRTR_MAX_BEAM) {
+            tr.allow[lane][0] = (unsigned long long)(unsigned)rec[0] | ((unsigned long long)(unsigned)rec[1] << 32);
+            tr.allow[lane][1] = (unsigned long long)(unsigned)rec[2] | ((unsigned long long)(unsigned)rec[3] << 32);
+            tr.first[lane] = rec[4];
+            tr.word[lane] = rec[5];
+            tr.node[lane] = my_node;
+        }
+    }
     for (int r = 0; r < W; ++r) {
         const long long* const q = seq + (row0 + r) * seq_len;
         if (c0 <= step) s.tok[r][c0] = (unsigned short)q[c0];
@@ -82,8 +140,17 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restr
         if (st == NRTR_LIVE) {
             const float* const x = logits + (row0 + r) * ldl;
             const CtcReal2 lp = beam_wave_log_probs(has0 ? x[c0] : ninf, has1 ? x[c1] : ninf, has0, has1, false, s.cand[r], C);
-            if (has0) s.cand[r][c0] = sc + lp.c0;                          // (-inf stays -inf: a score is finite or -inf)
-            if (has1) s.cand[r][c1] = sc + lp.c1;
+            if constexpr (kTrie) {                                         // an extension the trie has no edge for, an end where no
+                const unsigned long long m0 = tr.allow[r][0], m1 = tr.allow[r][1];             // word ends: no candidate
+                const bool word = tr.word[r] >= 0;
+                const bool ok0 = c0 == end_idx ? word : nrtr_trie_bit(m0, m1, c0 + trie.class_offset);
+                const bool ok1 = c1 == end_idx ? word : nrtr_trie_bit(m0, m1, c1 + trie.class_offset);
+                if (has0) s.cand[r][c0] = ok0 ? sc + lp.c0 : ctc_neg_inf();
+                if (has1) s.cand[r][c1] = ok1 ? sc + lp.c1 : ctc_neg_inf();
+            } else {
+                if (has0) s.cand[r][c0] = sc + lp.c0;                      // (-inf stays -inf: a score is finite or -inf)
+                if (has1) s.cand[r][c1] = sc + lp.c1;
+            }
         } else {
             const bool carry = st == NRTR_FINISHED;
             if (has0) s.cand[r][c0] = carry && c0 == end_idx ? sc : ctc_neg_inf();
@@ -95,6 +162,7 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restr
     // ---- 3. the W best, one per round; lane r keeps the slot of rank r
     ctc_real new_score = ctc_neg_inf();
     int new_state = NRTR_UNUSED, new_parent = -1, new_tok = pad_idx;
+    int new_node = 0, new_word = -1;                                       // kTrie: the node of the new slot; its word, if it has finished
     for (int r = 0; r < W; ++r) {
         ctc_real best = ctc_neg_inf();
         int best_k = 0x7fffffff;
@@ -124,6 +192,15 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restr
                 new_parent = i;
                 new_state = was_finished || c == end_idx ? NRTR_FINISHED : NRTR_LIVE;
                 new_tok = was_finished ? pad_idx : c;
+                if constexpr (kTrie) {                                     // the parent's record, which phase 1 left standing
+                    if (new_state == NRTR_FINISHED) {
+                        new_node = tr.node[i];
+                        new_word = tr.word[i];
+                    } else {
+                        const int child = ctc_trie_child(tr.first[i], tr.allow[i][0], tr.allow[i][1], c + trie.class_offset);
+                        new_node = child < 0 ? 0 : (child >= trie.n_nodes ? trie.n_nodes - 1 : child);
+                    }
+                }
             }
         }
         wave_lds_fence();
@@ -135,6 +212,10 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restr
         state[row0 + lane] = new_state;
         parent[row0 + lane] = new_parent;
         if (hyp_scores) hyp_scores[row0 + lane] = new_state == NRTR_UNUSED ? ninf : (float)new_score;
+        if constexpr (kTrie) {
+            trie.node[row0 + lane] = new_node;
+            if (paths) trie.word_ids[row0 + lane] = new_word;              // (a live or an unused slot is no word: -1)
+        }
     }
     const int T = seq_len - 1;
     for (int r = 0; r < W; ++r) {

@@ -99,6 +99,7 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
         self._graphs = {}
         self.beam_width = 0            # forward_beam's default width (DINO_Finetune sets it from decoder.beam_width); 0: none
         self._beam_graphs = {}
+        self._trie_graphs = {}         # forward_beam(trie=): graphs of their own, keyed by the trie as well
 
     def _transposed_names(self):
         names = []
@@ -165,25 +166,37 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
         key = (tuple(out_enc.shape), out_enc.device, self.arena.flat.data_ptr())
         return self._replay(self._graphs, key, lambda x: fe.greedy_decode(self, x), out_enc).clone()
 
-    def forward_beam(self, feat, out_enc, beam_width=None):
+    def forward_beam(self, feat, out_enc, beam_width=None, trie=None):
         """Beam search of width `beam_width` (default: self.beam_width, which must then be > 0) -> (paths int32 [N, W, max_seq_len] by
         rank, -1-padded; lengths int32 [N, W], -1 for an unused slot; scores fp32 [N, W], the log-probability of the word with its
         <EOS>, -inf for an unused slot): fe.beam_decode.  On the GPU the loop is captured into a HIP graph per (batch shape, width) and
-        replayed, as forward_test's (CCD_DECODE_GRAPH=0: eager)."""
-        from ..ops import NRTR_MAX_BEAM
+        replayed, as forward_test's (CCD_DECODE_GRAPH=0: eager).
+        trie: an ops.ctc_lexicon_trie handle (AttnConvertor.lexicon_trie: rows class + 1) - the beam walks the lexicon's prefix tree
+        and a fourth tensor comes back, word_ids int32 [N, W]: the lexicon row of every finished hypothesis, -1 for a slot that is
+        unused or still a prefix.  The trie's device copy is made before the capture; the graphs of this path are kept apart from
+        the plain beam's, one per (batch shape, width, trie)."""
+        from ..ops import NRTR_MAX_BEAM, CTCLexiconTrie
+        if trie is not None and not isinstance(trie, CTCLexiconTrie):
+            raise TypeError(f"forward_beam: trie must come from ops.ctc_lexicon_trie, got {type(trie).__name__}")
         width = int(self.beam_width if beam_width is None else beam_width)
         if not 1 <= width <= NRTR_MAX_BEAM:
             raise ValueError(f"forward_beam: beam_width must lie in 1..{NRTR_MAX_BEAM}, got {width}")
         self._ready()
         out_enc = out_enc.to(torch.bfloat16)
+        if trie is not None:
+            trie.on(out_enc.device)                        # the upload happens here, never inside a capture
         if out_enc.is_cuda and os.environ.get("CCD_DECODE_GRAPH", "1") != "0":
-            return self._graphed_beam(out_enc, width)
-        return fe.beam_decode(self, out_enc, width)
+            return self._graphed_beam(out_enc, width, trie)
+        return fe.beam_decode(self, out_enc, width, trie)
 
-    def _graphed_beam(self, out_enc, width):
-        """One graph per (batch shape, arena, width)."""
+    def _graphed_beam(self, out_enc, width, trie=None):
+        """One graph per (batch shape, arena, width) and, with a trie, per trie: the graph holds the address of its device copy, which
+        the handle keeps alive as long as the entry keeps the handle."""
         key = (tuple(out_enc.shape), out_enc.device, self.arena.flat.data_ptr(), width)
-        out = self._replay(self._beam_graphs, key, lambda x: fe.beam_decode(self, x, width), out_enc)
+        if trie is None:
+            out = self._replay(self._beam_graphs, key, lambda x: fe.beam_decode(self, x, width), out_enc)
+        else:
+            out = self._replay(self._trie_graphs, key + (trie,), lambda x: fe.beam_decode(self, x, width, trie), out_enc)
         return tuple(t.clone() for t in out)
 
     def forward_test_speed(self, feat, out_enc, img_metas=None):

@@ -411,14 +411,17 @@ def greedy_decode(module, out_enc, stop_on_eos_of_first=False):
 
 
 @torch.no_grad()
-def beam_decode(module, out_enc, beam_width):
+def beam_decode(module, out_enc, beam_width, trie=None):
     """Beam search of width W over the incremental decoder of `greedy_decode` (the rules: INTEGRATION.md, "Beam search over the NRTR
     decoder"; kernels/nrtr_beam.h) -> (paths int32 [B, W, max_seq_len] by rank, -1-padded; lengths int32 [B, W]; scores fp32 [B, W]),
     as ops.ctc_beam_search returns them.  The W hypotheses of a sample are rows b * W .. b * W + W - 1 of every activation: the
     self-attention runs per hypothesis (B * W samples, causal, padding mask from the hypothesis' own tokens), the encoder-decoder
     attention takes them as the W queries of sample b, so the encoder keys and values are never replicated.  Every step ends with the
     selection (ops.nrtr_beam_step) and the permutation of the cached keys and values by the parents (ops.nrtr_beam_reorder).  No length
-    normalisation, no early exit: all max_seq_len steps run, nothing is read back."""
+    normalisation, no early exit: all max_seq_len steps run, nothing is read back.
+    trie: an ops.ctc_lexicon_trie handle whose rows are class + 1 (AttnConvertor.set_lexicon) - the selection walks the lexicon's
+    prefix tree (ops.nrtr_beam_step_trie: a slot extends only along an edge and ends only where a word ends, at the plain beam's scores)
+    and the result gains word_ids int32 [B, W], the lexicon row of every finished hypothesis (-1: unused, or still a prefix)."""
     arena, pre, spec = module.arena, module.arena_prefix, module.dec_spec
     B, W = out_enc.shape[0], int(beam_width)
     D, L, C = spec.D, spec.L, spec.C
@@ -429,10 +432,15 @@ def beam_decode(module, out_enc, beam_width):
     kv = encoder_kv(arena, pre, spec, out_enc.reshape(-1, D))
     seq, score, state, parent = ops.nrtr_beam_state(B, W, T, spec.start_idx, spec.padding_idx, dev)
     cache = torch.zeros((L, R * T, 3 * D), dtype=BF16, device=dev)     # q | k | v of position t of every hypothesis
+    node = ops.nrtr_beam_trie_state(B, W, dev) if trie is not None else None
     out = None
     for s in range(steps):
         logits = decoder_position(module, s, seq, cache, kv, R, W)                           # W queries per sample
-        out = ops.nrtr_beam_step(logits, C, s, spec.start_idx, spec.padding_idx, seq, score, state, parent, final=s == steps - 1)
+        if trie is not None:
+            out = ops.nrtr_beam_step_trie(logits, C, s, spec.start_idx, spec.padding_idx, seq, score, state, parent, node, trie,
+                                          class_offset=1, final=s == steps - 1)
+        else:
+            out = ops.nrtr_beam_step(logits, C, s, spec.start_idx, spec.padding_idx, seq, score, state, parent, final=s == steps - 1)
         if s + 1 < steps and W > 1:
             ops.nrtr_beam_reorder(cache, parent, T, s)
     return out

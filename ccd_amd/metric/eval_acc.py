@@ -24,6 +24,8 @@ probable word OF THE LEXICON instead: ops.ctc_lexicon_score on the probabilities
 the word list into -1-padded paths, ops.text_score_paths - no host synchronisation either (host path: `tensor2lexicon`).  An AttnConvertor with `beam_width` > 0
 makes `compute` decode by beam search over the NRTR decoder (`DINO_Finetune.forward_beam`) and score the best word the same way
 (`update_paths`; on the host path: `idx2str` of `paths2nbest`); `forward_test` itself stays greedy.
+An AttnConvertor with a lexicon (and its `lexicon_beam`) makes `compute` decode over that closed vocabulary instead: rank 0 of
+`DINO_Finetune.forward_lexicon`'s paths through `update_paths` - no host synchronisation (host path: `paths2lexicon`).
 """
 from __future__ import annotations
 
@@ -204,25 +206,30 @@ class TextAccuracy:
         device = next(net.parameters()).device
         convertor = net.label_convertor
         attn_beam = not is_ctc(convertor) and getattr(convertor, "beam_width", 0) > 0     # beam search over the NRTR decoder, rank 0 scored
+        attn_lexicon = not is_ctc(convertor) and getattr(convertor, "lexicon", None) is not None     # ... along the lexicon's prefix tree
         if device.type == "cuda" and not self.case_sensitive and convertor.score_table() is not None:
             for image_tensors, label_tensors in dataloader:
                 image_tensors = image_tensors.to(device)
                 span = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 span[0].record()
-                if attn_beam:
+                if attn_lexicon:
+                    self.update_paths(net.forward_lexicon(image_tensors)[2][:, 0], list(label_tensors[0]), convertor)
+                elif attn_beam:
                     self.update_paths(net.forward_beam(image_tensors, convertor.beam_width)[0][:, 0], list(label_tensors[0]), convertor)
                 else:
                     out_dec = model(image_tensors, text=None, return_loss=False, test_speed=False)
                     self.update_scores(out_dec.float(), list(label_tensors[0]), convertor)
                 span[1].record()
                 self._spans.append(span)                                      # read in result(), behind its copy
-                if on_batch is not None and not attn_beam:
+                if on_batch is not None and not attn_beam and not attn_lexicon:
                     on_batch(out_dec.float(), list(label_tensors[0]))
             return self.result()
         for image_tensors, label_tensors in dataloader:
             image_tensors = image_tensors.to(device)
             start = time.time()
-            if attn_beam:
+            if attn_lexicon:
+                nbest = convertor.paths2lexicon(*net.forward_lexicon(image_tensors)[:2], nbest=1)[0]
+            elif attn_beam:
                 nbest = convertor.paths2nbest(*net.forward_beam(image_tensors, convertor.beam_width))[0]
             else:
                 out_dec = model(image_tensors, text=None, return_loss=False, test_speed=False)
@@ -234,6 +241,6 @@ class TextAccuracy:
             pt_text = convertor.idx2str(label_indexes)
             self.inference_time += time.time() - start
             self.update(list(label_tensors[0]), pt_text)
-            if on_batch is not None and not attn_beam:
+            if on_batch is not None and not attn_beam and not attn_lexicon:
                 on_batch(out_dec.float(), list(label_tensors[0]))
         return self.result()

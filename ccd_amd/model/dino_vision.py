@@ -150,9 +150,11 @@ class DINO_Finetune(ArenaModule):
     `decoder.type: 'CTCDecoder'` builds the CTC head instead (no reference counterpart): backbone -> CTCDecoder (frame pooling + one
     linear layer) -> CTCLoss, with a CTCConvertor; there is no `encoder` Mlp then.  `decoder.beam_width` > 0 makes evaluation decode by
     CTC prefix beam search of that width (absent or 0: the greedy rule); `decoder.lexicon: <path>` makes it pick the most probable word
-    of that word list instead (CTC head only; the NRTR head refuses a lexicon).  Any other type builds the NRTR recogniser; there
+    of that word list instead.  Any other type builds the NRTR recogniser; there
     `decoder.beam_width` > 0 is the width of `forward_beam` (beam search over the attention decoder: n-best words with their
-    log-probabilities), which TextAccuracy then scores the best word of.  `forward_test` and `forward_test_speed` return the greedy
+    log-probabilities), which TextAccuracy then scores the best word of, and `decoder.lexicon: <path>` together with
+    `decoder.lexicon_beam: N` (1..16; either alone is refused) makes evaluation decode over that word list instead: `forward_lexicon`,
+    a beam of width N along the lexicon's prefix tree.  `forward_test` and `forward_test_speed` return the greedy
     probabilities whatever the width: a beam has no per-step distribution to return."""
 
     def __init__(self, config):
@@ -167,8 +169,8 @@ class DINO_Finetune(ArenaModule):
         from ..modules import vision_transformer as vits
         self.label_convertor = AttnConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len, with_unknown=True,
                                              beam_width=int(getattr(config, "decoder_beam_width", 0) or 0),     # absent or 0: greedy
-                                             lexicon=getattr(config, "decoder_lexicon", None) or None,          # (refused: CTC head only)
-                                             lexicon_beam=int(getattr(config, "decoder_lexicon_beam", 0) or 0),  # (refused as well)
+                                             lexicon=getattr(config, "decoder_lexicon", None) or None,          # absent: no lexicon; with
+                                             lexicon_beam=int(getattr(config, "decoder_lexicon_beam", 0) or 0),  # its beam (alone: refused)
                                              lm=getattr(config, "decoder_lm", None) or None)                    # (refused as well)
         config.arch = config.arch.replace("deit", "vit")
         if config.arch not in vits.__dict__:
@@ -267,6 +269,25 @@ class DINO_Finetune(ArenaModule):
             raise NotImplementedError("forward_beam is the NRTR head's; the CTC head's beam is CTCConvertor.tensor2nbest on forward_test")
         feat = self.extract_feat(img)
         return self.decoder.forward_beam(feat, self.encoder(feat), beam_width)
+
+    def forward_lexicon(self, img, lexicon_beam=None):
+        """img [N,3,32,128] -> (word_ids int32 [N, W], log_probs fp32 [N, W], paths int32 [N, W, max_seq_len], lengths int32 [N, W]), best
+        first: the W most probable words OF THE LEXICON the beam over the NRTR decoder finds along the lexicon's prefix tree
+        (NRTRDecoder.forward_beam with the convertor's trie; W defaults to `decoder.lexicon_beam`).  word_ids are positions in
+        label_convertor.lexicon_words, log_probs the exact log p(word <EOS> | image) - a hypothesis has one path, so the beam's
+        score is the word's probability, comparable across words.  An empty slot is (-1, -inf, all -1, -1).  Device tensors, nothing
+        is read back; AttnConvertor.paths2lexicon is the host-side view."""
+        if self.ctc:
+            raise NotImplementedError("forward_lexicon is the NRTR head's; the CTC head's lexicon decoding is CTCConvertor.tensor2lexicon "
+                                      "on forward_test")
+        conv = self.label_convertor
+        if conv.lexicon_trie is None:
+            raise ValueError("forward_lexicon: the convertor has no lexicon (decoder.lexicon with decoder.lexicon_beam, or "
+                             "label_convertor.set_lexicon)")
+        width = conv.lexicon_beam if lexicon_beam is None else conv._checked_lexicon_beam(lexicon_beam)
+        feat = self.extract_feat(img)
+        paths, lengths, scores, word_ids = self.decoder.forward_beam(feat, self.encoder(feat), width, trie=conv.lexicon_trie)
+        return word_ids, torch.where(word_ids >= 0, scores, float("-inf")), paths, lengths
 
     @torch.no_grad()
     def forward_chars(self, img, words=None, nbest=1):

@@ -1305,6 +1305,53 @@ def nrtr_beam_step(logits, C, step, end_idx, pad_idx, seq, score, state, parent,
     return out if final else None
 
 
+def nrtr_beam_trie_state(B, beam_width, device):
+    """The trie node of every slot in front of step 0 -> node int32 [B, W], all zeros: the root of the lexicon's prefix tree."""
+    W = int(beam_width)
+    if not 1 <= W <= NRTR_MAX_BEAM:
+        raise ValueError(f"nrtr_beam_trie_state: beam_width must lie in 1..{NRTR_MAX_BEAM}, got {beam_width}")
+    return torch.zeros((B, W), dtype=I32, device=device)
+
+
+def nrtr_beam_step_trie(logits, C, step, end_idx, pad_idx, seq, score, state, parent, node, trie, class_offset=1, final=False):
+    """nrtr_beam_step along the prefix tree of a lexicon (kernels/nrtr_beam.h: nrtr_beam_step_kernel<true>), in place: node int32 [B, W]
+    (nrtr_beam_trie_state) is the trie node of every slot, trie a ctc_lexicon_trie handle whose mask bit for class c is c + class_offset
+    (1: the lexicon's rows are class + 1, AttnConvertor.set_lexicon's layout; 0: the classes themselves).  A live slot extends only
+    along an edge of its node and ends only where a word ends; the scores are nrtr_beam_step's, so a finished slot holds the exact
+    log-probability of its word with the <EOS>.  final=True returns (paths, lengths, hyp_scores) as nrtr_beam_step does and word_ids
+    int32 [B, W]: the lexicon row of every finished slot, -1 for a slot that is unused or still live."""
+    if not isinstance(trie, CTCLexiconTrie):
+        raise TypeError(f"nrtr_beam_step_trie: trie must come from ctc_lexicon_trie, got {type(trie).__name__}")
+    if score.dim() != 2 or not 1 <= score.shape[1] <= NRTR_MAX_BEAM:
+        raise ValueError(f"nrtr_beam_step_trie: score must be [B, W] with W in 1..{NRTR_MAX_BEAM}, got {list(score.shape)}")
+    B, W = score.shape
+    for name, t, dtype in (("score", score, F64), ("state", state, I32), ("parent", parent, I32), ("node", node, I32), ("seq", seq, I64),
+                           ("logits", logits, F32)):
+        if t.dtype != dtype:
+            raise ValueError(f"nrtr_beam_step_trie: {name} must be {dtype}, got {t.dtype}")
+    for name, t in (("score", score), ("state", state), ("parent", parent), ("node", node)):
+        if tuple(t.shape) != (B, W) or not t.is_contiguous():
+            raise ValueError(f"nrtr_beam_step_trie: {name} must be contiguous [{B}, {W}], got {list(t.shape)}")
+    if seq.dim() != 2 or seq.shape[0] != B * W or not seq.is_contiguous():
+        raise ValueError(f"nrtr_beam_step_trie: seq must be contiguous [{B * W}, seq_len], got {list(seq.shape)}")
+    if logits.dim() != 2 or logits.shape[0] != B * W or logits.stride(1) != 1 or not 1 <= int(C) <= logits.shape[1]:
+        raise ValueError(f"nrtr_beam_step_trie: expects logits [{B * W}, >= {C}] with dense rows, got {list(logits.shape)}")
+    seq_len = seq.shape[1]
+    if not 0 <= int(step) <= seq_len - 2:
+        raise ValueError(f"nrtr_beam_step_trie: step must lie in 0..seq_len - 2 = {seq_len - 2}, got {step}")
+    if not 0 <= int(end_idx) < int(C) or not 0 <= int(pad_idx) < 65536:
+        raise ValueError(f"nrtr_beam_step_trie: end_idx must lie in [0, {C}) and pad_idx in [0, 65536), got {end_idx}, {pad_idx}")
+    if isinstance(class_offset, bool) or class_offset not in (0, 1):
+        raise ValueError(f"nrtr_beam_step_trie: class_offset must be 0 or 1, got {class_offset!r}")
+    out = (None, None, None, None)
+    if final:
+        out = (torch.empty((B, W, seq_len - 1), dtype=I32, device=seq.device), torch.empty((B, W), dtype=I32, device=seq.device),
+               torch.empty((B, W), dtype=F32, device=seq.device), torch.empty((B, W), dtype=I32, device=seq.device))
+    _call("ccd_nrtr_beam_step_trie", logits, logits.stride(0), B, W, int(C), int(step), int(end_idx), int(pad_idx), seq, seq_len, score,
+          state, parent, *out[:3], trie.on(seq.device), trie.n_nodes, int(class_offset), node, out[3])
+    return out if final else None
+
+
 def nrtr_beam_reorder(cache, parent, positions, step):
     """The decode loop's cache bf16 [L, B * W * positions, 3 D] (q | k | v of position t of slot r of sample b in row (b * W + r) *
     positions + t), in place: for every position <= step, the K and V columns of slot r become those of slot parent[r] (int32 [B, W];

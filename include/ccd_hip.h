@@ -643,6 +643,30 @@ int ccd_ctc_align(const float* scores, long sample_stride, long step_stride, int
 int ccd_nrtr_beam_step(const float* logits, long ldl, int batch, int beam, int classes, int step, int end_idx, int pad_idx, int64_t* seq,
                        int seq_len, double* score, int* state, int* parent, int* paths, int* lengths, float* hyp_scores, void* stream);
 int ccd_nrtr_beam_reorder(ccd_bf16* cache, const int* parent, int layers, int batch, int beam, int positions, int D, int step, void* stream);
+/* Beam search over the NRTR decoder along a lexicon's prefix tree (ABI 27; kernels/nrtr_beam.h: nrtr_beam_step_kernel<true>, restated
+ * in numpy in tests/nrtr_trie_np.py): ccd_nrtr_beam_step with a trie node per slot.  Everything ccd_nrtr_beam_step takes means what it
+ * means there, and a finished or unused slot behaves as it does there.
+ *   nodes         int32 [n_nodes, 8]: the table of ccd_ctc_beam_search_trie (the layout is stated there).  Class c of the decoder is
+ *                 bit c + class_offset of a node's child mask; class_offset is 1 where the lexicon's rows are class + 1 (the decoder's
+ *                 class 0 is a character and the trie never sets bit 0), 0 where they are the classes themselves.
+ *   node          int32 [batch, beam], read and written in place like score and state: the node of every slot.  Before step 0: all 0,
+ *                 the root (a caller may start a sample at another node).  A value outside [0, n_nodes) is clamped into it.
+ *   A live slot r at node n gives the candidate (r, c), c != end_idx, iff c + class_offset <= 127 and that bit of mask[n] is set, and
+ *                 (r, end_idx) iff word_id[n] >= 0; every other candidate is -inf: never selected.  The score of an allowed candidate
+ *                 is ccd_nrtr_beam_step's - the log-softmax runs over all `classes` and is not renormalised - so the score of a finished
+ *                 slot is the exact log p(word <EOS> | image).  The selection key and the tie rule are unchanged.  A sample whose live
+ *                 slots have no allowed candidate of finite score ends with unused slots only.
+ *   A selected extension carries first_child[n] + popcount(mask[n] bits below c + class_offset), clamped to [0, n_nodes): a malformed
+ *                 table gives wrong words, never an access outside it.  A selected end_idx and a carried finished slot keep their node;
+ *                 an unused slot's node is 0.
+ *   word_ids      int32 [batch, beam], written with paths / lengths / hyp_scores (all four or none): word_id[node] of a finished slot, -1
+ *                 for an unused slot and for a slot that is still live - a prefix, no word.
+ * No atomics: the same input gives the same bits.  batch == 0 is a no-op.  CCD_EINVAL: a missing pointer (nodes and node included), a
+ * negative size, stride or step, paths / lengths / hyp_scores / word_ids given in part; CCD_ESHAPE: everything ccd_nrtr_beam_step
+ * refuses, n_nodes < 1, class_offset outside 0..1.  Nothing is launched on an error. */
+int ccd_nrtr_beam_step_trie(const float* logits, long ldl, int batch, int beam, int classes, int step, int end_idx, int pad_idx,
+                            int64_t* seq, int seq_len, double* score, int* state, int* parent, int* paths, int* lengths,
+                            float* hyp_scores, const int* nodes, int n_nodes, int class_offset, int* node, int* word_ids, void* stream);
 
 /* ---------------------------------------------------------------- DINOHead pieces, vit.py:313,326 */
 int ccd_l2norm_fwd(const ccd_bf16* x, ccd_bf16* y, float* inv, int max_rows, const int* d_rows, int rows_mul, int D,

@@ -94,10 +94,12 @@ def main():
     ap.add_argument("--beam_width", type=int, default=None,
                     help="beam search of this width, 1..16, for either head (CTC: prefix beam search; NRTR: beam over the decoder); 0: greedy decoding")
     ap.add_argument("--lexicon", type=str, default=None,
-                    help="evaluate the CTC head with lexicon-constrained decoding over this UTF-8 word list (one word per line); excludes a beam")
+                    help="evaluate with lexicon-constrained decoding over this UTF-8 word list (one word per line); excludes a beam.  The NRTR "
+                         "head needs --lexicon_beam with it")
     ap.add_argument("--lexicon_beam", type=int, default=None,
                     help="with a lexicon: search its prefix tree with a beam of this width, 1..16, and score only the proposed words "
-                         "exactly - the cost no longer grows with the lexicon; 0: score every word")
+                         "exactly - the cost no longer grows with the lexicon; 0: score every word (CTC head).  NRTR head: the width of the "
+                         "beam over the decoder that walks the lexicon's prefix tree, 1..16; its scores are exact already")
     ap.add_argument("--lm", type=str, default=None,
                     help="fuse a character n-gram language model into the CTC beam search: an .npz of CharNGram.save, or a UTF-8 word list "
                          "(estimated at decoder.lm_order); needs a beam, excludes a lexicon")
@@ -131,7 +133,8 @@ def main():
     torch.cuda.set_device(device)
     model = DINO_Finetune(config).to(device)
     if getattr(model.label_convertor, "lexicon_stats", None):
-        logging.info(f"lexicon {config.decoder_lexicon}: {model.label_convertor.lexicon_stats}")
+        logging.info(f"lexicon {config.decoder_lexicon} (lexicon_beam {getattr(model.label_convertor, 'lexicon_beam', 0)}): "
+                     f"{model.label_convertor.lexicon_stats}")
     if getattr(model.label_convertor, "lm_stats", None):
         conv = model.label_convertor
         logging.info(f"language model {config.decoder_lm}: {conv.lm_stats}, weight {conv.lm_weight}, bonus {conv.lm_bonus}, eos {conv.lm_eos}")

@@ -2,6 +2,7 @@
 """Time beam search over the NRTR decoder (kernels/nrtr_beam.h, finetune_engine.beam_decode) on the GPU.
 
     python tools/nrtr_beam_bench.py [--iters 30] [--rounds 5] [--out profiles/nrtr_beam.json]
+    python tools/nrtr_beam_bench.py --cases trie --out profiles/nrtr_beam_trie.json
 
 The cases, each in a process of its own under its own time limit; the next one starts only if the one before ended well:
   kernels  ccd_nrtr_beam_step and ccd_nrtr_beam_reorder per launch at B = 512, T = 25, C = 92 (logits rows 128 wide), D = 512,
@@ -13,6 +14,11 @@ The cases, each in a process of its own under its own time limit; the next one s
   rescore  the yardstick of tests/test_nrtr_beam_gpu.py: with that test's model (vit_tiny, 2 decoder layers, its seed, images and
            <EOS> bias) the largest |sum log p_incremental - sum log p_full| along the greedy paths of greedy_decode against
            greedy_decode_full ("rescore_base"; the test gates the beam's scores against teacher forcing at 4 x that).
+  trie     (not part of a default run) the lexicon-constrained beam: ccd_nrtr_beam_step_trie per launch at widths 4, 8, 16 over
+           synthetic lexicons of 1 000 / 10 000 / 90 000 words of 2..15 characters, next to ccd_nrtr_beam_step in the same process
+           on the same logits, both on a state eight steps into their own decode (with how many of its slots are still live: a
+           finished slot costs no log-softmax); then evaluation images/s at B = 512, vit_small: forward_lexicon with lexicon_beam
+           8 and 16 (the 10 000-word lexicon) against forward_beam at widths 8 and 16, rounds alternating.
 Warm-up first, HIP events around every timed call, a figure is the median of the round medians with the lowest and highest
 round.  No threshold is set; the file records what was measured.  `--case NAME` runs one case and prints its JSON line."""
 import argparse
@@ -27,7 +33,8 @@ sys.path.insert(0, ROOT)
 
 B, T, C, D, L = 512, 25, 92, 512, 6
 WIDTHS = (1, 4, 8, 16)
-LIMITS = {"kernels": 240, "eval": 420, "rescore": 180}                   # seconds per case
+LIMITS = {"kernels": 240, "eval": 420, "rescore": 180, "trie": 600}      # seconds per case
+TRIE_WIDTHS, TRIE_LEXICONS = (4, 8, 16), (1000, 10000, 90000)
 
 
 def event_ms(fn, iters):
@@ -156,7 +163,98 @@ def case_rescore(a):
     return out
 
 
-CASES = {"kernels": case_kernels, "eval": case_eval, "rescore": case_rescore}
+def synthetic_lexicon(n, seed=0):
+    """n distinct words of 2..15 of the classes 0..90, sorted -> a list of tuples."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    words = set()
+    while len(words) < n:
+        words.add(tuple(int(c) for c in rng.integers(0, 91, int(rng.integers(2, 16)))))
+    return sorted(words)
+
+
+def case_trie(a):
+    import numpy as np
+    import torch
+    from ccd_amd import finetune as ft, ops
+    dev = torch.device("cuda")
+    out = {"shape": {"B": B, "T": T, "C": C, "D": D, "L": L}, "lexicons": {}}
+    tries = {}
+    for n in TRIE_LEXICONS:
+        words = synthetic_lexicon(n, seed=n)
+        rows = np.zeros((n, 15), dtype=np.int64)
+        for row, w in zip(rows, words):
+            row[:len(w)] = np.asarray(w) + 1                                      # AttnConvertor.set_lexicon's layout: class + 1
+        tries[n] = ops.ctc_lexicon_trie(ops.ctc_lexicon(torch.from_numpy(rows)))
+        out["lexicons"][str(n)] = dict(tries[n].stats)
+    for W in TRIE_WIDTHS:
+        g = torch.Generator().manual_seed(W)
+        logits = torch.randn(B * W, 128, generator=g) * 2.0
+        logits.scatter_add_(1, torch.randint(0, C, (B * W, 1), generator=g), torch.full((B * W, 1), 6.0))
+        logits = logits.to(dev)
+        sides = {}
+        for name in ["plain"] + [str(n) for n in TRIE_LEXICONS]:
+            trie = None if name == "plain" else tries[int(name)]
+            seq, score, state, parent = ops.nrtr_beam_state(B, W, T + 1, C - 1, C, dev)
+            node = ops.nrtr_beam_trie_state(B, W, dev)
+
+            def launch(s, rows, seq=seq, score=score, state=state, parent=parent, node=node, trie=trie):
+                if trie is None:
+                    ops.nrtr_beam_step(rows, C, s, C - 1, C, seq, score, state, parent)
+                else:
+                    ops.nrtr_beam_step_trie(rows, C, s, C - 1, C, seq, score, state, parent, node, trie)
+
+            for s in range(8):                                                    # eight steps into its own decode
+                launch(s, logits.roll(s, 0))
+            live = int((state == ops.NRTR_LIVE).sum())
+            used = int((state != ops.NRTR_UNUSED).sum())
+            tensors = (seq, score, state, node)
+            saved = [t.clone() for t in tensors]
+
+            def restore(tensors=tensors, saved=saved):
+                for t, keep in zip(tensors, saved):
+                    t.copy_(keep)
+
+            def step(restore=restore, launch=launch):
+                restore()
+                launch(8, logits)
+
+            sides[name] = {"step": step, "restore": restore, "with_copy": [], "copies": [], "live": live, "used": used}
+        for _ in range(a.rounds):                                                 # rounds alternate between the sides
+            for side in sides.values():
+                side["with_copy"].append(event_ms(side["step"], a.iters))
+                side["copies"].append(event_ms(side["restore"], a.iters))
+        entry = {}
+        for name, side in sides.items():
+            e = {"step_with_state_restore": summary(side["with_copy"]), "state_restore_alone": summary(side["copies"])}
+            e["step_kernel_ms"] = round(e["step_with_state_restore"]["median_ms"] - e["state_restore_alone"]["median_ms"], 4)
+            e["slots_live_at_the_timed_step"] = f"{side['live']} of {B * W} ({side['used']} in use)"
+            entry["ccd_nrtr_beam_step" if name == "plain" else f"ccd_nrtr_beam_step_trie_{name}_words"] = e
+        out[f"w{W}"] = entry
+    # evaluation images/s: the lexicon beam against the plain beam of the same width
+    torch.manual_seed(0)
+    model = ft.build_model(ft.FinetuneConfig(), dev, dropout=0.0).eval()
+    conv = model.label_convertor
+    words = synthetic_lexicon(10000, seed=10000)
+    conv.set_lexicon(["".join(conv.idx2char[c] if c < 90 else "\u00e9" for c in w) for w in words], beam=8)
+    img = torch.randn(B, 3, 32, 128, generator=torch.Generator().manual_seed(4)).to(dev)
+    sides = {("beam_width", 8): [], ("lexicon_beam", 8): [], ("beam_width", 16): [], ("lexicon_beam", 16): []}
+    iters = max(3, a.iters // 6)
+    with torch.no_grad():
+        for _ in range(a.rounds):
+            for kind, width in sides:
+                fn = (lambda: model.forward_beam(img, width)) if kind == "beam_width" else (lambda: model.forward_lexicon(img, width))
+                sides[(kind, width)].append(event_ms(fn, iters))
+    ev = {"batch": B, "arch": "vit_small", "lexicon": dict(conv.lexicon_stats), "decode_graph": os.environ.get("CCD_DECODE_GRAPH", "1") != "0"}
+    for (kind, width), rounds in sides.items():
+        name = f"{kind}_{width}"
+        ev[name] = summary(rounds)
+        ev[name + "_images_per_s"] = round(B / (ev[name]["median_ms"] * 1e-3))
+    out["eval"] = ev
+    return out
+
+
+CASES = {"kernels": case_kernels, "eval": case_eval, "rescore": case_rescore, "trie": case_trie}
 
 
 def main():
