@@ -45,8 +45,9 @@ class AttnConvertor:
     is greedy decoding everywhere, and `tensor2idx` is the greedy rule whatever the width.  `lexicon` (a list of words or the path of
     a word list) TOGETHER WITH `lexicon_beam` in 1..16 asks for the closed vocabulary instead: a beam of that width over the decoder
     that walks the lexicon's prefix tree (DINO_Finetune.forward_lexicon); a finished hypothesis is a word of the lexicon and its score
-    the exact log p(word <EOS> | image).  Either of the two alone is refused: exhaustive scoring of a lexicon exists for the CTC head
-    only."""
+    the exact log p(word <EOS> | image).  Either of the two alone is refused: exhaustive scoring of ONE lexicon for the whole batch
+    exists for the CTC head only.  Words GIVEN per image - a 50-word lexicon for every image, an n-best to rescore, a transcription -
+    need no configuration: words2rows / scores2words / scores2chars below, with DINO_Finetune.forward_score / forward_words."""
 
     dicts = {name: tuple(chars) for name, chars in ALPHABETS.items()}      # same table name as the reference exposes
 
@@ -229,6 +230,87 @@ class AttnConvertor:
                                   "decoder has no frame axis to align a word against (use decoder.type: 'CTCDecoder')")
 
     tensor2chars = tensor2align
+
+    # ------------------------------------------------------------------ scoring given words (DINO_Finetune.forward_score / forward_words)
+    def words2rows(self, words):
+        """A list of N word lists - the words asked of image i; a word is a string or a list of class indices (what idx2str takes) ->
+        (seq int64 [R, max_seq_len + 1], row_ptr int32 [N + 1], rows): one row `<BOS> chars <EOS> <PAD>..` per word in the layout of
+        the decoder's sequences, the CSR table of which image owns which rows (image i: rows row_ptr[i] .. row_ptr[i + 1] - 1; a list
+        may be empty), and the R words as strings.  Host tensors.  A word of more than max_seq_len - 1 characters cannot write its
+        <EOS>: it STAYS, as a row of its first max_seq_len characters without one - an infeasible row, score -inf - so that index k
+        of a result is word k of the list, whatever the words are."""
+        if not isinstance(words, (list, tuple)) or not all(isinstance(w, (list, tuple)) for w in words):
+            raise TypeError("words2rows expects a list of word lists, one per image")
+        flat = [w for per_image in words for w in per_image]
+        if not all(isinstance(w, str) or (isinstance(w, (list, tuple)) and all(isinstance(c, (int, np.integer)) for c in w)) for w in flat):
+            raise TypeError("words2rows: a word is a string or a list of class indices")
+        T = self.max_seq_len + 1
+        seq = np.full((len(flat), T), self.padding_idx, dtype=np.int64)
+        seq[:, 0] = self.start_idx
+        rows = []
+        for row, word in zip(seq, flat):
+            cls = self._classes_of(word) if isinstance(word, str) else np.asarray(word, dtype=np.int64).reshape(-1)
+            rows.append(word if isinstance(word, str) else self.idx2str([cls.tolist()])[0])
+            n = min(cls.size, T - 1)
+            row[1:1 + n] = cls[:n]
+            if cls.size < T - 1:
+                row[1 + cls.size] = self.end_idx
+        row_ptr = np.zeros(len(words) + 1, dtype=np.int32)
+        np.cumsum([len(per_image) for per_image in words], out=row_ptr[1:])
+        return torch.from_numpy(seq), torch.from_numpy(row_ptr), rows
+
+    @torch.no_grad()
+    def scores2words(self, score, row_ptr, nbest=1):
+        """score fp32 [R] (forward_score's, on any device), row_ptr as words2rows returns it (host integers, or an ops.csr_rows handle)
+        -> (index int32 [N, nbest] into every image's OWN list, log_probs fp32 [N, nbest]), best first, on score's device: the scores
+        are scattered to [N, longest list] padded with -inf and ops.ctc_lexicon_best picks per row - by (score descending, index
+        ascending), -inf (an infeasible word, padding) never selected, a slot left over is (-1, -inf).  No host synchronisation."""
+        from .. import ops
+        rows = ops.csr_rows(row_ptr)
+        if score.dim() != 1 or score.shape[0] != rows.R or score.dtype != torch.float32:
+            raise ValueError(f"scores2words: expects score float32 [{rows.R}] (row_ptr ends there), got {score.dtype} {list(score.shape)}")
+        N, K = rows.B, rows.max_rows
+        table = torch.full((N, max(K, 1)), float("-inf"), dtype=torch.float32, device=score.device)
+        if rows.R:
+            counts = np.diff(rows.ptr)
+            owner = np.repeat(np.arange(N, dtype=np.int64), counts)
+            slot = owner * max(K, 1) + (np.arange(rows.R, dtype=np.int64) - rows.ptr[:-1].astype(np.int64)[owner])
+            table.view(-1).index_copy_(0, torch.from_numpy(slot).to(score.device, non_blocking=True), score)
+        return ops.ctc_lexicon_best(table, nbest)
+
+    @torch.no_grad()
+    def scores2chars(self, result, seq, img_hw=(32, 128), grid_hw=(8, 32)):
+        """The host view of DINO_Finetune.forward_score: `result` its dict, `seq` the rows of words2rows -> one record per word,
+        {'word', 'log_prob', 'eos_conf', 'chars': [{'char', 'conf', 'cx', 'cy', 'box': [x0, y0, x1, y1]}]}: conf = exp(char_logp), the
+        probability of the character given the ones before it; (cx, cy) the centre of the decoder's attention when it emits the
+        character, in pixels of the img_hw image - (mean + 0.5) cells of the grid_hw token grid; box that centre +- max(sqrt(3) std,
+        0.5) cells per axis (a uniform extent of width w has std w / sqrt(12)), clipped to the image.  This is where the decoder LOOKS
+        when it writes the character - the last layer's encoder-decoder attention, averaged over the heads - not the extent of the
+        ink: a sharp map gives the half-cell floor, a map spread over the word a box as wide as the word.  An infeasible row gives
+        {'word': None, 'log_prob': -inf, 'eos_conf': 0.0, 'chars': []}."""
+        length = result["length"].cpu().numpy()
+        logp, score = result["char_logp"].double().cpu().numpy(), result["score"].double().cpu().numpy()
+        pos = result["char_pos"].double().cpu().numpy()
+        seq = np.asarray(seq.cpu() if isinstance(seq, torch.Tensor) else seq)
+        if seq.shape[0] != length.shape[0] or seq.shape[1] != logp.shape[1] + 1:
+            raise ValueError(f"scores2chars: seq {list(seq.shape)} does not belong to a result of {length.shape[0]} rows of {logp.shape[1]} positions")
+        cell_h, cell_w = img_hw[0] / grid_hw[0], img_hw[1] / grid_hw[1]
+        records = []
+        for r, n in enumerate(length.tolist()):
+            if n < 0:
+                records.append({"word": None, "log_prob": float("-inf"), "eos_conf": 0.0, "chars": []})
+                continue
+            chars = []
+            for t in range(n):
+                mean_x, mean_y, std_x, std_y = pos[r, t]
+                cx, cy = (mean_x + 0.5) * cell_w, (mean_y + 0.5) * cell_h
+                hx, hy = max(np.sqrt(3.0) * std_x, 0.5) * cell_w, max(np.sqrt(3.0) * std_y, 0.5) * cell_h
+                chars.append({"char": self.idx2char[int(seq[r, t + 1])], "conf": float(np.exp(logp[r, t])), "cx": float(cx), "cy": float(cy),
+                              "box": [float(max(cx - hx, 0.0)), float(max(cy - hy, 0.0)), float(min(cx + hx, img_hw[1])),
+                                      float(min(cy + hy, img_hw[0]))]})
+            records.append({"word": "".join(c["char"] for c in chars), "log_prob": float(score[r]), "eos_conf": float(np.exp(logp[r, n])),
+                            "chars": chars})
+        return records
 
     @torch.no_grad()
     def tensor2idx(self, outputs, img_metas=None):

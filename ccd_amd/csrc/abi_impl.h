@@ -39,6 +39,7 @@
 #include "kernels/cls_tail.h"
 #include "kernels/decoder.h"
 #include "kernels/decoder_xattn.h"
+#include "kernels/nrtr_score.h"
 
 #define CCD_CHECK(cond, code) \
     do {                      \
@@ -342,7 +343,7 @@ static int ccd_seg_prepare(int images, long pixels, int* cm, int* status, int* c
 
 extern "C" {
 
-int ccd_abi_version(void) { return 27; }   // 27: ccd_nrtr_beam_step_trie (lexicon-constrained beam search over the NRTR decoder); 26: ccd_ctc_beam_search_trie (trie beam search over a lexicon in the CTC beam search); 25: ccd_ctc_align (CTC forced alignment); 24: ccd_ctc_beam_search_lm (character n-gram language-model fusion in the CTC beam search); 23: ccd_ctc_lexicon_score, ccd_ctc_lexicon_best (lexicon-constrained decoding of the CTC head); 22: ccd_nrtr_beam_step, ccd_nrtr_beam_reorder (beam search over the NRTR decoder); 21: ccd_ctc_beam_search, ccd_text_score_paths (CTC prefix beam search, n-best word scores); 20: ccd_ctc_pool_fwd / _bwd, ccd_ctc_loss_fwd / _bwd, ccd_ctc_greedy, ccd_text_score_ctc (the CTC recognition head); 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
+int ccd_abi_version(void) { return 28; }   // 28: ccd_xattn_rows_fwd, ccd_xattn_rows_chunk, ccd_nrtr_word_score (scoring given words with the NRTR decoder: per-image lexicons, character positions); 27: ccd_nrtr_beam_step_trie (lexicon-constrained beam search over the NRTR decoder); 26: ccd_ctc_beam_search_trie (trie beam search over a lexicon in the CTC beam search); 25: ccd_ctc_align (CTC forced alignment); 24: ccd_ctc_beam_search_lm (character n-gram language-model fusion in the CTC beam search); 23: ccd_ctc_lexicon_score, ccd_ctc_lexicon_best (lexicon-constrained decoding of the CTC head); 22: ccd_nrtr_beam_step, ccd_nrtr_beam_reorder (beam search over the NRTR decoder); 21: ccd_ctc_beam_search, ccd_text_score_paths (CTC prefix beam search, n-best word scores); 20: ccd_ctc_pool_fwd / _bwd, ccd_ctc_loss_fwd / _bwd, ccd_ctc_greedy, ccd_text_score_ctc (the CTC recognition head); 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
 const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi16"; }
 int ccd_policy_set(const char* key, int value) {
     CCD_CHECK(key, CCD_EINVAL);
@@ -2263,6 +2264,44 @@ int ccd_greedy_step(const float* logits, long ldl, int C, int B, float* probs, i
     if (B == 0) return CCD_OK;
     CCD_LAUNCH(ccd::greedy_step_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, logits, ldl, C, B, probs, steps, step,
                (long long*)seq, seq_len);
+    return ccd_rt_last_error();
+}
+
+// ------------------------------------------------------------------------------- scoring given words with the NRTR decoder (nrtr_score.h)
+int ccd_xattn_rows_chunk(long rows, int heads) {
+    CCD_CHECK(rows >= 0 && heads >= 1, CCD_EINVAL);
+    return ccd::xattn_rows_chunk(rows, heads, ccd_rt_num_cus());
+}
+int ccd_xattn_rows_fwd(const ccd_bf16* q, long ldq, const ccd_bf16* k, long ldk, const ccd_bf16* v, long ldv, const int* row_ptr,
+                       ccd_bf16* out, long ldo, float* moments, int rows, int batch, int heads, int Tq, int max_rows, float scale,
+                       void* stream) {
+    CCD_CHECK(rows >= 0 && batch >= 0 && heads >= 1 && max_rows >= 0 && max_rows <= rows, CCD_EINVAL);
+    CCD_CHECK(Tq >= 1 && Tq <= ccd::XA_TQ && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 && ldq >= 64L * heads &&
+              ldk >= 64L * heads && ldv >= 64L * heads && ldo >= 64L * heads && (long)batch * heads <= 0x7fffffffL, CCD_ESHAPE);
+    CCD_CHECK(((long)rows * Tq + 1) * ldq * 2 < (1L << 46) && ((long)rows * Tq + 1) * ldo * 2 < (1L << 46), CCD_ESHAPE);
+    if (rows == 0 || batch == 0 || max_rows == 0) return CCD_OK;           // nothing to do (pointers may be null)
+    CCD_CHECK(q && k && v && out && row_ptr, CCD_EINVAL);
+    CCD_CHECK(CCD_ALIGNED16(q) && CCD_ALIGNED16(k) && CCD_ALIGNED16(v) && CCD_ALIGNED16(out) && CCD_ALIGNED16(moments), CCD_EINVAL);
+    ccd::XattnRowsParams a;
+    a.q = q; a.k = k; a.v = v; a.row_ptr = row_ptr; a.out = out; a.moments = moments;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.R = rows; a.H = heads; a.Tq = Tq; a.scale = scale;
+    a.CH = ccd::xattn_rows_chunk(rows, heads, ccd_rt_num_cus());
+    long slots = ((long)max_rows + a.CH - 1) / a.CH;                       // chunk slots of the longest list; a workgroup walks further
+    if (slots > 65535) slots = 65535;                                      // chunks should the table hold a longer one
+    CCD_LAUNCH(ccd::xattn_rows_fwd_kernel, dim3((unsigned)(batch * heads), (unsigned)slots), dim3(256), (size_t)ccd::XR_SMEM, stream, a);
+    return ccd_rt_last_error();
+}
+int ccd_nrtr_word_score(const float* logits, long ldl, int classes, const int64_t* seq, int rows, int seq_len, int end_idx, int pad_idx,
+                        const float* moments, int heads, float* char_logp, float* score, int* length, float* char_pos, void* stream) {
+    CCD_CHECK(rows >= 0 && ldl >= 0 && ((moments && char_pos) || (!moments && !char_pos)), CCD_EINVAL);
+    CCD_CHECK(classes >= 1 && classes <= ccd::NRTR_MAX_C && ldl >= classes && seq_len >= 2 && seq_len <= ccd::NRTR_MAX_LEN &&
+              end_idx >= 0 && end_idx < classes && (!moments || heads >= 1), CCD_ESHAPE);
+    if (rows == 0) return CCD_OK;
+    CCD_CHECK(logits && seq && char_logp && score && length, CCD_EINVAL);
+    CCD_LAUNCH(ccd::nrtr_word_score_kernel, dim3((unsigned)((rows + ccd::NWS_WAVES - 1) / ccd::NWS_WAVES)), dim3(64 * ccd::NWS_WAVES), 0,
+               stream, logits, ldl, classes, reinterpret_cast<const long long*>(seq), rows, seq_len, end_idx, pad_idx, moments, heads,
+               char_logp, score, length, char_pos);
     return ccd_rt_last_error();
 }
 

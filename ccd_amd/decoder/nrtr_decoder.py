@@ -199,6 +199,14 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
             out = self._replay(self._trie_graphs, key + (trie,), lambda x: fe.beam_decode(self, x, width, trie), out_enc)
         return tuple(t.clone() for t in out)
 
+    def forward_score(self, feat, out_enc, seq, row_ptr):
+        """Teacher-forced scores of given words (fe.score_words): seq int64 [R, max_seq_len + 1] rows `<BOS> chars <EOS> <PAD>..`
+        (AttnConvertor.words2rows), row_ptr the CSR table of which image owns which rows (ops.csr_rows handle or host integers) ->
+        {'score' [R], 'length' [R], 'char_logp' [R, max_seq_len], 'char_pos' [R, max_seq_len, 4], 'row_ptr' [N + 1]} on the device.
+        Eager launches, no HIP graph: the shapes change with the word lists."""
+        self._ready()
+        return fe.score_words(self, out_enc.to(torch.bfloat16), seq.to(out_enc.device, non_blocking=True), row_ptr)
+
     def forward_test_speed(self, feat, out_enc, img_metas=None):
         self._ready()
         return fe.greedy_decode(self, out_enc.to(torch.bfloat16), stop_on_eos_of_first=True)

@@ -444,3 +444,56 @@ def beam_decode(module, out_enc, beam_width, trie=None):
         if s + 1 < steps and W > 1:
             ops.nrtr_beam_reorder(cache, parent, T, s)
     return out
+
+
+@torch.no_grad()
+def score_words(module, out_enc, seq, row_ptr):
+    """Teacher-forced scores of GIVEN words: out_enc bf16 [B, 256, D], seq int64 [R, max_seq_len + 1] = <BOS> c1 .. cn <EOS> <PAD> ..
+    (AttnConvertor.words2rows; the layout of beam_decode's sequences), row_ptr an ops.csr_rows handle (or B + 1 host integers): the
+    rows row_ptr[b] .. row_ptr[b + 1] - 1 are words asked of image b -> a dict of device tensors: score fp32 [R] = log p(word <EOS> |
+    image), the number beam_decode gives the same path; length int32 [R]; char_logp fp32 [R, max_seq_len]; char_pos fp32 [R,
+    max_seq_len, 4] = mean_x, mean_y, std_x, std_y of the last layer's head-averaged encoder-decoder attention of every character, in
+    token units of the 8 x 32 grid; row_ptr int32 [B + 1] on the device.  A word too long to write its <EOS>, or with a class the
+    classifier does not have, is an infeasible row: -inf, -1, zeros (ops.nrtr_word_score).
+    The encoder keys and values are computed once for the B images and never replicated: the decoder layers of `decoder_states` run
+    over the R rows - the self-attention with rows as samples, the encoder-decoder attention through ops.xattn_rows_fwd, which maps
+    every row onto its image's keys and values.  Dropout 0, nothing saved, no host synchronisation."""
+    arena, pre, spec, packed = module.arena, module.arena_prefix, module.dec_spec, module.packed
+    D, H, L, C = spec.D, spec.H, spec.L, spec.C
+    T = spec.max_seq_len + 1
+    rows = ops.csr_rows(row_ptr)
+    if out_enc.dim() != 3 or out_enc.shape[0] != rows.B or tuple(out_enc.shape[1:]) != (256, D):
+        raise ValueError(f"score_words: row_ptr names {rows.B} images, out_enc is {list(out_enc.shape)} (expects [{rows.B}, 256, {D}])")
+    if seq.dtype != torch.int64 or tuple(seq.shape) != (rows.R, T) or not seq.is_contiguous():
+        raise ValueError(f"score_words: seq must be contiguous int64 [{rows.R}, {T}], got {seq.dtype} {list(seq.shape)}")
+    R = rows.R
+    if R == 0:                                                                                   # no words: empty outputs, no launch
+        dev = out_enc.device
+        return {"score": torch.empty(0, dtype=F32, device=dev), "length": torch.empty(0, dtype=torch.int32, device=dev),
+                "char_logp": torch.empty((0, T - 1), dtype=F32, device=dev), "char_pos": torch.empty((0, T - 1, 4), dtype=F32, device=dev),
+                "row_ptr": rows.on(dev)}
+    scale = 64 ** -0.5
+    packed.refresh(arena, pre, spec)
+    kv = encoder_kv(arena, pre, spec, out_enc.reshape(-1, D))
+    x = ops.dec_embed_fwd(seq, arena.w(pre + "trg_word_emb.weight"), module.pos_table)
+    moments = None
+    for l in range(L):
+        b = f"{pre}layer_stack.{l}."
+        y, _, _ = ops.ln_fwd(x, arena.w(b + "norm1.weight"), arena.w(b + "norm1.bias"), 1e-5)
+        qkv = ops.gemm_nt(y, arena.span(b + "self_attn.linear_q.weight", 3 * D, "wb"))
+        att, _, _ = ops.dec_attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], R, H, T, T, scale, tokens=seq,
+                                     pad_idx=spec.padding_idx, causal=True)
+        x = _resid(x, att, arena.wb(b + "self_attn.fc.weight"), None, 0.0, 0)
+        y, _, _ = ops.ln_fwd(x, arena.w(b + "norm2.weight"), arena.w(b + "norm2.bias"), 1e-5)
+        q2 = ops.gemm_nt(y, arena.wb(b + "enc_attn.linear_q.weight"))
+        att, mom = ops.xattn_rows_fwd(q2, kv[:, l * 2 * D:l * 2 * D + D], kv[:, l * 2 * D + D:(l + 1) * 2 * D], rows, H, T, scale,
+                                      want_moments=l == L - 1)
+        moments = mom if mom is not None else moments
+        x = _resid(x, att, arena.wb(b + "enc_attn.fc.weight"), None, 0.0, 0)
+        y, _, _ = ops.ln_fwd(x, arena.w(b + "norm3.weight"), arena.w(b + "norm3.bias"), 1e-5)
+        _, g3 = ops.gemm_nt(y, arena.wb(b + "mlp.w_1.weight"), epilogue=ops.EPI_GELU, bias=arena.w(b + "mlp.w_1.bias"), store_u=False)
+        x = _resid(x, g3, arena.wb(b + "mlp.w_2.weight"), arena.w(b + "mlp.w_2.bias"), 0.0, 0)
+    y, _, _ = ops.ln_fwd(x, arena.w(pre + "layer_norm.weight"), arena.w(pre + "layer_norm.bias"), 1e-6)
+    logits = ops.gemm_nt(y, packed.cls, epilogue=ops.EPI_F32, bias=packed.cls_bias)
+    char_logp, score, length, char_pos = ops.nrtr_word_score(logits, C, seq, spec.start_idx, spec.padding_idx, moments=moments, H=H)
+    return {"score": score, "length": length, "char_logp": char_logp, "char_pos": char_pos, "row_ptr": rows.on(seq.device)}

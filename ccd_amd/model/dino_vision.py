@@ -300,6 +300,39 @@ class DINO_Finetune(ArenaModule):
                                       "(use decoder.type: 'CTCDecoder')")
         return self.label_convertor.tensor2align(self.forward_test(img), words=words, nbest=nbest, normalized=True)
 
+    _SCORE_IS_NRTR = ("forward_score / forward_words are the NRTR head's (a teacher-forced decoder pass over the given words); the CTC "
+                      "head scores given words with CTCConvertor.tensor2lexicon(subset=) and aligns them with forward_chars")
+
+    def _score_rows(self, img, words):
+        from ..ops import csr_rows
+        if self.ctc:
+            raise NotImplementedError(self._SCORE_IS_NRTR)
+        if len(words) != img.shape[0]:
+            raise ValueError(f"expects one word list per image, got {len(words)} lists for {img.shape[0]} images")
+        seq, row_ptr, _ = self.label_convertor.words2rows(words)
+        rows = csr_rows(row_ptr)
+        feat = self.extract_feat(img)
+        return self.decoder.forward_score(feat, self.encoder(feat), seq, rows), rows
+
+    @torch.no_grad()
+    def forward_score(self, img, words):
+        """img [N,3,32,128], words: a list of N word lists (strings, or lists of class indices: AttnConvertor.words2rows) - the words
+        asked of every image, R in all -> a dict of device tensors, one row per word in list order: 'score' fp32 [R] = log p(word <EOS> |
+        image), exact and comparable across words - the number forward_beam / forward_lexicon return for the same word; 'length' int32
+        [R]; 'char_logp' fp32 [R, max_seq_len] (entry `length`: the <EOS>); 'char_pos' fp32 [R, max_seq_len, 4] = mean_x, mean_y, std_x,
+        std_y of the decoder's attention over the 8 x 32 token grid for every character; 'row_ptr' int32 [N + 1].  A word too long for the
+        decoder is an infeasible row (-inf, -1, zeros).  One teacher-forced decoder pass over all R rows, the encoder memory of an
+        image shared by its words (NRTRDecoder.forward_score).  AttnConvertor.scores2chars is the host-side view."""
+        return self._score_rows(img, words)[0]
+
+    @torch.no_grad()
+    def forward_words(self, img, words, nbest=1):
+        """The closed-vocabulary protocol with a lexicon PER IMAGE: img [N,3,32,128], words a list of N word lists -> (index int32
+        [N, nbest] into every image's own list, log_probs fp32 [N, nbest]), best first; (-1, -inf) where a list holds fewer feasible
+        words.  forward_score, then AttnConvertor.scores2words on the device: nothing is read back."""
+        result, rows = self._score_rows(img, words)
+        return self.label_convertor.scores2words(result["score"], rows, nbest)
+
     def forward_test_speed(self, img):
         feat = self.extract_feat(img)
         if self.ctc:                                       # (one pass either way: nothing to stop early)

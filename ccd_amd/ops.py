@@ -1369,6 +1369,131 @@ def nrtr_beam_reorder(cache, parent, positions, step):
     _call("ccd_nrtr_beam_reorder", cache, parent, cache.shape[0], B, W, int(positions), cache.shape[2] // 3, int(step))
 
 
+# ------------------------------------------------------------------------------------------ scoring given words (kernels/nrtr_score.h)
+XATTN_ROWS_MAX_TQ = 32                                    # queries of a word row (decoder_xattn.h: XA_TQ)
+NRTR_MAX_CLASSES, NRTR_MAX_POSITIONS = 128, 128           # nrtr_beam.h: NRTR_MAX_C, NRTR_MAX_LEN
+
+
+class CsrRows:
+    """Which sample owns which word row, in CSR form: the rows of sample b are ptr[b] .. ptr[b + 1] - 1.  Built and checked on the host
+    (csr_rows below) - the counts are host knowledge, the word lists - and uploaded once per device."""
+
+    def __init__(self, ptr):
+        self.ptr = ptr                                    # numpy int32 [B + 1]
+        self.B, self.R = len(ptr) - 1, int(ptr[-1])
+        self.max_rows = int(np.diff(ptr).max()) if len(ptr) > 1 else 0
+        self._on = {}
+
+    def on(self, device):
+        key = str(device)
+        if key not in self._on:
+            self._on[key] = torch.from_numpy(self.ptr).to(device, non_blocking=True)
+        return self._on[key]
+
+
+def csr_rows(ptr):
+    """ptr: B + 1 host integers (a list, a numpy array, a CPU tensor), non-decreasing from 0 -> a CsrRows handle.  A sample may own no
+    rows.  A device tensor is refused: checking it would wait for the device."""
+    if isinstance(ptr, CsrRows):
+        return ptr
+    if isinstance(ptr, torch.Tensor):
+        if ptr.device.type != "cpu":
+            raise TypeError("csr_rows: expects host integers (the table is checked on the host), got a tensor on " + str(ptr.device))
+        if ptr.dtype not in (I32, I64):
+            raise TypeError(f"csr_rows: expects an integer table, got {ptr.dtype}")
+        ptr = ptr.numpy()
+    a = np.asarray(ptr)
+    if a.ndim != 1 or a.size < 1 or a.dtype.kind not in "iu":
+        raise TypeError(f"csr_rows: expects B + 1 integers, got {a.dtype} {list(a.shape)}")
+    a = a.astype(np.int64)
+    if a[0] != 0 or (np.diff(a) < 0).any() or a[-1] > 0x7fffffff:
+        raise ValueError("csr_rows: row_ptr must start at 0 and never decrease (CSR: sample b owns the rows ptr[b] .. ptr[b + 1] - 1), got "
+                         f"{a[:8].tolist()}{' ..' if a.size > 8 else ''}")
+    return CsrRows(np.ascontiguousarray(a.astype(np.int32)))
+
+
+def xattn_rows_chunk(R, H):
+    """The rows of one sample that a workgroup of xattn_rows_fwd takes (ccd_hip.h: ccd_xattn_rows_chunk): max(1, ceil(R * H / (4 *
+    compute units))).  It sizes the grid; results do not depend on it."""
+    ch = _lib.get().ccd_xattn_rows_chunk(int(R), int(H))
+    if ch < 1:
+        _lib.check(ch, "ccd_xattn_rows_chunk")
+    return ch
+
+
+def xattn_rows_fwd(q, k, v, row_ptr, H, Tq, scale, want_moments=False):
+    """The encoder-decoder attention of R word rows against the keys / values of the sample that owns each row (kernels/nrtr_score.h):
+    q bf16 [R * Tq, >= 64 H], k, v bf16 [B * 256, >= 64 H] 2-D views (head h at column 64 h; any row stride that is a multiple of 8),
+    row_ptr a CsrRows handle or B + 1 host integers (ops.csr_rows) -> (out bf16 [R * Tq, 64 H], moments fp32 [R, H, Tq, 4] or None).  `out` is
+    bit-equal to dec_attn_fwd on k / v gathered per row; moments = sum p x, sum p y, sum p x^2, sum p y^2 of every attention map over
+    the 8 x 32 token grid (x = key & 31, y = key >> 5).  Inference only."""
+    rp = csr_rows(row_ptr)
+    H, Tq = int(H), int(Tq)
+    if not 1 <= Tq <= XATTN_ROWS_MAX_TQ:
+        raise ValueError(f"xattn_rows_fwd: Tq must lie in 1..{XATTN_ROWS_MAX_TQ}, got {Tq}")
+    if H < 1:
+        raise ValueError(f"xattn_rows_fwd: H must be positive, got {H}")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dtype != BF16:
+            raise TypeError(f"xattn_rows_fwd: {name} must be bfloat16, got {t.dtype}")
+        if t.dim() != 2 or t.shape[1] < 64 * H or (t.shape[0] > 0 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) % 8):
+            raise ValueError(f"xattn_rows_fwd: {name} must be a 2-D view of >= {64 * H} dense columns whose row stride is a multiple of 8, "
+                             f"got {list(t.shape)}, strides {t.stride()}")
+    if q.shape[0] != rp.R * Tq:
+        raise ValueError(f"xattn_rows_fwd: row_ptr ends at {rp.R} rows of {Tq} queries, q has {q.shape[0]} rows")
+    if k.shape[0] != rp.B * 256 or v.shape[0] != rp.B * 256:
+        raise ValueError(f"xattn_rows_fwd: row_ptr names {rp.B} samples of 256 keys, k / v have {k.shape[0]} / {v.shape[0]} rows")
+    out = torch.empty((rp.R * Tq, 64 * H), dtype=BF16, device=q.device)
+    moments = torch.empty((rp.R, H, Tq, 4), dtype=F32, device=q.device) if want_moments else None
+    if rp.R and rp.B:
+        ld = [t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in (q, k, v)]
+        _call("ccd_xattn_rows_fwd", q, ld[0], k, ld[1], v, ld[2], rp.on(q.device), out, 64 * H, moments, rp.R, rp.B, H, Tq, rp.max_rows,
+              float(scale))
+    return out, moments
+
+
+def nrtr_word_score(logits, C, seq, end_idx, pad_idx, moments=None, H=None):
+    """log-probabilities and positions of every character of R given words (kernels/nrtr_score.h; tests/nrtr_score_np.py is the
+    specification): logits fp32 [R * T, ld >= C] of the teacher-forced decoder, seq int64 [R, T] = <BOS> c1 .. cn <EOS> <PAD> .. ->
+    (char_logp fp32 [R, T - 1], score fp32 [R], length int32 [R], char_pos fp32 [R, T - 1, 4] or None).  char_logp[r, t] is the fp64
+    log-softmax over the classes [0, C) at position t taken at seq[r, t + 1], for t = 0 .. n (entry n: the <EOS>), 0 behind it; score
+    their fp64 sum = log p(word <EOS> | image); length = n.  A row without an <EOS> behind position 0, or with a character outside [0, C)
+    or equal to pad_idx, is infeasible: score -inf, length -1, zeros.  moments fp32 [R, H, T, 4] (xattn_rows_fwd, the last layer's) gives
+    char_pos = mean_x, mean_y, std_x, std_y of the head-averaged attention of every character, in token units."""
+    if seq.dtype != I64:
+        raise TypeError(f"nrtr_word_score: seq must be int64, got {seq.dtype}")
+    if seq.dim() != 2 or not seq.is_contiguous():
+        raise ValueError(f"nrtr_word_score: seq must be contiguous [R, T], got {list(seq.shape)}, strides {seq.stride()}")
+    if logits.dtype != F32:
+        raise TypeError(f"nrtr_word_score: logits must be float32, got {logits.dtype}")
+    R, T = seq.shape
+    C = int(C)
+    if not 2 <= T <= NRTR_MAX_POSITIONS or not 1 <= C <= NRTR_MAX_CLASSES:
+        raise ValueError(f"nrtr_word_score: expects 2..{NRTR_MAX_POSITIONS} positions and 1..{NRTR_MAX_CLASSES} classes, got T = {T}, C = {C}")
+    if logits.dim() != 2 or logits.shape[0] != R * T or logits.shape[1] < C or (R and logits.stride(1) != 1):
+        raise ValueError(f"nrtr_word_score: expects logits [{R * T}, >= {C}] with dense rows, got {list(logits.shape)}")
+    if not 0 <= int(end_idx) < C:
+        raise ValueError(f"nrtr_word_score: end_idx must lie in [0, {C}), got {end_idx}")
+    dev = logits.device
+    char_pos = None
+    if moments is not None:
+        if H is None or int(H) < 1:
+            raise ValueError(f"nrtr_word_score: moments need the number of heads H >= 1, got {H!r}")
+        if moments.dtype != F32:
+            raise TypeError(f"nrtr_word_score: moments must be float32, got {moments.dtype}")
+        if tuple(moments.shape) != (R, int(H), T, 4) or not moments.is_contiguous():
+            raise ValueError(f"nrtr_word_score: moments must be contiguous [{R}, {int(H)}, {T}, 4], got {list(moments.shape)}")
+        char_pos = torch.empty((R, T - 1, 4), dtype=F32, device=dev)
+    char_logp = torch.empty((R, T - 1), dtype=F32, device=dev)
+    score = torch.empty(R, dtype=F32, device=dev)
+    length = torch.empty(R, dtype=I32, device=dev)
+    if R:
+        ld = logits.stride(0) if logits.shape[0] > 1 else logits.shape[1]
+        _call("ccd_nrtr_word_score", logits, ld, C, seq, R, T, int(end_idx), int(pad_idx), moments, int(H) if moments is not None else 0,
+              char_logp, score, length, char_pos)
+    return char_logp, score, length, char_pos
+
+
 class SsimFn(torch.autograd.Function):
     """apply(window, taps, size_average, img1, img2[, img3]) -> mean (0-dim) or per-image means [N]; backward on the kernels."""
 

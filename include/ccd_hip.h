@@ -667,6 +667,48 @@ int ccd_nrtr_beam_reorder(ccd_bf16* cache, const int* parent, int layers, int ba
 int ccd_nrtr_beam_step_trie(const float* logits, long ldl, int batch, int beam, int classes, int step, int end_idx, int pad_idx,
                             int64_t* seq, int seq_len, double* score, int* state, int* parent, int* paths, int* lengths,
                             float* hyp_scores, const int* nodes, int n_nodes, int class_offset, int* node, int* word_ids, void* stream);
+/* Scoring GIVEN words with the NRTR decoder (ABI 28; kernels/nrtr_score.h, the second kernel restated in numpy in
+ * tests/nrtr_score_np.py).  Inference only: no dropout, no mask, no backward.
+ *
+ * ccd_xattn_rows_fwd: the encoder-decoder attention of `rows` word rows against the keys and values of the sample that owns each row.
+ *   q        bf16 [rows * Tq, ldq]: row r holds Tq queries (1 <= Tq <= 32), head h at column 64 h
+ *   k, v     bf16 [batch * 256, ldk / ldv]: the 256 image tokens of every sample, head h at column 64 h (ccd_dec_attn_fwd's layout)
+ *   row_ptr  int32 [batch + 1], DEVICE memory, CSR: sample b owns the rows row_ptr[b] .. row_ptr[b + 1] - 1; non-decreasing, row_ptr[0]
+ *            = 0, row_ptr[batch] = rows; a sample may own none.  The entry point does not read it (the caller, who built it, checks
+ *            it); the kernel clamps what it reads into [0, rows], so a malformed table gives wrong results, never an access outside q / out.
+ *   max_rows the caller's upper bound on the rows of one sample (<= rows): the grid holds ceil(max_rows / chunk) chunk slots per
+ *            (sample, head); a sample with more rows is still computed in full, by workgroups that walk several chunks.
+ *   out      bf16 [rows * Tq, ldo]: BIT-EQUAL to ccd_dec_attn_fwd (Tk = 256, no mask, p = 0) on k / v gathered per row.
+ *   moments  optional fp32 [rows, heads, Tq, 4]: sum_j p_j x_j, sum_j p_j y_j, sum_j p_j x_j^2, sum_j p_j y_j^2 over the 256 keys, x = j & 31,
+ *            y = j >> 5 - the moments of the attention map over the 8 x 32 token grid, p the fp32 probabilities ccd_dec_attn_fwd would
+ *            write as `probs`.  Summed in a fixed order, no atomics: |error| <= 23 * 2^-24 * value.
+ * ccd_xattn_rows_chunk(rows, heads): the rows of one sample that a workgroup takes, max(1, ceil(rows * heads / (4 * compute units))).  It
+ *            sizes the grid and nothing else: results do not depend on it.  Negative on an error.
+ * rows == 0, batch == 0 or max_rows == 0 is a no-op.  CCD_EINVAL: a missing or misaligned (16 B) pointer, a negative size, max_rows >
+ * rows; CCD_ESHAPE: Tq outside 1..32, a leading dimension that is no multiple of 8 or below 64 * heads.
+ *
+ * ccd_nrtr_word_score, one wavefront per row: logits fp32 [rows * seq_len, ldl >= classes] of the teacher-forced decoder, seq int64
+ * [rows, seq_len] = <BOS> c1 .. cn <EOS> <PAD> .. (the layout of ccd_nrtr_beam_step's seq).  The first end_idx behind position 0 ends the
+ * word; n is the number of tokens in front of it.
+ *   char_logp fp32 [rows, seq_len - 1]: entry t = log_softmax(logits[r * seq_len + t, :classes])[seq[r, t + 1]] for t = 0 .. n (entry n is
+ *             the <EOS>), in fp64 by the routine of ccd_nrtr_beam_step, rounded once; 0 behind it
+ *   score     fp32 [rows]: the fp64 sum of those entries in position order, rounded once = log p(word <EOS> | image), the number
+ *             ccd_nrtr_beam_step gives the same path
+ *   length    int32 [rows]: n
+ *   char_pos  fp32 [rows, seq_len - 1, 4], with moments fp32 [rows, heads, seq_len, 4] of ccd_xattn_rows_fwd (both or none): mean_x,
+ *             mean_y, std_x, std_y of the head-averaged attention map of position t, in token units (variance clamped at 0); 0 behind
+ *             the <EOS>
+ *   An INFEASIBLE row - no end_idx behind position 0 (a word longer than seq_len - 2), or one of c1 .. cn outside [0, classes) or equal
+ *   to pad_idx - gives score -inf, length -1 and zeros elsewhere; nothing is addressed through such a token.  A -inf logit at a target
+ *   gives -inf in char_logp and score, the length stays.
+ * rows == 0 is a no-op.  CCD_EINVAL: a missing pointer, moments without char_pos or the reverse, a negative size; CCD_ESHAPE: classes
+ * outside 1..128, ldl < classes, seq_len outside 2..128, end_idx outside [0, classes), moments with heads < 1. */
+int ccd_xattn_rows_chunk(long rows, int heads);
+int ccd_xattn_rows_fwd(const ccd_bf16* q, long ldq, const ccd_bf16* k, long ldk, const ccd_bf16* v, long ldv, const int* row_ptr,
+                       ccd_bf16* out, long ldo, float* moments, int rows, int batch, int heads, int Tq, int max_rows, float scale,
+                       void* stream);
+int ccd_nrtr_word_score(const float* logits, long ldl, int classes, const int64_t* seq, int rows, int seq_len, int end_idx, int pad_idx,
+                        const float* moments, int heads, float* char_logp, float* score, int* length, float* char_pos, void* stream);
 
 /* ---------------------------------------------------------------- DINOHead pieces, vit.py:313,326 */
 int ccd_l2norm_fwd(const ccd_bf16* x, ccd_bf16* y, float* inv, int max_rows, const int* d_rows, int rows_mul, int D,

@@ -60,6 +60,46 @@ def alignment_writer(convertor, out, name, image_width=128):
     return write
 
 
+def decoded_words(net, images):
+    """The word the NRTR head's configured decoder returns for every image, as class indices (None: the lexicon's beam ended without
+    a word): rank 0 of forward_lexicon (a lexicon and its lexicon_beam), of forward_beam at beam_width, or of the beam of width 1,
+    which is greedy decoding."""
+    conv = net.label_convertor
+    if conv.lexicon is not None:
+        _, _, paths, lengths = net.forward_lexicon(images)
+    else:
+        paths, lengths, _ = net.forward_beam(images, conv.beam_width if conv.beam_width > 0 else 1)
+    paths, lengths = paths[:, 0].cpu().numpy(), lengths[:, 0].cpu().numpy()
+    return [None if n < 0 else paths[i, :n].tolist() for i, n in enumerate(lengths.tolist())]
+
+
+def write_char_scores(model, loaders, config, out, names=None):
+    """--char_scores: a pass of its own over the test sets, behind the accuracy run and changing nothing of it - one JSON line per image:
+    ground truth, the word the configured decoder returns (`decoded_words`), its log-probability log p(word <EOS> | image), and per
+    character conf = p(character | the ones before it) with the centre and box of the decoder's attention in pixels of the crop, all
+    from ONE DINO_Finetune.forward_score pass per batch (AttnConvertor.scores2chars).  A box is where the decoder LOOKS when it writes
+    the character, not the extent of the ink.  `pred` is null where the decoder returned no word."""
+    names = names or EVAL_DATA_NAMES
+    net = model.module if hasattr(model, "module") else model
+    net.eval()
+    conv = net.label_convertor
+    device = next(net.parameters()).device
+    hw = (int(config.dataset_image_height or 32), int(config.dataset_image_width or 128))
+    with torch.no_grad():
+        for i, loader in enumerate(loaders):
+            name, count = names[i] if i < len(names) else f"dataset{i}", 0
+            for image_tensors, label_tensors in loader:
+                image_tensors = image_tensors.to(device)
+                words = [[w] if w is not None else [] for w in decoded_words(net, image_tensors)]
+                seq, row_ptr, _ = conv.words2rows(words)
+                records = conv.scores2chars(net.forward_score(image_tensors, words), seq, img_hw=hw)
+                for b, gt in enumerate(list(label_tensors[0])):
+                    rec = records[int(row_ptr[b])] if words[b] else {"word": None, "log_prob": None, "eos_conf": None, "chars": []}
+                    out.write(json.dumps({"dataset": name, "index": count, "gt": gt, "pred": rec["word"], "log_prob": rec["log_prob"],
+                                          "eos_conf": rec["eos_conf"], "chars": rec["chars"]}, ensure_ascii=False) + "\n")
+                    count += 1
+
+
 def evaluate(model, loaders, config, names=None, alignments=None):
     """alignments: a text file open for writing (--alignments); None: nothing but the accuracy run."""
     names = names or EVAL_DATA_NAMES
@@ -85,6 +125,12 @@ def evaluate(model, loaders, config, names=None, alignments=None):
     return report, results
 
 
+def check_arguments(a):
+    """What can be refused before anything is built."""
+    if a.char_scores is not None and a.alignments is not None:
+        raise ValueError("--char_scores (the NRTR head) and --alignments (the CTC head) exclude each other: a model has one head")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default="Dino/configs/CCD_vision_model_ARD.yaml", help="path to config file")
@@ -108,7 +154,12 @@ def main():
     ap.add_argument("--alignments", type=str, default=None, metavar="PATH",
                     help="next to the accuracy run write one JSON line per image to PATH - ground truth, predicted word, the log-probability of "
                          "its best alignment, and per character x0, x1, first / last frame and confidence (the CTC head only)")
+    ap.add_argument("--char_scores", type=str, default=None, metavar="PATH",
+                    help="behind the accuracy run write one JSON line per image to PATH - ground truth, the word the configured decoder returns "
+                         "(greedy, --beam_width, or --lexicon with --lexicon_beam), its log-probability, and per character the confidence and "
+                         "the box of the decoder's attention (the NRTR head only; the CTC head has --alignments)")
     a = ap.parse_args()
+    check_arguments(a)
     config = Config(a.config)
     if a.checkpoint is not None:
         config.model_checkpoint = a.checkpoint
@@ -146,6 +197,9 @@ def main():
         model.load_state_dict(sd["net"])
         model.module.ensure_arena()
     logging.info("eval model")
+    if a.char_scores is not None and model.module.ctc:
+        raise NotImplementedError("--char_scores is for the NRTR head only: the CTC head writes character spans and confidences with "
+                                  "--alignments")
     if a.alignments is not None:
         if not model.module.ctc:
             raise NotImplementedError("--alignments is for the CTC head only: the NRTR decoder has no frame axis to align a word against")
@@ -153,6 +207,9 @@ def main():
             report, _ = evaluate(model, loaders, config, alignments=f)
     else:
         report, _ = evaluate(model, loaders, config)
+    if a.char_scores is not None:
+        with open(a.char_scores, "w", encoding="utf-8") as f:
+            write_char_scores(model, loaders, config, f)
     print("-" * 80)
     print(report + "\n")
 

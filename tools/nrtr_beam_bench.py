@@ -3,6 +3,7 @@
 
     python tools/nrtr_beam_bench.py [--iters 30] [--rounds 5] [--out profiles/nrtr_beam.json]
     python tools/nrtr_beam_bench.py --cases trie --out profiles/nrtr_beam_trie.json
+    python tools/nrtr_beam_bench.py --cases score --out profiles/nrtr_score.json
 
 The cases, each in a process of its own under its own time limit; the next one starts only if the one before ended well:
   kernels  ccd_nrtr_beam_step and ccd_nrtr_beam_reorder per launch at B = 512, T = 25, C = 92 (logits rows 128 wide), D = 512,
@@ -19,6 +20,12 @@ The cases, each in a process of its own under its own time limit; the next one s
            on the same logits, both on a state eight steps into their own decode (with how many of its slots are still live: a
            finished slot costs no log-softmax); then evaluation images/s at B = 512, vit_small: forward_lexicon with lexicon_beam
            8 and 16 (the 10 000-word lexicon) against forward_beam at widths 8 and 16, rounds alternating.
+  score    (not part of a default run) scoring given words (kernels/nrtr_score.h): ccd_xattn_rows_fwd at B = 64 images with 50 words
+           each (R = 3 200 rows of 26 queries, 8 heads) against ccd_dec_attn_fwd on K / V replicated per row - the same process, the same
+           q, rounds alternating, the outputs compared bit for bit first - with the bytes each side has to move and the rate, and at
+           B = 512 x 50 (R = 25 600) alone, with and without moments; ccd_nrtr_word_score at R = 25 600, T = 26, C = 92, per launch and
+           per row; then evaluation images/s at B = 512, vit_small: forward_words with 50 words per image against forward_lexicon at
+           lexicon_beam 16 over the same 50 words, rounds alternating.
 Warm-up first, HIP events around every timed call, a figure is the median of the round medians with the lowest and highest
 round.  No threshold is set; the file records what was measured.  `--case NAME` runs one case and prints its JSON line."""
 import argparse
@@ -33,7 +40,7 @@ sys.path.insert(0, ROOT)
 
 B, T, C, D, L = 512, 25, 92, 512, 6
 WIDTHS = (1, 4, 8, 16)
-LIMITS = {"kernels": 240, "eval": 420, "rescore": 180, "trie": 600}      # seconds per case
+LIMITS = {"kernels": 240, "eval": 420, "rescore": 180, "trie": 600, "score": 420}      # seconds per case
 TRIE_WIDTHS, TRIE_LEXICONS = (4, 8, 16), (1000, 10000, 90000)
 
 
@@ -254,7 +261,107 @@ def case_trie(a):
     return out
 
 
-CASES = {"kernels": case_kernels, "eval": case_eval, "rescore": case_rescore, "trie": case_trie}
+def case_score(a):
+    import numpy as np
+    import torch
+    from ccd_amd import finetune as ft, ops
+    dev = torch.device("cuda")
+    H, Tq, words_per_image = 8, T + 1, 50
+    scale = 64 ** -0.5
+    out = {"shape": {"H": H, "Tq": Tq, "words_per_image": words_per_image, "D": D}}
+
+    def operands(n_img, seed):
+        g = torch.Generator().manual_seed(seed)
+        R = n_img * words_per_image
+        q = torch.randn(R * Tq, D, generator=g).to(torch.bfloat16).to(dev)
+        kv = torch.randn(n_img * 256, 2 * D, generator=g).to(torch.bfloat16).to(dev)
+        rows = ops.csr_rows(np.arange(n_img + 1) * words_per_image)
+        return q, kv, rows, R
+
+    # ---- B = 64: against the replicated attention
+    q, kv, rows, R = operands(64, 1)
+    rep = kv.view(64, 256, 2 * D).repeat_interleave(words_per_image, 0).reshape(-1, 2 * D)
+    new = lambda: ops.xattn_rows_fwd(q, kv[:, :D], kv[:, D:], rows, H, Tq, scale)
+    old = lambda: ops.dec_attn_fwd(q, rep[:, :D], rep[:, D:], R, H, Tq, 256, scale)
+    assert torch.equal(new()[0].view(torch.int16), old()[0].view(torch.int16)), "xattn_rows_fwd differs from the replicated attention"
+    sides = {"xattn_rows_fwd": (new, []), "dec_attn_fwd_replicated": (old, [])}
+    for _ in range(a.rounds):
+        for fn, rounds in sides.values():
+            rounds.append(event_ms(fn, a.iters))
+    qo = 2.0 * R * Tq * D * 2                                                  # q read + out written
+    nbytes = {"xattn_rows_fwd": qo + 64 * 256 * 2 * D * 2 * -(-words_per_image // ops.xattn_rows_chunk(R, H)),
+              "dec_attn_fwd_replicated": qo + R * 256 * 2 * D * 2}
+    entry = {"rows": R, "chunk": ops.xattn_rows_chunk(R, H), "replication_buffers_megabytes": round(rep.numel() * 2e-6, 1)}
+    for name, (_, rounds) in sides.items():
+        e = summary(rounds)
+        e["megabytes_moved"] = round(nbytes[name] * 1e-6, 1)
+        e["gigabytes_per_s"] = round(nbytes[name] * 1e-9 / (e["median_ms"] * 1e-3), 1)
+        entry[name] = e
+    entry["speedup"] = round(entry["dec_attn_fwd_replicated"]["median_ms"] / entry["xattn_rows_fwd"]["median_ms"], 2)
+    out["b64_x_50"] = entry
+    del rep, q, kv
+    # ---- B = 512: the new kernel alone (the replicated K / V would be 2 x 6.7 GB)
+    q, kv, rows, R = operands(512, 2)
+    entry = {"rows": R, "chunk": ops.xattn_rows_chunk(R, H)}
+    sides = {"xattn_rows_fwd": [], "xattn_rows_fwd_with_moments": []}
+    for _ in range(a.rounds):
+        for name, rounds in sides.items():
+            rounds.append(event_ms(lambda: ops.xattn_rows_fwd(q, kv[:, :D], kv[:, D:], rows, H, Tq, scale, want_moments=name.endswith("moments")),
+                                   a.iters))
+    moved = 2.0 * R * Tq * D * 2 + 512 * 256 * 2 * D * 2 * -(-words_per_image // entry["chunk"])
+    for name, rounds in sides.items():
+        e = summary(rounds)
+        e["megabytes_moved"] = round((moved + (R * H * Tq * 16 if name.endswith("moments") else 0)) * 1e-6, 1)
+        e["gigabytes_per_s"] = round(e["megabytes_moved"] * 1e-3 / (e["median_ms"] * 1e-3), 1)
+        entry[name] = e
+    out["b512_x_50"] = entry
+    del q, kv
+    # ---- the word scores
+    g = torch.Generator().manual_seed(3)
+    logits = (torch.randn(R * Tq, 128, generator=g) * 2.0).to(dev)
+    seq = torch.full((R, Tq), C, dtype=torch.int64)
+    seq[:, 0] = C - 1
+    lengths = torch.randint(2, 16, (R,), generator=g)
+    for r in range(R):
+        n = int(lengths[r])
+        seq[r, 1:1 + n] = torch.randint(0, C - 1, (n,), generator=g)
+        seq[r, 1 + n] = C - 1
+    seq = seq.to(dev)
+    moments = torch.rand(R, H, Tq, 4, generator=g).to(dev)
+    rounds = [event_ms(lambda: ops.nrtr_word_score(logits, C, seq, C - 1, C, moments=moments, H=H), a.iters) for _ in range(a.rounds)]
+    e = summary(rounds)
+    e["rows"], e["mean_word_length"] = R, round(float(lengths.float().mean()), 2)
+    e["nanoseconds_per_row"] = round(e["median_ms"] * 1e6 / R, 1)
+    out["nrtr_word_score"] = e
+    del logits, moments
+    # ---- evaluation images/s: 50 words per image, the same 50 for every image so that forward_lexicon answers the same question
+    torch.manual_seed(0)
+    model = ft.build_model(ft.FinetuneConfig(), dev, dropout=0.0).eval()
+    conv = model.label_convertor
+    lexicon = ["".join(conv.idx2char[c] if c < 90 else "\u00e9" for c in w) for w in synthetic_lexicon(words_per_image, seed=50)]
+    conv.set_lexicon(lexicon, beam=16)
+    img = torch.randn(B, 3, 32, 128, generator=torch.Generator().manual_seed(4)).to(dev)
+    lists = [lexicon] * B
+    sides = {"forward_words_50_per_image": (lambda: model.forward_words(img, lists), []),
+             "forward_lexicon_beam_16": (lambda: model.forward_lexicon(img, 16), [])}
+    iters = max(3, a.iters // 6)
+    with torch.no_grad():
+        a_idx = sides["forward_words_50_per_image"][0]()[0][:, 0]
+        b_idx = sides["forward_lexicon_beam_16"][0]()[0][:, 0]
+        agree = int((a_idx == b_idx).sum())
+        for _ in range(a.rounds):
+            for fn, rounds in sides.values():
+                rounds.append(event_ms(fn, iters))
+    ev = {"batch": B, "arch": "vit_small", "lexicon": dict(conv.lexicon_stats), "best_word_agrees": f"{agree} of {B}",
+          "decode_graph": os.environ.get("CCD_DECODE_GRAPH", "1") != "0"}
+    for name, (_, rounds) in sides.items():
+        ev[name] = summary(rounds)
+        ev[name + "_images_per_s"] = round(B / (ev[name]["median_ms"] * 1e-3))
+    out["eval"] = ev
+    return out
+
+
+CASES = {"kernels": case_kernels, "eval": case_eval, "rescore": case_rescore, "trie": case_trie, "score": case_score}
 
 
 def main():
