@@ -22,6 +22,7 @@ _ALIASES = {
     "Dino.decoder.nrtr_decoder": "ccd_amd.decoder.nrtr_decoder",
     "Dino.decoder.ctc_decoder": "ccd_amd.decoder.ctc_decoder",
     "Dino.convertor": "ccd_amd.convertor",
+    "Dino.convertor.base": "ccd_amd.convertor.base",
     "Dino.convertor.attn": "ccd_amd.convertor.attn",
     "Dino.convertor.ctc": "ccd_amd.convertor.ctc",
     "Dino.metric": "ccd_amd.metric",

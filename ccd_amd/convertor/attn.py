@@ -6,40 +6,18 @@ Dino/convertor/base.py:3-110, Dino/convertor/attn.py:81-154): the DICT90 alphabe
 a target row is `<BOS> chars <EOS> <PAD>...` cut to `max_seq_len`; decoding takes the arg-max class per position,
 drops `<PAD>` and stops at the first `<EOS>`.
 
-Implementation: the alphabet is a code-point -> class lookup table (numpy), so encoding a batch is three array
-operations instead of a Python loop per character, and decoding is one arg-max + one first-EOS scan on the device.
+The alphabet, words <-> class indices and the reading of a lexicon's word list are base.BaseConvertor's; decoding is one arg-max +
+one first-EOS scan on the device.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from . import checked_beam_width, nbest_lists
-
-_DIGITS_LOWER = "0123456789abcdefghijklmnopqrstuvwxyz"
-_UPPER_PUNCT = "ABCDEFGHIJKLMNOPQRSTUVWXYZ!\"#$%&'()*+,-./:;<=>?@[\\]_`~"
-ALPHABETS = {
-    "DICT36": _DIGITS_LOWER,
-    "DICT37": _DIGITS_LOWER + " ",
-    "DICT90": _DIGITS_LOWER + _UPPER_PUNCT,
-    "DICT91": _DIGITS_LOWER + _UPPER_PUNCT + " ",
-}
-_NO_CLASS = -1
+from .base import ALPHABETS, BaseConvertor, _read_alphabet_file, checked_beam_width, nbest_lists  # noqa: F401 (the dataset and the tools import the alphabets from here)
 
 
-def _read_alphabet_file(path):
-    chars = []
-    with open(path, encoding="utf-8") as f:
-        for number, raw in enumerate(f, start=1):
-            entry = raw.rstrip("\r\n")
-            if len(entry) > 1:
-                raise ValueError(f"{path}:{number}: a dictionary line holds at most one character, found {len(entry)}")
-            if entry:
-                chars.append(entry)
-    return chars
-
-
-class AttnConvertor:
+class AttnConvertor(BaseConvertor):
     """AttnConvertor(dict_type='DICT90', max_seq_len=40, with_unknown=True, beam_width=0) - see the module docstring.  `beam_width` > 0
     asks for beam search over the decoder (DINO_Finetune.forward_beam) where words are scored (TextAccuracy.compute); 0, the default,
     is greedy decoding everywhere, and `tensor2idx` is the greedy rule whatever the width.  `lexicon` (a list of words or the path of
@@ -48,8 +26,6 @@ class AttnConvertor:
     the exact log p(word <EOS> | image).  Either of the two alone is refused: exhaustive scoring of ONE lexicon for the whole batch
     exists for the CTC head only.  Words GIVEN per image - a 50-word lexicon for every image, an n-best to rescore, a transcription -
     need no configuration: words2rows / scores2words / scores2chars below, with DINO_Finetune.forward_score / forward_words."""
-
-    dicts = {name: tuple(chars) for name, chars in ALPHABETS.items()}      # same table name as the reference exposes
 
     def __init__(self, dict_type="DICT90", dict_file=None, dict_list=None, with_unknown=True, max_seq_len=40, lower=False,
                  start_end_same=True, beam_width=0, lexicon=None, lm=None, lexicon_beam=0, **_ignored):
@@ -62,33 +38,18 @@ class AttnConvertor:
                                       "under the NRTR decoder takes one teacher-forced decoder pass per word, not a closed-form "
                                       "recursion over the frames (use decoder.type: 'CTCDecoder').  The NRTR head takes `lexicon` "
                                       "together with `lexicon_beam: N` (1..16): a beam of width N over the lexicon's prefix tree")
-        if dict_file is not None:
-            alphabet = _read_alphabet_file(dict_file)
-        elif dict_list is not None:
-            alphabet = list(dict_list)
-        elif dict_type in ALPHABETS:
-            alphabet = list(ALPHABETS[dict_type])
-        else:
-            raise NotImplementedError(f"unknown dictionary type {dict_type!r} (have {sorted(ALPHABETS)})")
-        if len(set(alphabet)) != len(alphabet):
-            raise AssertionError("dictionary holds a character twice")
+        alphabet = self._alphabet(dict_type, dict_file, dict_list)
         self.with_unknown, self.max_seq_len = bool(with_unknown), int(max_seq_len)
         self.lower, self.start_end_same = bool(lower), bool(start_end_same)
         from ..ops import NRTR_MAX_BEAM
         self.beam_width = checked_beam_width(beam_width, NRTR_MAX_BEAM)
         # special classes behind the alphabet, in the reference's order
-        self.idx2char = alphabet
+        self.idx2char = list(alphabet)
         self.unknown_idx = self._append("<UKN>") if self.with_unknown else None
         self.start_idx = self._append("<BOS/EOS>")
         self.end_idx = self.start_idx if self.start_end_same else self._append("<BOS/EOS>")
         self.padding_idx = self._append("<PAD>")
-        self.char2idx = {c: i for i, c in enumerate(self.idx2char)}
-        # code point -> class; characters outside the table resolve to <UKN> (or to _NO_CLASS -> error)
-        points = [ord(c) for c in alphabet if len(c) == 1]
-        self._lut = np.full(max(points) + 1 if points else 1, _NO_CLASS, dtype=np.int64)
-        for cls, c in enumerate(self.idx2char[:len(alphabet)]):
-            if len(c) == 1:
-                self._lut[ord(c)] = cls
+        self._index_alphabet(alphabet, 0)
         self.lexicon, self.lexicon_words, self.lexicon_stats, self.lexicon_trie, self.lexicon_beam = None, None, None, None, 0
         if lexicon is not None:
             self.set_lexicon(lexicon, beam=lexicon_beam)
@@ -119,67 +80,16 @@ class AttnConvertor:
         if self.beam_width > 0:
             raise ValueError(f"a lexicon and beam_width = {self.beam_width} exclude each other: the lexicon's beam is lexicon_beam, set "
                              "beam_width to 0")
-        if isinstance(strings_or_path, (str, bytes)) or hasattr(strings_or_path, "__fspath__"):
-            with open(strings_or_path, encoding="utf-8") as f:
-                strings = [line.rstrip("\r\n") for line in f]
-            strings = [w for w in strings if w]
-        else:
-            strings = list(strings_or_path)
-            if not all(isinstance(w, str) for w in strings):
-                raise TypeError("set_lexicon expects a list of strings or the path of a word list")
-        longest = min(self.max_seq_len - 1, ops.CTC_MAX_LABELS)
-        kept, rows, seen, too_long, duplicates = [], [], set(), 0, 0
-        for word, cls in zip(strings, self.str2idx(strings)):
-            if len(cls) > longest:
-                too_long += 1
-            elif tuple(cls) in seen:
-                duplicates += 1
-            else:
-                seen.add(tuple(cls))
-                kept.append(word)
-                rows.append(cls)
-        words = np.zeros((len(rows), max(1, max(map(len, rows), default=1))), dtype=np.int64)
-        for row, cls in zip(words, rows):
-            row[:len(cls)] = np.asarray(cls, dtype=np.int64) + 1
+        words, kept, stats = self._lexicon_rows(strings_or_path, min(self.max_seq_len - 1, ops.CTC_MAX_LABELS), 1)
         self.lexicon = ops.ctc_lexicon(torch.from_numpy(words))
         self.lexicon_words, self.lexicon_beam = kept, width
         self.lexicon_trie = ops.ctc_lexicon_trie(self.lexicon)
-        self.lexicon_stats = {"read": len(strings), "kept": len(kept), "too_long": too_long, "duplicates": duplicates,
-                              "nodes": self.lexicon_trie.n_nodes}
+        self.lexicon_stats = dict(stats, nodes=self.lexicon_trie.n_nodes)
         return self.lexicon_stats
 
     def _append(self, token):
         self.idx2char.append(token)
         return len(self.idx2char) - 1
-
-    def num_classes(self):
-        return len(self.idx2char)
-
-    # ------------------------------------------------------------------ encode
-    def _classes_of(self, word):
-        if self.lower:
-            word = word.lower()
-        points = np.frombuffer(word.encode("utf-32-le"), dtype="<u4").astype(np.int64)
-        inside = points < self._lut.size
-        cls = np.where(inside, self._lut[np.minimum(points, self._lut.size - 1)], _NO_CLASS)
-        missing = cls == _NO_CLASS
-        if missing.any():
-            if self.unknown_idx is None:
-                bad = word[int(np.argmax(missing))]
-                raise KeyError(f"character {bad!r} is not in the dictionary (pass with_unknown=True or a custom dict_file)")
-            cls = np.where(missing, self.unknown_idx, cls)
-        return cls
-
-    def str2idx(self, strings):
-        if not isinstance(strings, list):
-            raise TypeError("str2idx expects a list of strings")
-        return [self._classes_of(w).tolist() for w in strings]
-
-    def idx2str(self, indexes):
-        if not isinstance(indexes, list):
-            raise TypeError("idx2str expects a list of index lists")
-        table = self.idx2char
-        return ["".join(table[i] for i in row) for row in indexes]
 
     def str2tensor(self, strings):
         """['hello', ...] -> int64 [N, max_seq_len]: <BOS> chars <EOS> <PAD>... (cut to max_seq_len)."""
@@ -197,22 +107,13 @@ class AttnConvertor:
 
     # ------------------------------------------------------------------ decode
     def score_table(self):
-        """The classes as code points, for scoring on the device (ops.text_score): (raw, normalised) int32 [num_classes, width]
-        tables, row c = the code points of idx2char[c] as idx2str writes it / as TextAccuracy normalises it, padded with -1.  The
-        end and padding classes never reach a decoded string: their rows are empty.  None when max_seq_len steps of the longest
+        """The classes as code points, for scoring on the device (ops.text_score): the (raw, normalised) tables of
+        BaseConvertor._code_point_tables, the rows of the end and padding classes empty.  None when max_seq_len steps of the longest
         normalised row would not fit the kernel's columns (the caller scores on the host).  Built once."""
         if not hasattr(self, "_score_table"):
-            from ..metric.eval_acc import normalise
             from ..ops import TEXT_COLS
-            silent = {self.end_idx, self.padding_idx}
-            raw = ["" if c in silent else s for c, s in enumerate(self.idx2char)]
-            tables = []
-            for rows in (raw, [normalise(s) for s in raw]):
-                table = np.full((len(rows), max(1, max(map(len, rows)))), -1, dtype=np.int32)
-                for row, s in zip(table, rows):
-                    row[:len(s)] = np.frombuffer(s.encode("utf-32-le"), dtype="<u4")
-                tables.append(table)
-            self._score_table = tuple(tables) if self.max_seq_len * tables[1].shape[1] <= TEXT_COLS else None
+            tables = self._code_point_tables({self.end_idx, self.padding_idx})
+            self._score_table = tables if self.max_seq_len * tables[1].shape[1] <= TEXT_COLS else None
         return self._score_table
 
     def path_score_table(self):

@@ -3,8 +3,9 @@
 Class layout: `<BLK>` (the CTC blank) is class 0, the alphabet occupies 1..n, `<UKN>` (when enabled) is last: DICT90 gives 92
 classes.  A target row is the word's classes followed by zeros, cut to `max_seq_len` - a valid label is never 0, so the length of a
 row is its count of leading non-zero entries (what ccd_ctc_loss_fwd reads on the device).  Decoding is the greedy CTC rule: the
-arg-max class of every frame (first maximum), repeats collapsed, blanks dropped.  The reference has no CTC head; the surface follows
-AttnConvertor's so that DINO_Finetune, TextAccuracy, train_finetune.py and test.py take either.
+arg-max class of every frame (first maximum), repeats collapsed, blanks dropped.  The reference has no CTC head; the codec shares
+base.BaseConvertor with AttnConvertor and follows its surface, so that DINO_Finetune, TextAccuracy, train_finetune.py and test.py take
+either.  Which decoder the configuration below selects is decided in one place: `_beam`, `_lexicon_pick`, `best_paths`.
 
 `beam_width` > 0 asks for CTC prefix beam search (ops.ctc_beam_search) where words are scored (TextAccuracy) and in `tensor2nbest`,
 which returns an n-best list with the log-probability of each word summed over its alignments; 0, the default, is the greedy rule
@@ -37,8 +38,7 @@ import math
 import numpy as np
 import torch
 
-from . import checked_beam_width, nbest_lists
-from .attn import ALPHABETS, _NO_CLASS, _read_alphabet_file
+from .base import BaseConvertor, checked_beam_width, nbest_lists
 
 
 def is_ctc(convertor):
@@ -46,24 +46,13 @@ def is_ctc(convertor):
     return isinstance(convertor, CTCConvertor)
 
 
-class CTCConvertor:
+class CTCConvertor(BaseConvertor):
     """CTCConvertor(dict_type='DICT90', with_unknown=True, max_seq_len=25, lower=False, beam_width=0, lexicon=None, lexicon_beam=0,
     lm=None, lm_order=2, lm_weight=1.0, lm_bonus=0.0, lm_eos=True) - see the module docstring."""
 
-    dicts = {name: tuple(chars) for name, chars in ALPHABETS.items()}
-
     def __init__(self, dict_type="DICT90", dict_file=None, dict_list=None, with_unknown=True, max_seq_len=25, lower=False, beam_width=0,
                  lexicon=None, lexicon_beam=0, lm=None, lm_order=2, lm_weight=1.0, lm_bonus=0.0, lm_eos=True, **_ignored):
-        if dict_file is not None:
-            alphabet = _read_alphabet_file(dict_file)
-        elif dict_list is not None:
-            alphabet = list(dict_list)
-        elif dict_type in ALPHABETS:
-            alphabet = list(ALPHABETS[dict_type])
-        else:
-            raise NotImplementedError(f"unknown dictionary type {dict_type!r} (have {sorted(ALPHABETS)})")
-        if len(set(alphabet)) != len(alphabet):
-            raise AssertionError("dictionary holds a character twice")
+        alphabet = self._alphabet(dict_type, dict_file, dict_list)
         self.with_unknown, self.max_seq_len, self.lower = bool(with_unknown), int(max_seq_len), bool(lower)
         from ..ops import CTC_MAX_BEAM
         self.beam_width = checked_beam_width(beam_width, CTC_MAX_BEAM)
@@ -73,12 +62,7 @@ class CTCConvertor:
         if self.with_unknown:
             self.idx2char.append("<UKN>")
             self.unknown_idx = len(self.idx2char) - 1
-        self.char2idx = {c: i for i, c in enumerate(self.idx2char)}
-        points = [ord(c) for c in alphabet if len(c) == 1]
-        self._lut = np.full(max(points) + 1 if points else 1, _NO_CLASS, dtype=np.int64)
-        for cls, c in enumerate(alphabet, start=1):
-            if len(c) == 1:
-                self._lut[ord(c)] = cls
+        self._index_alphabet(alphabet, 1)                                    # the alphabet starts behind the blank
         self.lexicon, self.lexicon_words, self.lexicon_stats, self.lexicon_trie = None, None, None, None
         self.lexicon_beam = self._checked_lexicon_beam(lexicon_beam)
         if lexicon is not None:
@@ -152,30 +136,8 @@ class CTCConvertor:
         if self.beam_width > 0:
             raise ValueError(f"a lexicon and beam_width = {self.beam_width} exclude each other: lexicon decoding scores every word of "
                              "the lexicon exactly, set beam_width to 0")
-        if isinstance(strings_or_path, (str, bytes)) or hasattr(strings_or_path, "__fspath__"):
-            with open(strings_or_path, encoding="utf-8") as f:
-                strings = [line.rstrip("\r\n") for line in f]
-            strings = [w for w in strings if w]
-        else:
-            strings = list(strings_or_path)
-            if not all(isinstance(w, str) for w in strings):
-                raise TypeError("set_lexicon expects a list of strings or the path of a word list")
-        kept, rows, seen, too_long, duplicates = [], [], set(), 0, 0
-        for word, cls in zip(strings, self.str2idx(strings)):
-            if len(cls) > ops.CTC_MAX_LABELS:
-                too_long += 1
-            elif tuple(cls) in seen:
-                duplicates += 1
-            else:
-                seen.add(tuple(cls))
-                kept.append(word)
-                rows.append(cls)
-        words = np.zeros((len(rows), max(1, max(map(len, rows), default=1))), dtype=np.int64)
-        for row, cls in zip(words, rows):
-            row[:len(cls)] = cls
+        words, self.lexicon_words, self.lexicon_stats = self._lexicon_rows(strings_or_path, ops.CTC_MAX_LABELS, 0)
         self.lexicon = ops.ctc_lexicon(torch.from_numpy(words))
-        self.lexicon_words = kept
-        self.lexicon_stats = {"read": len(strings), "kept": len(kept), "too_long": too_long, "duplicates": duplicates}
         if beam is not None:
             self.lexicon_beam = beam
         self.lexicon_trie = None
@@ -184,35 +146,7 @@ class CTCConvertor:
             self.lexicon_stats["nodes"] = self.lexicon_trie.n_nodes
         return self.lexicon_stats
 
-    def num_classes(self):
-        return len(self.idx2char)
-
     # ------------------------------------------------------------------ encode
-    def _classes_of(self, word):
-        if self.lower:
-            word = word.lower()
-        points = np.frombuffer(word.encode("utf-32-le"), dtype="<u4").astype(np.int64)
-        inside = points < self._lut.size
-        cls = np.where(inside, self._lut[np.minimum(points, self._lut.size - 1)], _NO_CLASS)
-        missing = cls == _NO_CLASS
-        if missing.any():
-            if self.unknown_idx is None:
-                bad = word[int(np.argmax(missing))]
-                raise KeyError(f"character {bad!r} is not in the dictionary (pass with_unknown=True or a custom dict_file)")
-            cls = np.where(missing, self.unknown_idx, cls)
-        return cls
-
-    def str2idx(self, strings):
-        if not isinstance(strings, list):
-            raise TypeError("str2idx expects a list of strings")
-        return [self._classes_of(w).tolist() for w in strings]
-
-    def idx2str(self, indexes):
-        if not isinstance(indexes, list):
-            raise TypeError("idx2str expects a list of index lists")
-        table = self.idx2char
-        return ["".join(table[i] for i in row) for row in indexes]
-
     def str2tensor(self, strings):
         """['hello', ...] -> int64 [N, max_seq_len]: the word's classes, zero-padded (longer words cut)."""
         if not isinstance(strings, list) or not all(isinstance(w, str) for w in strings):
@@ -225,19 +159,11 @@ class CTCConvertor:
 
     # ------------------------------------------------------------------ decode
     def score_table(self, steps=32):
-        """The classes as code points for ops.text_score_ctc, as AttnConvertor.score_table: (raw, normalised) int32 [num_classes,
-        width], rows padded with -1, the blank's row empty.  None when `steps` frames of the longest normalised row would not fit the
-        kernel's columns.  The tables are built once."""
+        """The classes as code points for ops.text_score_ctc: the (raw, normalised) tables of BaseConvertor._code_point_tables, the
+        blank's row empty.  None when `steps` frames of the longest normalised row would not fit the kernel's columns.  The tables
+        are built once."""
         if not hasattr(self, "_tables"):
-            from ..metric.eval_acc import normalise
-            raw = ["" if c == self.blank_idx else s for c, s in enumerate(self.idx2char)]
-            tables = []
-            for rows in (raw, [normalise(s) for s in raw]):
-                table = np.full((len(rows), max(1, max(map(len, rows)))), -1, dtype=np.int32)
-                for row, s in zip(table, rows):
-                    row[:len(s)] = np.frombuffer(s.encode("utf-32-le"), dtype="<u4")
-                tables.append(table)
-            self._tables = tuple(tables)
+            self._tables = self._code_point_tables({self.blank_idx})
         from ..ops import TEXT_COLS
         return self._tables if steps * self._tables[1].shape[1] <= TEXT_COLS else None
 
@@ -263,14 +189,10 @@ class CTCConvertor:
         probability summed over the alignments the beam kept, -inf where a slot is empty.  With a language model set (set_lm) the search
         is the fused one and log_probs are the fused scores: log p_ctc(word) + lm_weight * sum log P_lm + lm_bonus * len(word), with
         lm_eos the end-of-word term included - comparable with the plain beam's only after that sum is subtracted."""
-        from .. import ops
         width = self.beam_width if beam_width is None else int(beam_width)
         if width < 1:
             raise ValueError("tensor2nbest: needs a beam_width >= 1 (the convertor's is 0: greedy decoding)")
-        if self.lm is not None:
-            return nbest_lists("tensor2nbest", *ops.ctc_beam_search_lm(outputs.float(), width, self.lm, self.lm_weight, self.lm_bonus,
-                                                                       self.lm_eos, normalized=normalized), nbest)
-        return nbest_lists("tensor2nbest", *ops.ctc_beam_search(outputs.float(), width, normalized=normalized), nbest)
+        return nbest_lists("tensor2nbest", *self._beam(outputs.float(), width, normalized), nbest)
 
     @torch.no_grad()
     def tensor2lexicon(self, outputs, nbest=1, normalized=True, subset=None, beam=None):
@@ -292,17 +214,13 @@ class CTCConvertor:
                                  "scored exhaustively (pass beam=0)")
             if not 1 <= int(nbest) <= width:
                 raise ValueError(f"tensor2lexicon: nbest must lie in 1..beam = {width}, got {nbest}")
-            ids, best = ops.ctc_lexicon_search(outputs.float(), self._trie(), width, nbest=nbest, normalized=normalized)
-            ids = ids.long().cpu()
-        else:
-            scores = ops.ctc_lexicon_score(outputs.float(), self.lexicon, normalized=normalized, subset=subset)
-            if not 1 <= int(nbest) <= ops.CTC_LEXICON_MAX_NBEST:
-                raise ValueError(f"tensor2lexicon: nbest must lie in 1..{ops.CTC_LEXICON_MAX_NBEST}, got {nbest}")
-            index, best = ops.ctc_lexicon_best(scores, nbest)
-            ids = index.long()
-            if subset is not None and subset.shape[1]:
-                ids = torch.where(ids >= 0, subset.long().gather(1, ids.clamp(min=0)), ids)
-            ids = ids.cpu()
+        elif not 1 <= int(nbest) <= ops.CTC_LEXICON_MAX_NBEST:
+            raise ValueError(f"tensor2lexicon: nbest must lie in 1..{ops.CTC_LEXICON_MAX_NBEST}, got {nbest}")
+        ids, best = self._lexicon_pick(outputs.float(), nbest, normalized, beam=width, subset=subset)
+        ids = ids.long()
+        if subset is not None and subset.shape[1]:                           # positions in the subset -> positions in the lexicon
+            ids = torch.where(ids >= 0, subset.long().gather(1, ids.clamp(min=0)), ids)
+        ids = ids.cpu()
         words, lengths = self.lexicon.words, self.lexicon.lengths
         indexes = [[words[v, :lengths[v]].tolist() for v in row if v >= 0] for row in ids.tolist()]
         return indexes, best.cpu(), ids
@@ -313,6 +231,57 @@ class CTCConvertor:
         if self.lexicon_trie is None:
             self.lexicon_trie = ops.ctc_lexicon_trie(self.lexicon)
         return self.lexicon_trie
+
+    # ------------------------------------------------------------------ the configured decoder: each choice is made here, once
+    def _beam(self, scores, width, normalized):
+        """(paths, lengths, hyp_scores) of the prefix beam search of `width`, fused with the language model where one is set."""
+        from .. import ops
+        if self.lm is not None:
+            return ops.ctc_beam_search_lm(scores, width, self.lm, self.lm_weight, self.lm_bonus, self.lm_eos, normalized=normalized)
+        return ops.ctc_beam_search(scores, width, normalized=normalized)
+
+    def _lexicon_pick(self, scores, nbest, normalized, beam=None, subset=None):
+        """(index int32 [N, nbest], log_probs fp32 [N, nbest]) of the lexicon's best words, -1 and -inf in an empty slot: by the search
+        over the trie with beam (default: lexicon_beam) > 0, by scoring every word - of subset[i] where given - otherwise."""
+        from .. import ops
+        width = self.lexicon_beam if beam is None else beam
+        if width > 0:
+            return ops.ctc_lexicon_search(scores, self._trie(), width, nbest=nbest, normalized=normalized)
+        return ops.ctc_lexicon_best(ops.ctc_lexicon_score(scores, self.lexicon, normalized=normalized, subset=subset), nbest)
+
+    def _lexicon_paths(self, scores):
+        """The best lexicon word of every sample as -1-padded int32 paths [B, max_len] (all -1 where no word has an alignment of finite
+        probability): the pick and plain indexing, nothing is read back."""
+        index, _ = self._lexicon_pick(scores, 1, True)
+        words = self.lexicon.on(scores.device)[0]
+        if not words.shape[0]:
+            return torch.full((scores.shape[0], 1), -1, dtype=torch.int32, device=scores.device)
+        best = index[:, 0].long()
+        rows = words[best.clamp(min=0)]
+        ended = (rows == 0).cumsum(dim=1) > 0                                 # behind the word's first zero
+        return torch.where(ended | (best < 0)[:, None], -1, rows).to(torch.int32)
+
+    def best_paths(self, scores):
+        """What TextAccuracy scores on the device: the rank-0 word of the configured decoder for [N, T, C] probabilities, as -1-padded
+        int32 paths [N, width] (any row stride) - of the lexicon, else of the beam (LM-fused where an LM is set); None at beam_width 0
+        without a lexicon: the greedy rule, which ops.text_score_ctc applies to the frames itself.  No host synchronisation."""
+        if self.lexicon is not None:
+            return self._lexicon_paths(scores)
+        if self.beam_width > 0:
+            return self._beam(scores, self.beam_width, True)[0][:, 0]
+        return None
+
+    @torch.no_grad()
+    def tensor2best(self, outputs):
+        """The host-side counterpart of best_paths: the best word of every sample as a list of class indices ([] where the decoder
+        returns no word), by the lexicon, else the beam, else the greedy rule."""
+        if self.lexicon is not None:
+            nbest = self.tensor2lexicon(outputs, nbest=1)[0]
+        elif self.beam_width > 0:
+            nbest = self.tensor2nbest(outputs, nbest=1)[0]
+        else:
+            return self.tensor2idx(outputs)[0]
+        return [words[0] if words else [] for words in nbest]
 
     # ------------------------------------------------------------------ alignment
     @torch.no_grad()
@@ -341,12 +310,9 @@ class CTCConvertor:
         elif self.lexicon is not None:
             if not 1 <= k <= ops.CTC_LEXICON_MAX_NBEST:
                 raise ValueError(f"tensor2align: nbest must lie in 1..{ops.CTC_LEXICON_MAX_NBEST}, got {nbest}")
-            if self.lexicon_beam > 0:                                        # the words the trie search picks
-                if k > self.lexicon_beam:
-                    raise ValueError(f"tensor2align: nbest must lie in 1..lexicon_beam = {self.lexicon_beam}, got {nbest}")
-                index, _ = ops.ctc_lexicon_search(scores, self._trie(), self.lexicon_beam, nbest=k, normalized=normalized)
-            else:
-                index, _ = ops.ctc_lexicon_best(ops.ctc_lexicon_score(scores, self.lexicon, normalized=normalized), k)
+            if 0 < self.lexicon_beam < k:                                    # the trie search proposes lexicon_beam words
+                raise ValueError(f"tensor2align: nbest must lie in 1..lexicon_beam = {self.lexicon_beam}, got {nbest}")
+            index, _ = self._lexicon_pick(scores, k, normalized)
             table = self.lexicon.on(scores.device)[0]
             if table.shape[0]:
                 targets = table[index.long().clamp(min=0).flatten()]
@@ -356,11 +322,7 @@ class CTCConvertor:
         elif self.beam_width > 0:
             if not 1 <= k <= self.beam_width:
                 raise ValueError(f"tensor2align: nbest must lie in 1..beam_width = {self.beam_width}, got {nbest}")
-            if self.lm is not None:
-                paths, lengths, _ = ops.ctc_beam_search_lm(scores, self.beam_width, self.lm, self.lm_weight, self.lm_bonus, self.lm_eos,
-                                                           normalized=normalized)
-            else:
-                paths, lengths, _ = ops.ctc_beam_search(scores, self.beam_width, normalized=normalized)
+            paths, lengths, _ = self._beam(scores, self.beam_width, normalized)
             lengths = lengths[:, :k]
             targets = ops.ctc_paths_to_targets(paths[:, :k]).flatten(0, 1)
             rows = torch.where((lengths >= 0) & (lengths <= ops.CTC_MAX_LABELS), sample[:, None], -1).flatten()

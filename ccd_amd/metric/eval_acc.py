@@ -17,11 +17,10 @@ those of `update` on the decoded strings: the counts exactly, `ned` up to the or
 `AttnConvertor.score_table()` (None when max_seq_len steps of the longest class do not fit the kernel: host path) and takes the
 first maximum of the scores themselves where `tensor2idx` takes the maximum of their softmax; the two differ only where two
 classes of a step are closer than the softmax resolves.  With a CTCConvertor the same path decodes by the greedy CTC rule
-(ops.text_score_ctc: repeats collapsed, blanks dropped); everything behind the decode step is shared.  A CTCConvertor with
-`beam_width` > 0 decodes by CTC prefix beam search instead (ops.ctc_beam_search on the head's probabilities) and scores the best
-word (ops.text_score_paths): three launches per batch, still no host synchronisation.  A CTCConvertor with a lexicon scores the most
-probable word OF THE LEXICON instead: ops.ctc_lexicon_score on the probabilities, ops.ctc_lexicon_best, a gather of the winning rows of
-the word list into -1-padded paths, ops.text_score_paths - no host synchronisation either (host path: `tensor2lexicon`).  An AttnConvertor with `beam_width` > 0
+(ops.text_score_ctc: repeats collapsed, blanks dropped); everything behind the decode step is shared.  A CTCConvertor configured
+with a beam (`beam_width` > 0, with or without a language model) or a lexicon (with or without `lexicon_beam`) decodes the head's
+probabilities itself - `CTCConvertor.best_paths`, the one place that picks the decoder - and the best word's -1-padded paths are
+scored by ops.text_score_paths, still without a host synchronisation (host path: `CTCConvertor.tensor2best`).  An AttnConvertor with `beam_width` > 0
 makes `compute` decode by beam search over the NRTR decoder (`DINO_Finetune.forward_beam`) and score the best word the same way
 (`update_paths`; on the host path: `idx2str` of `paths2nbest`); `forward_test` itself stays greedy.
 An AttnConvertor with a lexicon (and its `lexicon_beam`) makes `compute` decode over that closed vocabulary instead: rank 0 of
@@ -55,12 +54,6 @@ def encode_truth(strings):
     codes = np.zeros((len(strings), max(1, int(lens.max(initial=0)))), dtype=np.int32)
     codes[np.arange(codes.shape[1], dtype=np.int32)[None, :] < lens[:, None]] = flat
     return codes, lens
-
-
-def _to_device(array, device):
-    """numpy -> device without a host synchronisation: through pinned memory, asynchronously (a CPU `device`: no copy)."""
-    t = torch.from_numpy(array)
-    return t.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else t
 
 
 def levenshtein(a: str, b: str) -> int:
@@ -118,7 +111,7 @@ class TextAccuracy:
             if tables is None:
                 raise ValueError(f"{who}: max_seq_len steps of the convertor's longest class exceed ops.TEXT_COLS characters; "
                                  "score on the host with update()")
-            cached = (convertor, dev) + tuple(_to_device(t, dev) for t in tables)
+            cached = (convertor, dev) + tuple(ops.upload(torch.from_numpy(t), dev) for t in tables)
             setattr(self, slot, cached)
         if cached is None:
             raise ValueError(f"{who}: pass the model's label convertor")
@@ -130,7 +123,7 @@ class TextAccuracy:
         codes, lens = encode_truth(gt_text)
         if len(lens) != samples:
             raise ValueError(f"{who}: {samples} samples but {len(lens)} ground-truth strings")
-        both = _to_device(np.concatenate([codes.ravel(), lens]), dev)         # one host-to-device copy for both
+        both = ops.upload(torch.from_numpy(np.concatenate([codes.ravel(), lens])), dev)        # one host-to-device copy for both
         return both[:codes.size].view(codes.shape), both[codes.size:]
 
     def _accumulate(self, records):
@@ -146,36 +139,12 @@ class TextAccuracy:
         self._refuse_case_sensitive()
         conv, _, raw, norm = self._device_tables("update_scores", "_tables", convertor, lambda c: c.score_table(), scores.device)
         gt, gt_len = self._upload_truth("update_scores", gt_text, scores.shape[0], scores.device)
-        if is_ctc(conv) and conv.lexicon is not None:                         # the most probable word of the lexicon
-            records = ops.text_score_paths(self._lexicon_paths(conv, scores), raw, norm, gt, gt_len)
-        elif is_ctc(conv) and conv.beam_width > 0 and getattr(conv, "lm", None) is not None:     # the beam fused with the language model
-            paths, _, _ = ops.ctc_beam_search_lm(scores, conv.beam_width, conv.lm, conv.lm_weight, conv.lm_bonus, conv.lm_eos, normalized=True)
-            records = ops.text_score_paths(paths[:, 0], raw, norm, gt, gt_len)
-        elif is_ctc(conv) and conv.beam_width > 0:                            # prefix beam search on the probabilities, rank 0 scored
-            paths, _, _ = ops.ctc_beam_search(scores, conv.beam_width, normalized=True)
-            records = ops.text_score_paths(paths[:, 0], raw, norm, gt, gt_len)
-        elif is_ctc(conv):                                                    # CTCConvertor: frames, not decoding steps
-            records = ops.text_score_ctc(scores, raw, norm, gt, gt_len)
+        if is_ctc(conv):                                                      # frames, not decoding steps
+            paths = conv.best_paths(scores)                                   # None: the greedy rule, applied by the scoring kernel
+            records = ops.text_score_ctc(scores, raw, norm, gt, gt_len) if paths is None else ops.text_score_paths(paths, raw, norm, gt, gt_len)
         else:
             records = ops.text_score(scores, raw, norm, conv.end_idx, conv.padding_idx, gt, gt_len)
         return self._accumulate(records)
-
-    @staticmethod
-    def _lexicon_paths(conv, scores):
-        """The best lexicon word of every sample as -1-padded int32 paths [B, max_len] (all -1 where no word has an alignment of finite
-        probability): two launches and plain indexing, nothing is read back.  With lexicon_beam > 0 the word is the trie search's
-        (ops.ctc_lexicon_search: three launches and a sort, nothing read back either)."""
-        if getattr(conv, "lexicon_beam", 0) > 0:
-            index, _ = ops.ctc_lexicon_search(scores, conv._trie(), conv.lexicon_beam, nbest=1, normalized=True)
-        else:
-            index, _ = ops.ctc_lexicon_best(ops.ctc_lexicon_score(scores, conv.lexicon, normalized=True), 1)
-        words = conv.lexicon.on(scores.device)[0]
-        if not words.shape[0]:
-            return torch.full((scores.shape[0], 1), -1, dtype=torch.int32, device=scores.device)
-        best = index[:, 0].long()
-        rows = words[best.clamp(min=0)]
-        ended = (rows == 0).cumsum(dim=1) > 0                                 # behind the word's first zero
-        return torch.where(ended | (best < 0)[:, None], -1, rows).to(torch.int32)
 
     def update_paths(self, paths, gt_text, convertor):
         """Score one batch of decoded words on the device: paths int32 [B, T] (any row stride: rank 0 of forward_beam's paths), the
@@ -232,12 +201,10 @@ class TextAccuracy:
             elif attn_beam:
                 nbest = convertor.paths2nbest(*net.forward_beam(image_tensors, convertor.beam_width))[0]
             else:
+                nbest = None
                 out_dec = model(image_tensors, text=None, return_loss=False, test_speed=False)
-                # a CTC beam: the best word of the beam (the kernel, on any device)
-                nbest = convertor.tensor2nbest(out_dec, nbest=1)[0] if is_ctc(convertor) and convertor.beam_width > 0 else None
-                if is_ctc(convertor) and convertor.lexicon is not None:       # the best word of the lexicon (the kernels, on any device)
-                    nbest = convertor.tensor2lexicon(out_dec, nbest=1)[0]
-            label_indexes = convertor.tensor2idx(out_dec)[0] if nbest is None else [words[0] if words else [] for words in nbest]
+            # the best word of the configured decoder: a CTC beam or lexicon runs its kernels, on any device
+            label_indexes = convertor.tensor2best(out_dec) if nbest is None else [words[0] if words else [] for words in nbest]
             pt_text = convertor.idx2str(label_indexes)
             self.inference_time += time.time() - start
             self.update(list(label_tensors[0]), pt_text)

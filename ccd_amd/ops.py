@@ -97,6 +97,27 @@ def _call(name, *args):
     _lib.check(code, name)
 
 
+def upload(t, device):
+    """A host tensor on `device` without a host synchronisation: through pinned memory and asynchronously to a GPU, a plain `.to` to
+    the CPU (no copy)."""
+    return t.pin_memory().to(device, non_blocking=True) if torch.device(device).type == "cuda" else t.to(device)
+
+
+class _OncePerDevice:
+    """A handle built on the host whose device copy is made once per device: `_upload(device)` says what the copy is, `on(device)`
+    returns it."""
+
+    _copies = None
+
+    def on(self, device):
+        if self._copies is None:
+            self._copies = {}
+        key = str(device)
+        if key not in self._copies:
+            self._copies[key] = self._upload(device)
+        return self._copies[key]
+
+
 def _ld(t):
     """(tensor, leading stride) of an optional 2-D operand: (None, 0) when it is absent."""
     return (None, 0) if t is None else (t, t.stride(0))
@@ -892,13 +913,31 @@ def ctc_loss_bwd(logits, C, targets, T, ws, upstream=None, ldd=None):
     return d
 
 
+def _frame_scores(who, scores, what="scores"):
+    """The check every CTC decoder starts with: `what` fp32 [B, T, C] with contiguous classes (any sample / step stride) -> (B, T, C)."""
+    if scores.dim() != 3 or (scores.shape[2] > 1 and scores.stride(2) != 1):
+        raise ValueError(f"{who}: expects {what} [B, T, C] with contiguous classes, got {list(scores.shape)}, strides {scores.stride()}")
+    return scores.shape
+
+
+def _beam_width(who, beam_width, limit):
+    W = int(beam_width)
+    if not 1 <= W <= limit:
+        raise ValueError(f"{who}: beam_width must lie in 1..{limit}, got {beam_width}")
+    return W
+
+
+def _beam_outputs(B, W, T, device):
+    """(paths int32 [B, W, T], lengths int32 [B, W], hyp_scores fp32 [B, W]) for a beam decoder to fill."""
+    return (torch.empty((B, W, T), dtype=I32, device=device), torch.empty((B, W), dtype=I32, device=device),
+            torch.empty((B, W), dtype=F32, device=device))
+
+
 def ctc_greedy(logits):
     """logits fp32 [B, T, C] (any sample / step stride) -> (path int32 [B, T] left-aligned, -1-padded; length int32 [B]; conf fp32
     [B, T]): arg-max class per frame (first maximum), repeats collapsed, blanks dropped; conf = the softmax probability of the first
     frame of each kept run."""
-    if logits.dim() != 3 or (logits.shape[2] > 1 and logits.stride(2) != 1):
-        raise ValueError(f"ctc_greedy: expects logits [B, T, C] with contiguous classes, got {list(logits.shape)}, strides {logits.stride()}")
-    B, T, C = logits.shape
+    B, T, C = _frame_scores("ctc_greedy", logits, "logits")
     path = torch.empty((B, T), dtype=I32, device=logits.device)
     length = torch.empty(B, dtype=I32, device=logits.device)
     conf = torch.empty((B, T), dtype=F32, device=logits.device)
@@ -911,15 +950,9 @@ def ctc_beam_search(scores, beam_width, normalized=False):
     probabilities, as CTCDecoder.forward_test returns them -> (paths int32 [B, W, T] by rank, -1-padded; lengths int32 [B, W], -1 for
     an unused slot; hyp_scores fp32 [B, W]: the log of the word's probability summed over the alignments the beam kept, -inf for an
     unused slot).  W = beam_width in 1..CTC_MAX_BEAM."""
-    if scores.dim() != 3 or (scores.shape[2] > 1 and scores.stride(2) != 1):
-        raise ValueError(f"ctc_beam_search: expects scores [B, T, C] with contiguous classes, got {list(scores.shape)}, strides {scores.stride()}")
-    B, T, C = scores.shape
-    W = int(beam_width)
-    if not 1 <= W <= CTC_MAX_BEAM:
-        raise ValueError(f"ctc_beam_search: beam_width must lie in 1..{CTC_MAX_BEAM}, got {beam_width}")
-    paths = torch.empty((B, W, T), dtype=I32, device=scores.device)
-    lengths = torch.empty((B, W), dtype=I32, device=scores.device)
-    hyp_scores = torch.empty((B, W), dtype=F32, device=scores.device)
+    B, T, C = _frame_scores("ctc_beam_search", scores)
+    W = _beam_width("ctc_beam_search", beam_width, CTC_MAX_BEAM)
+    paths, lengths, hyp_scores = _beam_outputs(B, W, T, scores.device)
     _call("ccd_ctc_beam_search", scores, scores.stride(0), scores.stride(1), B, T, C, 1 if normalized else 0, W, paths, lengths, hyp_scores)
     return paths, lengths, hyp_scores
 
@@ -928,20 +961,15 @@ def ctc_beam_search(scores, beam_width, normalized=False):
 CTC_LM_MAX_ORDER = 3                                      # ccd_hip.h: CCD_CTC_LM_MAX_ORDER
 
 
-class CTCCharLM:
+class CTCCharLM(_OncePerDevice):
     """A character n-gram table for ctc_beam_search_lm (build it with ctc_char_lm): `table` fp32 [C^(order-1), C] on the host; a device
     copy is uploaded once per device."""
 
     def __init__(self, table, order):
         self.table, self.order, self.classes = table, order, table.shape[1]
-        self._device = {}
 
-    def on(self, device):
-        key = str(device)
-        if key not in self._device:                                  # no host synchronisation: through pinned memory, asynchronously
-            cuda = torch.device(device).type == "cuda"
-            self._device[key] = self.table.pin_memory().to(device, non_blocking=True) if cuda else self.table.to(device)
-        return self._device[key]
+    def _upload(self, device):
+        return upload(self.table, device)
 
 
 def ctc_char_lm(table, order):
@@ -970,20 +998,13 @@ def ctc_beam_search_lm(scores, beam_width, lm, weight=1.0, bonus=0.0, eos=False,
     hypothesis scores log p_ctc(word | kept alignments) + weight * sum lm + bonus * len(word); eos=True adds weight * lm[row, 0] behind
     the last frame and ranks the hypotheses again (a -inf one becomes an unused slot).  weight = 0, bonus = 0 and a finite table give
     ctc_beam_search's result bit for bit."""
-    if scores.dim() != 3 or (scores.shape[2] > 1 and scores.stride(2) != 1):
-        raise ValueError(f"ctc_beam_search_lm: expects scores [B, T, C] with contiguous classes, got {list(scores.shape)}, strides "
-                         f"{scores.stride()}")
+    B, T, C = _frame_scores("ctc_beam_search_lm", scores)
     if not isinstance(lm, CTCCharLM):
         raise TypeError(f"ctc_beam_search_lm: lm must come from ctc_char_lm, got {type(lm).__name__}")
-    B, T, C = scores.shape
     if lm.classes != C:
         raise ValueError(f"ctc_beam_search_lm: the table was built for {lm.classes} classes, the scores have {C}")
-    W = int(beam_width)
-    if not 1 <= W <= CTC_MAX_BEAM:
-        raise ValueError(f"ctc_beam_search_lm: beam_width must lie in 1..{CTC_MAX_BEAM}, got {beam_width}")
-    paths = torch.empty((B, W, T), dtype=I32, device=scores.device)
-    lengths = torch.empty((B, W), dtype=I32, device=scores.device)
-    hyp_scores = torch.empty((B, W), dtype=F32, device=scores.device)
+    W = _beam_width("ctc_beam_search_lm", beam_width, CTC_MAX_BEAM)
+    paths, lengths, hyp_scores = _beam_outputs(B, W, T, scores.device)
     _call("ccd_ctc_beam_search_lm", scores, scores.stride(0), scores.stride(1), B, T, C, 1 if normalized else 0, W, lm.on(scores.device),
           lm.order, float(weight), float(bonus), 1 if eos else 0, paths, lengths, hyp_scores)
     return paths, lengths, hyp_scores
@@ -994,7 +1015,7 @@ CTC_LEXICON_MAX_NBEST = 16                                # ccd_hip.h: CCD_CTC_L
 CTC_LEXICON_CLASSES = (7, 15, CTC_MAX_LABELS)             # longest word of a length class: 16 / 32 / 64 lanes per word
 
 
-class CTCLexicon:
+class CTCLexicon(_OncePerDevice):
     """A word list for ctc_lexicon_score (build it with ctc_lexicon): `words` int64 [V, max_len] on the host, in the caller's order;
     a device copy in that order and up to three length-class slices (L <= 7, <= 15, <= 31), each (words int64 [n, class width],
     columns int32 [n]), are uploaded once per device."""
@@ -1002,26 +1023,20 @@ class CTCLexicon:
     def __init__(self, words):
         self.words = words
         self.lengths = (words != 0).to(I64).cumprod(dim=1).sum(dim=1) if words.shape[0] else torch.zeros(0, dtype=I64)
-        self._device = {}
 
     def __len__(self):
         return self.words.shape[0]
 
-    def on(self, device):
+    def _upload(self, device):
         """(words on `device`, [(slice words, columns)])"""
-        key = str(device)
-        if key not in self._device:
-            def up(t):                                               # no host synchronisation: through pinned memory, asynchronously
-                return t.pin_memory().to(device, non_blocking=True) if torch.device(device).type == "cuda" else t.to(device)
-            slices, lo = [], -1
-            for hi in CTC_LEXICON_CLASSES:
-                cols = torch.nonzero((self.lengths > lo) & (self.lengths <= hi)).flatten()
-                lo = hi
-                if cols.numel():
-                    width = min(hi, self.words.shape[1])
-                    slices.append((up(self.words[cols][:, :width].contiguous()), up(cols.to(I32))))
-            self._device[key] = (up(self.words), slices)
-        return self._device[key]
+        slices, lo = [], -1
+        for hi in CTC_LEXICON_CLASSES:
+            cols = torch.nonzero((self.lengths > lo) & (self.lengths <= hi)).flatten()
+            lo = hi
+            if cols.numel():
+                width = min(hi, self.words.shape[1])
+                slices.append((upload(self.words[cols][:, :width].contiguous(), device), upload(cols.to(I32), device)))
+        return upload(self.words, device), slices
 
 
 def ctc_lexicon(words):
@@ -1041,11 +1056,9 @@ def ctc_lexicon_score(scores, lexicon, normalized=False, subset=None):
     all alignments, -inf for a word no alignment of finite probability spells (a class outside [1, C), more characters than frames, a
     masked class).  subset int32 [B, K]: sample b scores only the words subset[b, k] -> fp32 [B, K], -inf where an entry is negative
     (padding) or >= V."""
-    if scores.dim() != 3 or (scores.shape[2] > 1 and scores.stride(2) != 1):
-        raise ValueError(f"ctc_lexicon_score: expects scores [B, T, C] with contiguous classes, got {list(scores.shape)}, strides {scores.stride()}")
+    B, T, C = _frame_scores("ctc_lexicon_score", scores)
     if not isinstance(lexicon, CTCLexicon):
         raise TypeError(f"ctc_lexicon_score: lexicon must come from ctc_lexicon, got {type(lexicon).__name__}")
-    B, T, C = scores.shape
     V = len(lexicon)
     words, slices = lexicon.on(scores.device)
     flag = 1 if normalized else 0
@@ -1086,7 +1099,7 @@ def ctc_lexicon_best(word_scores, nbest=1):
 CTC_TRIE_NODE_WORDS = 8                                   # ccd_hip.h: int32 words per node of ccd_ctc_beam_search_trie's table
 
 
-class CTCLexiconTrie:
+class CTCLexiconTrie(_OncePerDevice):
     """The prefix tree of a lexicon for ctc_beam_search_trie / ctc_lexicon_search (build it with ctc_lexicon_trie): `nodes` int32
     [n_nodes, 8] on the host (the layout: ctc_lexicon_trie), `lexicon` the CTCLexicon it was built from, `stats` = {'nodes', 'bytes',
     'terminals'}; a device copy is uploaded once per device."""
@@ -1094,14 +1107,9 @@ class CTCLexiconTrie:
     def __init__(self, lexicon, nodes):
         self.lexicon, self.nodes, self.n_nodes = lexicon, nodes, nodes.shape[0]
         self.stats = {"nodes": self.n_nodes, "bytes": self.n_nodes * CTC_TRIE_NODE_WORDS * 4, "terminals": int((nodes[:, 5] >= 0).sum())}
-        self._device = {}
 
-    def on(self, device):
-        key = str(device)
-        if key not in self._device:                                  # no host synchronisation: through pinned memory, asynchronously
-            cuda = torch.device(device).type == "cuda"
-            self._device[key] = self.nodes.pin_memory().to(device, non_blocking=True) if cuda else self.nodes.to(device)
-        return self._device[key]
+    def _upload(self, device):
+        return upload(self.nodes, device)
 
 
 def _trie_nodes(words):
@@ -1174,18 +1182,11 @@ def ctc_beam_search_trie(scores, beam_width, trie, normalized=False):
     edge of the trie and is a hypothesis only where a word ends; prefixes that end no word compete for the beam's slots during the
     search, so a narrow beam may end with no word at all.  hyp_scores is a lower bound of ctc_lexicon_score's number for that word: the
     sum over the alignments the beam kept.  The cost does not depend on the size of the lexicon."""
-    if scores.dim() != 3 or (scores.shape[2] > 1 and scores.stride(2) != 1):
-        raise ValueError(f"ctc_beam_search_trie: expects scores [B, T, C] with contiguous classes, got {list(scores.shape)}, strides "
-                         f"{scores.stride()}")
+    B, T, C = _frame_scores("ctc_beam_search_trie", scores)
     if not isinstance(trie, CTCLexiconTrie):
         raise TypeError(f"ctc_beam_search_trie: trie must come from ctc_lexicon_trie, got {type(trie).__name__}")
-    B, T, C = scores.shape
-    W = int(beam_width)
-    if not 1 <= W <= CTC_MAX_BEAM:
-        raise ValueError(f"ctc_beam_search_trie: beam_width must lie in 1..{CTC_MAX_BEAM}, got {beam_width}")
-    paths = torch.empty((B, W, T), dtype=I32, device=scores.device)
-    lengths = torch.empty((B, W), dtype=I32, device=scores.device)
-    hyp_scores = torch.empty((B, W), dtype=F32, device=scores.device)
+    W = _beam_width("ctc_beam_search_trie", beam_width, CTC_MAX_BEAM)
+    paths, lengths, hyp_scores = _beam_outputs(B, W, T, scores.device)
     word_ids = torch.empty((B, W), dtype=I32, device=scores.device)
     _call("ccd_ctc_beam_search_trie", scores, scores.stride(0), scores.stride(1), B, T, C, 1 if normalized else 0, W, trie.on(scores.device),
           trie.n_nodes, paths, lengths, hyp_scores, word_ids)
@@ -1222,9 +1223,7 @@ def ctc_align(scores, targets, normalized=False, rows=None):
     last frame of every character, -1 behind the word; char_logp fp32 [N, Lmax]: the summed frame log-probability of every character;
     score fp32 [N]: the log-probability of the alignment).  An infeasible row (a class outside [1, C), more characters than frames, no
     alignment of finite probability, a rows entry outside [0, B)) has score -inf and padding everywhere else."""
-    if scores.dim() != 3 or (scores.shape[2] > 1 and scores.stride(2) != 1):
-        raise ValueError(f"ctc_align: expects scores [B, T, C] with contiguous classes, got {list(scores.shape)}, strides {scores.stride()}")
-    B, T, C = scores.shape
+    B, T, C = _frame_scores("ctc_align", scores)
     if targets.dim() != 2 or not targets.is_contiguous():
         raise ValueError(f"ctc_align: expects contiguous targets [N, Lmax], got {list(targets.shape)}")
     N, Lmax = targets.shape
@@ -1261,9 +1260,7 @@ NRTR_UNUSED, NRTR_LIVE, NRTR_FINISHED = 0, 1, 2           # ccd_hip.h: CCD_NRTR_
 def nrtr_beam_state(B, beam_width, seq_len, start_idx, pad_idx, device):
     """The state in front of step 0 -> (seq int64 [B * W, seq_len] = start, padding, ...; score fp64 [B, W] = 0, -inf, ...; state int32
     [B, W] = live, unused, ...; parent int32 [B, W])."""
-    W = int(beam_width)
-    if not 1 <= W <= NRTR_MAX_BEAM:
-        raise ValueError(f"nrtr_beam_state: beam_width must lie in 1..{NRTR_MAX_BEAM}, got {beam_width}")
+    W = _beam_width("nrtr_beam_state", beam_width, NRTR_MAX_BEAM)
     seq = torch.full((B * W, seq_len), pad_idx, dtype=I64, device=device)
     seq[:, 0] = start_idx
     score = torch.full((B, W), float("-inf"), dtype=F64, device=device)
@@ -1273,44 +1270,51 @@ def nrtr_beam_state(B, beam_width, seq_len, start_idx, pad_idx, device):
     return seq, score, state, torch.full((B, W), -1, dtype=I32, device=device)
 
 
+def _nrtr_beam_step(who, logits, C, step, end_idx, pad_idx, seq, score, state, parent, final, node=None, trie=None, class_offset=1):
+    """The body of nrtr_beam_step (trie None) and nrtr_beam_step_trie: the checks under the caller's name `who`, the outputs of the
+    final step, the launch."""
+    if score.dim() != 2 or not 1 <= score.shape[1] <= NRTR_MAX_BEAM:
+        raise ValueError(f"{who}: score must be [B, W] with W in 1..{NRTR_MAX_BEAM}, got {list(score.shape)}")
+    B, W = score.shape
+    slots = [("score", score, F64), ("state", state, I32), ("parent", parent, I32)] + ([("node", node, I32)] if trie is not None else [])
+    for name, t, dtype in slots + [("seq", seq, I64), ("logits", logits, F32)]:
+        if t.dtype != dtype:
+            raise ValueError(f"{who}: {name} must be {dtype}, got {t.dtype}")
+    for name, t, _ in slots:
+        if tuple(t.shape) != (B, W) or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous [{B}, {W}], got {list(t.shape)}")
+    if seq.dim() != 2 or seq.shape[0] != B * W or not seq.is_contiguous():
+        raise ValueError(f"{who}: seq must be contiguous [{B * W}, seq_len], got {list(seq.shape)}")
+    if logits.dim() != 2 or logits.shape[0] != B * W or logits.stride(1) != 1 or not 1 <= int(C) <= logits.shape[1]:
+        raise ValueError(f"{who}: expects logits [{B * W}, >= {C}] with dense rows, got {list(logits.shape)}")
+    seq_len = seq.shape[1]
+    if not 0 <= int(step) <= seq_len - 2:
+        raise ValueError(f"{who}: step must lie in 0..seq_len - 2 = {seq_len - 2}, got {step}")
+    if not 0 <= int(end_idx) < int(C) or not 0 <= int(pad_idx) < 65536:
+        raise ValueError(f"{who}: end_idx must lie in [0, {C}) and pad_idx in [0, 65536), got {end_idx}, {pad_idx}")
+    if trie is not None and (isinstance(class_offset, bool) or class_offset not in (0, 1)):
+        raise ValueError(f"{who}: class_offset must be 0 or 1, got {class_offset!r}")
+    out = _beam_outputs(B, W, seq_len - 1, seq.device) if final else (None, None, None)
+    args = (logits, logits.stride(0), B, W, int(C), int(step), int(end_idx), int(pad_idx), seq, seq_len, score, state, parent, *out)
+    if trie is None:
+        _call("ccd_nrtr_beam_step", *args)
+    else:
+        out += (torch.empty((B, W), dtype=I32, device=seq.device) if final else None,)
+        _call("ccd_nrtr_beam_step_trie", *args, trie.on(seq.device), trie.n_nodes, int(class_offset), node, out[3])
+    return out if final else None
+
+
 def nrtr_beam_step(logits, C, step, end_idx, pad_idx, seq, score, state, parent, final=False):
     """One decoding position of the beam over the NRTR decoder, in place: logits fp32 [B * W, ld >= C] (row b * W + r = slot r of sample
     b), seq int64 [B * W, seq_len], score fp64 [B, W], state int32 [B, W], parent int32 [B, W] (written) - the layout of ccd_hip.h.
     Writes seq[:, step + 1].  final=True also returns (paths int32 [B, W, seq_len - 1] by rank, -1-padded; lengths int32 [B, W], -1
     for an unused slot; hyp_scores fp32 [B, W], -inf for an unused slot) of the new state, as ctc_beam_search returns them."""
-    if score.dim() != 2 or not 1 <= score.shape[1] <= NRTR_MAX_BEAM:
-        raise ValueError(f"nrtr_beam_step: score must be [B, W] with W in 1..{NRTR_MAX_BEAM}, got {list(score.shape)}")
-    B, W = score.shape
-    for name, t, dtype in (("score", score, F64), ("state", state, I32), ("parent", parent, I32), ("seq", seq, I64), ("logits", logits, F32)):
-        if t.dtype != dtype:
-            raise ValueError(f"nrtr_beam_step: {name} must be {dtype}, got {t.dtype}")
-    for name, t in (("score", score), ("state", state), ("parent", parent)):
-        if tuple(t.shape) != (B, W) or not t.is_contiguous():
-            raise ValueError(f"nrtr_beam_step: {name} must be contiguous [{B}, {W}], got {list(t.shape)}")
-    if seq.dim() != 2 or seq.shape[0] != B * W or not seq.is_contiguous():
-        raise ValueError(f"nrtr_beam_step: seq must be contiguous [{B * W}, seq_len], got {list(seq.shape)}")
-    if logits.dim() != 2 or logits.shape[0] != B * W or logits.stride(1) != 1 or not 1 <= int(C) <= logits.shape[1]:
-        raise ValueError(f"nrtr_beam_step: expects logits [{B * W}, >= {C}] with dense rows, got {list(logits.shape)}")
-    seq_len = seq.shape[1]
-    if not 0 <= int(step) <= seq_len - 2:
-        raise ValueError(f"nrtr_beam_step: step must lie in 0..seq_len - 2 = {seq_len - 2}, got {step}")
-    if not 0 <= int(end_idx) < int(C) or not 0 <= int(pad_idx) < 65536:
-        raise ValueError(f"nrtr_beam_step: end_idx must lie in [0, {C}) and pad_idx in [0, 65536), got {end_idx}, {pad_idx}")
-    out = (None, None, None)
-    if final:
-        out = (torch.empty((B, W, seq_len - 1), dtype=I32, device=seq.device), torch.empty((B, W), dtype=I32, device=seq.device),
-               torch.empty((B, W), dtype=F32, device=seq.device))
-    _call("ccd_nrtr_beam_step", logits, logits.stride(0), B, W, int(C), int(step), int(end_idx), int(pad_idx), seq, seq_len, score, state,
-          parent, *out)
-    return out if final else None
+    return _nrtr_beam_step("nrtr_beam_step", logits, C, step, end_idx, pad_idx, seq, score, state, parent, final)
 
 
 def nrtr_beam_trie_state(B, beam_width, device):
     """The trie node of every slot in front of step 0 -> node int32 [B, W], all zeros: the root of the lexicon's prefix tree."""
-    W = int(beam_width)
-    if not 1 <= W <= NRTR_MAX_BEAM:
-        raise ValueError(f"nrtr_beam_trie_state: beam_width must lie in 1..{NRTR_MAX_BEAM}, got {beam_width}")
-    return torch.zeros((B, W), dtype=I32, device=device)
+    return torch.zeros((B, _beam_width("nrtr_beam_trie_state", beam_width, NRTR_MAX_BEAM)), dtype=I32, device=device)
 
 
 def nrtr_beam_step_trie(logits, C, step, end_idx, pad_idx, seq, score, state, parent, node, trie, class_offset=1, final=False):
@@ -1320,36 +1324,9 @@ def nrtr_beam_step_trie(logits, C, step, end_idx, pad_idx, seq, score, state, pa
     along an edge of its node and ends only where a word ends; the scores are nrtr_beam_step's, so a finished slot holds the exact
     log-probability of its word with the <EOS>.  final=True returns (paths, lengths, hyp_scores) as nrtr_beam_step does and word_ids
     int32 [B, W]: the lexicon row of every finished slot, -1 for a slot that is unused or still live."""
-    if not isinstance(trie, CTCLexiconTrie):
+    if not isinstance(trie, CTCLexiconTrie):                         # (None included: it would select the plain step)
         raise TypeError(f"nrtr_beam_step_trie: trie must come from ctc_lexicon_trie, got {type(trie).__name__}")
-    if score.dim() != 2 or not 1 <= score.shape[1] <= NRTR_MAX_BEAM:
-        raise ValueError(f"nrtr_beam_step_trie: score must be [B, W] with W in 1..{NRTR_MAX_BEAM}, got {list(score.shape)}")
-    B, W = score.shape
-    for name, t, dtype in (("score", score, F64), ("state", state, I32), ("parent", parent, I32), ("node", node, I32), ("seq", seq, I64),
-                           ("logits", logits, F32)):
-        if t.dtype != dtype:
-            raise ValueError(f"nrtr_beam_step_trie: {name} must be {dtype}, got {t.dtype}")
-    for name, t in (("score", score), ("state", state), ("parent", parent), ("node", node)):
-        if tuple(t.shape) != (B, W) or not t.is_contiguous():
-            raise ValueError(f"nrtr_beam_step_trie: {name} must be contiguous [{B}, {W}], got {list(t.shape)}")
-    if seq.dim() != 2 or seq.shape[0] != B * W or not seq.is_contiguous():
-        raise ValueError(f"nrtr_beam_step_trie: seq must be contiguous [{B * W}, seq_len], got {list(seq.shape)}")
-    if logits.dim() != 2 or logits.shape[0] != B * W or logits.stride(1) != 1 or not 1 <= int(C) <= logits.shape[1]:
-        raise ValueError(f"nrtr_beam_step_trie: expects logits [{B * W}, >= {C}] with dense rows, got {list(logits.shape)}")
-    seq_len = seq.shape[1]
-    if not 0 <= int(step) <= seq_len - 2:
-        raise ValueError(f"nrtr_beam_step_trie: step must lie in 0..seq_len - 2 = {seq_len - 2}, got {step}")
-    if not 0 <= int(end_idx) < int(C) or not 0 <= int(pad_idx) < 65536:
-        raise ValueError(f"nrtr_beam_step_trie: end_idx must lie in [0, {C}) and pad_idx in [0, 65536), got {end_idx}, {pad_idx}")
-    if isinstance(class_offset, bool) or class_offset not in (0, 1):
-        raise ValueError(f"nrtr_beam_step_trie: class_offset must be 0 or 1, got {class_offset!r}")
-    out = (None, None, None, None)
-    if final:
-        out = (torch.empty((B, W, seq_len - 1), dtype=I32, device=seq.device), torch.empty((B, W), dtype=I32, device=seq.device),
-               torch.empty((B, W), dtype=F32, device=seq.device), torch.empty((B, W), dtype=I32, device=seq.device))
-    _call("ccd_nrtr_beam_step_trie", logits, logits.stride(0), B, W, int(C), int(step), int(end_idx), int(pad_idx), seq, seq_len, score,
-          state, parent, *out[:3], trie.on(seq.device), trie.n_nodes, int(class_offset), node, out[3])
-    return out if final else None
+    return _nrtr_beam_step("nrtr_beam_step_trie", logits, C, step, end_idx, pad_idx, seq, score, state, parent, final, node, trie, class_offset)
 
 
 def nrtr_beam_reorder(cache, parent, positions, step):
@@ -1374,7 +1351,7 @@ XATTN_ROWS_MAX_TQ = 32                                    # queries of a word ro
 NRTR_MAX_CLASSES, NRTR_MAX_POSITIONS = 128, 128           # nrtr_beam.h: NRTR_MAX_C, NRTR_MAX_LEN
 
 
-class CsrRows:
+class CsrRows(_OncePerDevice):
     """Which sample owns which word row, in CSR form: the rows of sample b are ptr[b] .. ptr[b + 1] - 1.  Built and checked on the host
     (csr_rows below) - the counts are host knowledge, the word lists - and uploaded once per device."""
 
@@ -1382,13 +1359,9 @@ class CsrRows:
         self.ptr = ptr                                    # numpy int32 [B + 1]
         self.B, self.R = len(ptr) - 1, int(ptr[-1])
         self.max_rows = int(np.diff(ptr).max()) if len(ptr) > 1 else 0
-        self._on = {}
 
-    def on(self, device):
-        key = str(device)
-        if key not in self._on:
-            self._on[key] = torch.from_numpy(self.ptr).to(device, non_blocking=True)
-        return self._on[key]
+    def _upload(self, device):
+        return upload(torch.from_numpy(self.ptr), device)
 
 
 def csr_rows(ptr):

@@ -19,6 +19,7 @@ from Dino.metric.eval_acc import TextAccuracy
 from Dino.model.dino_vision import DINO_Finetune
 from Dino.modules import utils
 from Dino.utils.utils import Config, Logger
+from ccd_amd import decoding_cli
 from ccd_amd.dataset.dataset_pretrain import ImageDataset, collate_fn_filter_none
 from ccd_amd.parallel import DataParallel
 from train import _lmdb_dirs
@@ -137,20 +138,7 @@ def main():
     ap.add_argument("--checkpoint", type=str, default=None)
     ap.add_argument("--test_root", type=str, default=None)
     ap.add_argument("--batch_size", type=int, default=None)
-    ap.add_argument("--beam_width", type=int, default=None,
-                    help="beam search of this width, 1..16, for either head (CTC: prefix beam search; NRTR: beam over the decoder); 0: greedy decoding")
-    ap.add_argument("--lexicon", type=str, default=None,
-                    help="evaluate with lexicon-constrained decoding over this UTF-8 word list (one word per line); excludes a beam.  The NRTR "
-                         "head needs --lexicon_beam with it")
-    ap.add_argument("--lexicon_beam", type=int, default=None,
-                    help="with a lexicon: search its prefix tree with a beam of this width, 1..16, and score only the proposed words "
-                         "exactly - the cost no longer grows with the lexicon; 0: score every word (CTC head).  NRTR head: the width of the "
-                         "beam over the decoder that walks the lexicon's prefix tree, 1..16; its scores are exact already")
-    ap.add_argument("--lm", type=str, default=None,
-                    help="fuse a character n-gram language model into the CTC beam search: an .npz of CharNGram.save, or a UTF-8 word list "
-                         "(estimated at decoder.lm_order); needs a beam, excludes a lexicon")
-    ap.add_argument("--lm_weight", type=float, default=None, help="weight of the language model's log-probabilities (default 1.0)")
-    ap.add_argument("--lm_bonus", type=float, default=None, help="added per decoded character (default 0.0)")
+    decoding_cli.add_decoding_flags(ap)
     ap.add_argument("--alignments", type=str, default=None, metavar="PATH",
                     help="next to the accuracy run write one JSON line per image to PATH - ground truth, predicted word, the log-probability of "
                          "its best alignment, and per character x0, x1, first / last frame and confidence (the CTC head only)")
@@ -167,15 +155,7 @@ def main():
         config.dataset_test_roots = [a.test_root]
     if a.batch_size is not None:
         config.dataset_test_batch_size = a.batch_size
-    if a.beam_width is not None:
-        config.decoder_beam_width = a.beam_width
-    if a.lexicon is not None:
-        config.decoder_lexicon = a.lexicon
-    if a.lexicon_beam is not None:
-        config.decoder_lexicon_beam = a.lexicon_beam
-    for key in ("lm", "lm_weight", "lm_bonus"):
-        if getattr(a, key) is not None:
-            setattr(config, f"decoder_{key}", getattr(a, key))
+    decoding_cli.apply_decoding_flags(a, config)
     Logger.init(config.global_workdir, config.global_name, "test")
     utils.fix_random_seeds(int(config.global_seed or 0))
     logging.info("Construct dataset.")
@@ -183,12 +163,7 @@ def main():
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
     torch.cuda.set_device(device)
     model = DINO_Finetune(config).to(device)
-    if getattr(model.label_convertor, "lexicon_stats", None):
-        logging.info(f"lexicon {config.decoder_lexicon} (lexicon_beam {getattr(model.label_convertor, 'lexicon_beam', 0)}): "
-                     f"{model.label_convertor.lexicon_stats}")
-    if getattr(model.label_convertor, "lm_stats", None):
-        conv = model.label_convertor
-        logging.info(f"language model {config.decoder_lm}: {conv.lm_stats}, weight {conv.lm_weight}, bonus {conv.lm_bonus}, eos {conv.lm_eos}")
+    decoding_cli.log_decoding(model.label_convertor, config)
     model.ensure_arena()
     model = DataParallel(model)
     if config.model_checkpoint:

@@ -181,7 +181,8 @@ def test_lexicon_beam_reaches_the_convertor_from_the_config(tmp_path):
 
 
 def test_command_lines_take_a_lexicon_beam():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for name in ("test.py", "train_finetune.py"):
-        src = open(os.path.join(root, name)).read()
-        assert '"--lexicon_beam"' in src and "config.decoder_lexicon_beam = " in src, name
+    from decoding_flags import SCRIPTS, declared
+    for name in SCRIPTS:
+        helps, configure = declared(name)
+        assert "--lexicon_beam" in helps and configure(["--lexicon_beam", "16"]) == {"decoder_lexicon_beam": 16}, name
+        assert configure([]) == {}, name                                      # a flag that is absent leaves the YAML's value

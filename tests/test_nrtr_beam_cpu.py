@@ -81,6 +81,8 @@ def test_yaml_and_cli_width_reach_the_nrtr_head(tmp_path):
     config.decoder_beam_width = 17                                             # what --beam_width 17 sets
     with pytest.raises(ValueError, match="beam_width must lie in 0..16"):
         DINO_Finetune(config)
-    for script in ("test.py", "train_finetune.py"):
-        source = open(os.path.join(root, script)).read()
-        assert "--beam_width" in source and "either head" in source and 'help="CTC head' not in source
+    from decoding_flags import SCRIPTS, declared
+    for script in SCRIPTS:
+        helps, configure = declared(script)
+        assert "either head" in helps["--beam_width"] and not any(text.startswith("CTC head") for text in helps.values())
+        assert configure(["--beam_width", "17"]) == {"decoder_beam_width": 17}

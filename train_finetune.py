@@ -25,6 +25,7 @@ import torch.utils.data
 from Dino.model.dino_vision import DINO_Finetune
 from Dino.modules import utils
 from Dino.utils.utils import Config, Logger
+from ccd_amd import decoding_cli
 from ccd_amd import finetune as ft
 from ccd_amd.convertor.ctc import is_ctc
 from ccd_amd.parallel import DataParallel
@@ -121,12 +122,7 @@ def main(config):
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
     utils.fix_random_seeds(int(config.global_seed or config.seed or 0))
     model = DINO_Finetune(config).to(device)
-    if getattr(model.label_convertor, "lexicon_stats", None):
-        logging.info(f"lexicon {config.decoder_lexicon} (lexicon_beam {getattr(model.label_convertor, 'lexicon_beam', 0)}): "
-                     f"{model.label_convertor.lexicon_stats}")
-    if getattr(model.label_convertor, "lm_stats", None):
-        conv = model.label_convertor
-        logging.info(f"language model {config.decoder_lm}: {conv.lm_stats}, weight {conv.lm_weight}, bonus {conv.lm_bonus}, eos {conv.lm_eos}")
+    decoding_cli.log_decoding(model.label_convertor, config)
     model.ensure_arena()
     model = DataParallel(model)                          # `module.` key prefix like nn.DataParallel; reducer when world > 1
     model.train()
@@ -212,31 +208,10 @@ def _parse_arguments():
     parser = argparse.ArgumentParser()
     parser.add_argument("-c", "--config", type=str, required=True, help="path to config file")
     parser.add_argument("--local_rank", "--local-rank", default=0, type=int, help="set by the launcher; ignored")
-    parser.add_argument("--beam_width", type=int, default=None,
-                        help="evaluate with beam search of this width, 1..16, for either head (CTC: prefix beam search; NRTR: beam over the decoder); 0: greedy")
-    parser.add_argument("--lexicon", type=str, default=None,
-                        help="evaluate with lexicon-constrained decoding over this UTF-8 word list (one word per line); excludes a beam.  The NRTR "
-                             "head needs --lexicon_beam with it")
-    parser.add_argument("--lexicon_beam", type=int, default=None,
-                        help="with a lexicon: search its prefix tree with a beam of this width, 1..16, and score only the proposed words "
-                             "exactly - the cost no longer grows with the lexicon; 0: score every word (CTC head).  NRTR head: the width of the "
-                             "beam over the decoder that walks the lexicon's prefix tree, 1..16; its scores are exact already")
-    parser.add_argument("--lm", type=str, default=None,
-                        help="evaluate the CTC head with a character n-gram language model fused into the beam search: an .npz of CharNGram.save, "
-                             "or a UTF-8 word list (estimated at decoder.lm_order); needs a beam, excludes a lexicon")
-    parser.add_argument("--lm_weight", type=float, default=None, help="weight of the language model's log-probabilities (default 1.0)")
-    parser.add_argument("--lm_bonus", type=float, default=None, help="added per decoded character (default 0.0)")
+    decoding_cli.add_decoding_flags(parser, training=True)
     args, _ = parser.parse_known_args()
     config = Config(args.config)
-    if args.beam_width is not None:
-        config.decoder_beam_width = args.beam_width
-    if args.lexicon is not None:
-        config.decoder_lexicon = args.lexicon
-    if args.lexicon_beam is not None:
-        config.decoder_lexicon_beam = args.lexicon_beam
-    for key in ("lm", "lm_weight", "lm_bonus"):
-        if getattr(args, key) is not None:
-            setattr(config, f"decoder_{key}", getattr(args, key))
+    decoding_cli.apply_decoding_flags(args, config)
     return config
 
 
