@@ -19,7 +19,7 @@ _stream_override = None   # tests of the ABI may pin the stream argument
 
 HEADER_PATH = os.path.join(_HERE, "..", "include", "ccd_hip.h")
 
-_SCALARS = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "uint64_t": C.c_uint64, "const char*": C.c_char_p}
+_SCALARS = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double, "uint64_t": C.c_uint64, "const char*": C.c_char_p}
 _RETURNS = {"int": C.c_int, "long": C.c_long, "const char*": C.c_char_p}
 # element type of a pointer parameter -> the tensor dtypes it takes (None: untyped, any dtype)
 _ELEMENT_DTYPES = {"float": (torch.float32,), "ccd_bf16": (torch.bfloat16,), "uint16_t": (torch.float16,), "double": (torch.float64,),

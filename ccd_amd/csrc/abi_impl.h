@@ -26,6 +26,7 @@
 #include "kernels/ctc.h"
 #include "kernels/ctc_beam.h"
 #include "kernels/nrtr_beam.h"
+#include "kernels/nrtr_joint.h"
 #include "kernels/ctc_lexicon.h"
 #include "kernels/ctc_align.h"
 #include "kernels/datapipe.h"
@@ -343,7 +344,7 @@ static int ccd_seg_prepare(int images, long pixels, int* cm, int* status, int* c
 
 extern "C" {
 
-int ccd_abi_version(void) { return 28; }   // 28: ccd_xattn_rows_fwd, ccd_xattn_rows_chunk, ccd_nrtr_word_score (scoring given words with the NRTR decoder: per-image lexicons, character positions); 27: ccd_nrtr_beam_step_trie (lexicon-constrained beam search over the NRTR decoder); 26: ccd_ctc_beam_search_trie (trie beam search over a lexicon in the CTC beam search); 25: ccd_ctc_align (CTC forced alignment); 24: ccd_ctc_beam_search_lm (character n-gram language-model fusion in the CTC beam search); 23: ccd_ctc_lexicon_score, ccd_ctc_lexicon_best (lexicon-constrained decoding of the CTC head); 22: ccd_nrtr_beam_step, ccd_nrtr_beam_reorder (beam search over the NRTR decoder); 21: ccd_ctc_beam_search, ccd_text_score_paths (CTC prefix beam search, n-best word scores); 20: ccd_ctc_pool_fwd / _bwd, ccd_ctc_loss_fwd / _bwd, ccd_ctc_greedy, ccd_text_score_ctc (the CTC recognition head); 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
+int ccd_abi_version(void) { return 29; }   // 29: ccd_nrtr_joint_begin, ccd_nrtr_beam_step_joint (joint CTC / attention decoding: the NRTR beam rescored with CTC prefix probabilities); 28: ccd_xattn_rows_fwd, ccd_xattn_rows_chunk, ccd_nrtr_word_score (scoring given words with the NRTR decoder: per-image lexicons, character positions); 27: ccd_nrtr_beam_step_trie (lexicon-constrained beam search over the NRTR decoder); 26: ccd_ctc_beam_search_trie (trie beam search over a lexicon in the CTC beam search); 25: ccd_ctc_align (CTC forced alignment); 24: ccd_ctc_beam_search_lm (character n-gram language-model fusion in the CTC beam search); 23: ccd_ctc_lexicon_score, ccd_ctc_lexicon_best (lexicon-constrained decoding of the CTC head); 22: ccd_nrtr_beam_step, ccd_nrtr_beam_reorder (beam search over the NRTR decoder); 21: ccd_ctc_beam_search, ccd_text_score_paths (CTC prefix beam search, n-best word scores); 20: ccd_ctc_pool_fwd / _bwd, ccd_ctc_loss_fwd / _bwd, ccd_ctc_greedy, ccd_text_score_ctc (the CTC recognition head); 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
 const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi16"; }
 int ccd_policy_set(const char* key, int value) {
     CCD_CHECK(key, CCD_EINVAL);
@@ -1534,6 +1535,34 @@ int ccd_nrtr_beam_step_trie(const float* logits, long ldl, int batch, int beam, 
     CCD_LAUNCH(ccd::nrtr_beam_step_kernel<true>, dim3((unsigned)batch), dim3(64), 0, stream, logits, ldl, beam, classes, step, end_idx,
                pad_idx, reinterpret_cast<long long*>(seq), seq_len, score, state, parent, paths, lengths, hyp_scores,
                ccd::NrtrBeamTrie{nodes, n_nodes, class_offset, node, word_ids});
+    return ccd_rt_last_error();
+}
+int ccd_nrtr_joint_begin(const float* frames, long sample_stride, long step_stride, int batch, int ctc_steps, int ctc_classes, int normalized,
+                         int beam, double* log_probs, double* prefix, void* stream) {
+    CCD_CHECK(batch >= 0 && sample_stride >= 0 && step_stride >= 0, CCD_EINVAL);
+    CCD_CHECK(beam >= 1 && beam <= ccd::NRTR_MAX_BEAM && ctc_steps >= 1 && ctc_steps <= ccd::NRTR_JOINT_MAX_T && ctc_classes >= 1 &&
+              ctc_classes <= ccd::NRTR_MAX_C && (normalized == 0 || normalized == 1), CCD_ESHAPE);
+    if (batch == 0) return CCD_OK;
+    CCD_CHECK(frames && log_probs && prefix, CCD_EINVAL);
+    CCD_LAUNCH(ccd::nrtr_joint_begin_kernel, dim3((unsigned)batch), dim3(64), 0, stream, frames, sample_stride, step_stride, ctc_steps,
+               ctc_classes, normalized, beam, log_probs, prefix);
+    return ccd_rt_last_error();
+}
+int ccd_nrtr_beam_step_joint(const float* logits, long ldl, int batch, int beam, int classes, int step, int end_idx, int pad_idx,
+                             int64_t* seq, int seq_len, double* score, int* state, int* parent, int* paths, int* lengths,
+                             float* hyp_scores, const double* log_probs, int ctc_steps, int ctc_classes, int class_offset, double weight,
+                             double* prefix, double* att, float* att_scores, void* stream) {
+    CCD_CHECK(batch >= 0 && ldl >= 0 && step >= 0, CCD_EINVAL);
+    CCD_CHECK(beam >= 1 && beam <= ccd::NRTR_MAX_BEAM && classes >= 1 && classes <= ccd::NRTR_MAX_C && ldl >= classes && seq_len >= 2 &&
+              seq_len <= ccd::NRTR_MAX_LEN && step + 2 <= seq_len && end_idx >= 0 && end_idx < classes && pad_idx >= 0 && pad_idx < 65536 &&
+              ctc_steps >= 1 && ctc_steps <= ccd::NRTR_JOINT_MAX_T && ctc_classes >= 1 && ctc_classes <= ccd::NRTR_MAX_C &&
+              class_offset >= 0 && class_offset <= 1 && weight >= 0.0 && weight <= 1.0, CCD_ESHAPE);      // (a NaN weight fails both)
+    if (batch == 0) return CCD_OK;
+    CCD_CHECK(logits && seq && score && state && parent && log_probs && prefix && att, CCD_EINVAL);
+    CCD_CHECK((paths && lengths && hyp_scores && att_scores) || (!paths && !lengths && !hyp_scores && !att_scores), CCD_EINVAL);
+    CCD_LAUNCH(ccd::nrtr_beam_step_joint_kernel, dim3((unsigned)batch), dim3(64), 0, stream, logits, ldl, beam, classes, step, end_idx,
+               pad_idx, reinterpret_cast<long long*>(seq), seq_len, score, state, parent, paths, lengths, hyp_scores,
+               ccd::NrtrJoint{log_probs, ctc_steps, ctc_classes, class_offset, weight, prefix, att, att_scores});
     return ccd_rt_last_error();
 }
 int ccd_nrtr_beam_reorder(ccd_bf16* cache, const int* parent, int layers, int batch, int beam, int positions, int D, int step, void* stream) {

@@ -100,6 +100,7 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
         self.beam_width = 0            # forward_beam's default width (DINO_Finetune sets it from decoder.beam_width); 0: none
         self._beam_graphs = {}
         self._trie_graphs = {}         # forward_beam(trie=): graphs of their own, keyed by the trie as well
+        self._joint_graphs = {}        # forward_beam(ctc_frames=): graphs of their own, keyed by the frames' shape and the weight too
 
     def _transposed_names(self):
         names = []
@@ -135,29 +136,35 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
             return self._graphed_decode(out_enc)
         return fe.greedy_decode(self, out_enc)
 
-    def _replay(self, graphs, key, decode, out_enc):
+    def _replay(self, graphs, key, decode, out_enc, *more):
         """The 25 decoding steps launch ~1 800 small kernels (6 layers x ~12 kernels per step): launch-bound when issued one
         by one.  The whole loop `decode(input)` is captured ONCE per `key` into a HIP graph, on a single stream, and replayed; the
         graph reads the arena / packed operands in place, so optimizer steps between evaluations need no re-capture.
+        `more`: further input tensors of `decode` (dense), each a graph input buffer of its own like out_enc.
         -> the graph's static outputs, which the caller clones."""
         entry = graphs.get(key)
         if entry is None:
             static_in = torch.empty_like(out_enc)
             static_in.copy_(out_enc)
+            static_more = tuple(torch.empty_like(t) for t in more)
+            for dst, src in zip(static_more, more):
+                dst.copy_(src)
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream(device=out_enc.device)
             side.wait_stream(cur)
             with torch.cuda.stream(side):                  # warm-up outside the capture (lazy one-time kernel attributes)
-                decode(static_in)
+                decode(static_in, *static_more)
             cur.wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                static_out = decode(static_in)
+                static_out = decode(static_in, *static_more)
             if len(graphs) >= 4:                           # a few batch shapes at most (last partial batch, ...)
                 graphs.pop(next(iter(graphs)))
-            entry = graphs[key] = (graph, static_in, static_out)
-        graph, static_in, static_out = entry
+            entry = graphs[key] = (graph, static_in, static_out) + static_more
+        graph, static_in, static_out = entry[:3]
         static_in.copy_(out_enc)
+        for dst, src in zip(entry[3:], more):
+            dst.copy_(src)
         graph.replay()
         return static_out
 
@@ -166,7 +173,7 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
         key = (tuple(out_enc.shape), out_enc.device, self.arena.flat.data_ptr())
         return self._replay(self._graphs, key, lambda x: fe.greedy_decode(self, x), out_enc).clone()
 
-    def forward_beam(self, feat, out_enc, beam_width=None, trie=None):
+    def forward_beam(self, feat, out_enc, beam_width=None, trie=None, ctc_frames=None, ctc_weight=None):
         """Beam search of width `beam_width` (default: self.beam_width, which must then be > 0) -> (paths int32 [N, W, max_seq_len] by
         rank, -1-padded; lengths int32 [N, W], -1 for an unused slot; scores fp32 [N, W], the log-probability of the word with its
         <EOS>, -inf for an unused slot): fe.beam_decode.  On the GPU the loop is captured into a HIP graph per (batch shape, width) and
@@ -174,10 +181,18 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
         trie: an ops.ctc_lexicon_trie handle (AttnConvertor.lexicon_trie: rows class + 1) - the beam walks the lexicon's prefix tree
         and a fourth tensor comes back, word_ids int32 [N, W]: the lexicon row of every finished hypothesis, -1 for a slot that is
         unused or still a prefix.  The trie's device copy is made before the capture; the graphs of this path are kept apart from
-        the plain beam's, one per (batch shape, width, trie)."""
+        the plain beam's, one per (batch shape, width, trie).
+        ctc_frames: fp32 [N, Tc <= 64, Cc <= 128] logits of an auxiliary CTC head (class c of the decoder is its class c + 1), with
+        ctc_weight w in [0, 1] - joint CTC / attention decoding (fe.beam_decode, kernels/nrtr_joint.h): scores are S = (1 - w)
+        attention + w CTC and a fourth tensor comes back, att_scores fp32 [N, W], the attention parts.  Excludes a trie.  The frames
+        are an input buffer of a graph of their own kind, one per (batch shape, width, frames' shape, weight)."""
         from ..ops import NRTR_MAX_BEAM, CTCLexiconTrie
         if trie is not None and not isinstance(trie, CTCLexiconTrie):
             raise TypeError(f"forward_beam: trie must come from ops.ctc_lexicon_trie, got {type(trie).__name__}")
+        if ctc_frames is not None and trie is not None:
+            raise ValueError("forward_beam: ctc_frames (joint CTC / attention decoding) excludes a trie")
+        if (ctc_frames is None) != (ctc_weight is None):
+            raise ValueError("forward_beam: ctc_frames and ctc_weight come together")
         width = int(self.beam_width if beam_width is None else beam_width)
         if not 1 <= width <= NRTR_MAX_BEAM:
             raise ValueError(f"forward_beam: beam_width must lie in 1..{NRTR_MAX_BEAM}, got {width}")
@@ -185,7 +200,22 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
         out_enc = out_enc.to(torch.bfloat16)
         if trie is not None:
             trie.on(out_enc.device)                        # the upload happens here, never inside a capture
-        if out_enc.is_cuda and os.environ.get("CCD_DECODE_GRAPH", "1") != "0":
+        graphed = out_enc.is_cuda and os.environ.get("CCD_DECODE_GRAPH", "1") != "0"
+        if ctc_frames is not None:
+            w = float(ctc_weight)
+            if ctc_frames.dim() != 3 or ctc_frames.shape[0] != out_enc.shape[0] or ctc_frames.dtype != torch.float32:
+                raise ValueError(f"forward_beam: ctc_frames must be float32 [{out_enc.shape[0]}, Tc, Cc], got {ctc_frames.dtype} "
+                                 f"{list(ctc_frames.shape)}")
+            if not 0.0 <= w <= 1.0:
+                raise ValueError(f"forward_beam: ctc_weight must lie in [0, 1], got {ctc_weight!r}")
+            if not graphed:
+                return fe.beam_decode(self, out_enc, width, ctc_frames=ctc_frames, ctc_weight=w)
+            frames = ctc_frames.contiguous()
+            key = (tuple(out_enc.shape), out_enc.device, self.arena.flat.data_ptr(), width, tuple(frames.shape), w)
+            out = self._replay(self._joint_graphs, key, lambda x, f: fe.beam_decode(self, x, width, ctc_frames=f, ctc_weight=w), out_enc,
+                               frames)
+            return tuple(t.clone() for t in out)
+        if graphed:
             return self._graphed_beam(out_enc, width, trie)
         return fe.beam_decode(self, out_enc, width, trie)
 

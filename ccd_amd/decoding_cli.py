@@ -1,10 +1,11 @@
-"""The decoding flags of test.py and train_finetune.py, declared once: --beam_width, --lexicon, --lexicon_beam and the --lm group, their
-copy into `config.decoder_*`, and the log lines that say which lexicon and language model the built model decodes with."""
+"""The decoding flags of test.py and train_finetune.py, declared once: --beam_width, --lexicon, --lexicon_beam, the --lm group and
+--joint_ctc_weight, their copy into `config.decoder_*`, and the log lines that say which lexicon and language model the built model
+decodes with."""
 from __future__ import annotations
 
 import logging
 
-DECODING_FLAGS = ("beam_width", "lexicon", "lexicon_beam", "lm", "lm_weight", "lm_bonus")      # flag `--x` sets `config.decoder_x`
+DECODING_FLAGS = ("beam_width", "lexicon", "lexicon_beam", "lm", "lm_weight", "lm_bonus", "joint_ctc_weight")      # flag `--x` sets `config.decoder_x`
 
 
 def add_decoding_flags(parser, training=False):
@@ -26,6 +27,10 @@ def add_decoding_flags(parser, training=False):
                         ": an .npz of CharNGram.save, or a UTF-8 word list (estimated at decoder.lm_order); needs a beam, excludes a lexicon")
     parser.add_argument("--lm_weight", type=float, default=None, help="weight of the language model's log-probabilities (default 1.0)")
     parser.add_argument("--lm_bonus", type=float, default=None, help="added per decoded character (default 0.0)")
+    parser.add_argument("--joint_ctc_weight", type=float, default=None,
+                        help="NRTR head with an auxiliary CTC head (decoder.aux_ctc_weight): joint CTC / attention decoding - the beam over the "
+                             "decoder is rescored with the CTC prefix probability of every candidate at this weight, 0..1; needs --beam_width "
+                             "1..16, excludes a lexicon")
 
 
 def apply_decoding_flags(args, config):

@@ -411,7 +411,7 @@ def greedy_decode(module, out_enc, stop_on_eos_of_first=False):
 
 
 @torch.no_grad()
-def beam_decode(module, out_enc, beam_width, trie=None):
+def beam_decode(module, out_enc, beam_width, trie=None, ctc_frames=None, ctc_weight=0.0):
     """Beam search of width W over the incremental decoder of `greedy_decode` (the rules: INTEGRATION.md, "Beam search over the NRTR
     decoder"; kernels/nrtr_beam.h) -> (paths int32 [B, W, max_seq_len] by rank, -1-padded; lengths int32 [B, W]; scores fp32 [B, W]),
     as ops.ctc_beam_search returns them.  The W hypotheses of a sample are rows b * W .. b * W + W - 1 of every activation: the
@@ -421,7 +421,12 @@ def beam_decode(module, out_enc, beam_width, trie=None):
     normalisation, no early exit: all max_seq_len steps run, nothing is read back.
     trie: an ops.ctc_lexicon_trie handle whose rows are class + 1 (AttnConvertor.set_lexicon) - the selection walks the lexicon's
     prefix tree (ops.nrtr_beam_step_trie: a slot extends only along an edge and ends only where a word ends, at the plain beam's scores)
-    and the result gains word_ids int32 [B, W], the lexicon row of every finished hypothesis (-1: unused, or still a prefix)."""
+    and the result gains word_ids int32 [B, W], the lexicon row of every finished hypothesis (-1: unused, or still a prefix).
+    ctc_frames: fp32 [B, Tc, Cc] logits of an auxiliary CTC head whose class c + 1 is the decoder's class c, with ctc_weight w in [0, 1] -
+    joint CTC / attention decoding ("Joint CTC / attention decoding"; ops.nrtr_beam_step_joint): the selection runs
+    over S = (1 - w) attention score + w CTC prefix score, `scores` is S and the result gains att_scores fp32 [B, W].  Excludes trie."""
+    if trie is not None and ctc_frames is not None:
+        raise ValueError("beam_decode: ctc_frames (joint CTC / attention decoding) excludes a trie")
     arena, pre, spec = module.arena, module.arena_prefix, module.dec_spec
     B, W = out_enc.shape[0], int(beam_width)
     D, L, C = spec.D, spec.L, spec.C
@@ -433,10 +438,14 @@ def beam_decode(module, out_enc, beam_width, trie=None):
     seq, score, state, parent = ops.nrtr_beam_state(B, W, T, spec.start_idx, spec.padding_idx, dev)
     cache = torch.zeros((L, R * T, 3 * D), dtype=BF16, device=dev)     # q | k | v of position t of every hypothesis
     node = ops.nrtr_beam_trie_state(B, W, dev) if trie is not None else None
+    joint = ops.nrtr_joint_state(ctc_frames, W) if ctc_frames is not None else None
     out = None
     for s in range(steps):
         logits = decoder_position(module, s, seq, cache, kv, R, W)                           # W queries per sample
-        if trie is not None:
+        if joint is not None:
+            out = ops.nrtr_beam_step_joint(logits, C, s, spec.start_idx, spec.padding_idx, seq, score, state, parent, joint,
+                                           float(ctc_weight), class_offset=1, final=s == steps - 1)
+        elif trie is not None:
             out = ops.nrtr_beam_step_trie(logits, C, s, spec.start_idx, spec.padding_idx, seq, score, state, parent, node, trie,
                                           class_offset=1, final=s == steps - 1)
         else:

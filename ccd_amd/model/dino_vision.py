@@ -9,6 +9,8 @@ Differences from the reference that are invisible at the boundary:
 """
 from __future__ import annotations
 
+import logging
+
 import torch
 import torch.nn as nn
 
@@ -20,6 +22,9 @@ from ..utils.DBSCAN import DBSCAN_cluster, label_cluster
 # keeps its character regions on the device as id maps (ops.ccl_label) and does not go through these.
 dbscan = DBSCAN_cluster(eps=1.5, min_samples=4)
 label = label_cluster()
+
+
+AUX_CTC_CLASSES = 92             # the auxiliary CTC head of the hybrid model: the blank, DICT90's 90 characters, <UKN>
 
 
 def _absent(value, default):
@@ -155,11 +160,22 @@ class DINO_Finetune(ArenaModule):
     log-probabilities), which TextAccuracy then scores the best word of, and `decoder.lexicon: <path>` together with
     `decoder.lexicon_beam: N` (1..16; either alone is refused) makes evaluation decode over that word list instead: `forward_lexicon`,
     a beam of width N along the lexicon's prefix tree.  `forward_test` and `forward_test_speed` return the greedy
-    probabilities whatever the width: a beam has no per-step distribution to return."""
+    probabilities whatever the width: a beam has no per-step distribution to return.
+    `decoder.aux_ctc_weight: a`, 0 < a < 1, on the NRTR recogniser makes it the hybrid CTC / attention model: an auxiliary
+    `ctc_decoder = CTCDecoder(embed_dim, 92)` on the same backbone tokens, trained under (1 - a) TFLoss + a CTCLoss (the parts:
+    `last_losses`), read through `forward_ctc`; absent or 0 is the model without it, key for key.  `decoder.joint_ctc_weight: w` in
+    [0, 1] - it needs that head and `decoder.beam_width` in 1..16, and excludes a lexicon - makes `forward_beam` rescore every
+    candidate with the CTC prefix probability of its characters (kernels/nrtr_joint.h)."""
+
+    aux_ctc_weight = 0.0               # decoder.aux_ctc_weight; > 0: the model owns ctc_decoder and ctc_loss
+    joint_ctc_weight = None            # decoder.joint_ctc_weight; a number: forward_beam decodes jointly
+    last_losses = None                 # hybrid: {'tf', 'ctc'}, the two parts of the last forward_train as device scalars
+    last_att_scores = None             # joint decoding: the attention scores of the last forward_beam, fp32 [N, W]
 
     def __init__(self, config):
         super().__init__()
         self.ctc = getattr(config, "decoder_type", None) == "CTCDecoder"
+        aux, joint = self._checked_hybrid_keys(config)
         if self.ctc:
             self._init_ctc(config)
             return
@@ -188,6 +204,47 @@ class DINO_Finetune(ArenaModule):
             start_idx=config.decoder_start_idx, padding_idx=config.decoder_padding_idx)
         self.decoder.beam_width = self.label_convertor.beam_width
         self.loss = TFLoss(ignore_index=self.label_convertor.padding_idx)
+        if joint is not None and self.label_convertor.lexicon is not None:
+            raise ValueError("decoder.joint_ctc_weight excludes decoder.lexicon / decoder.lexicon_beam: joint decoding along a lexicon's "
+                             "prefix tree is not implemented")
+        if joint is not None and self.label_convertor.beam_width < 1:
+            raise ValueError("decoder.joint_ctc_weight needs decoder.beam_width in 1..16: the CTC prefix scores rescore a beam")
+        if aux > 0:                                        # (built last: the init RNG stream of everything above is the plain model's)
+            from ..decoder.ctc_decoder import CTCDecoder
+            from ..loss.ctc_loss import CTCLoss
+            self.ctc_decoder = CTCDecoder(in_features=embed_dim, num_classes=AUX_CTC_CLASSES)
+            self.ctc_loss = CTCLoss(blank=0, zero_infinity=True)
+        self.aux_ctc_weight, self.joint_ctc_weight = aux, joint
+
+    @staticmethod
+    def _checked_joint_weight(w):
+        if isinstance(w, bool) or not isinstance(w, (int, float)) or not 0.0 <= float(w) <= 1.0:
+            raise ValueError(f"decoder.joint_ctc_weight must lie in [0, 1], got {w!r}")
+        return float(w)
+
+    def _checked_hybrid_keys(self, config):
+        """(decoder.aux_ctc_weight, absent: 0; decoder.joint_ctc_weight, absent: None), checked against each other and the head."""
+        aux, joint = getattr(config, "decoder_aux_ctc_weight", None), getattr(config, "decoder_joint_ctc_weight", None)
+        aux = 0.0 if aux is None else aux
+        if isinstance(aux, bool) or not isinstance(aux, (int, float)) or not 0.0 <= float(aux) < 1.0:
+            raise ValueError(f"decoder.aux_ctc_weight must lie in [0, 1) (0: no auxiliary CTC head), got {aux!r}")
+        if joint is not None:
+            joint = self._checked_joint_weight(joint)
+        if self.ctc:                                       # a CTC head is the CTC model already: the auxiliary weight means nothing there
+            if joint is not None:
+                raise ValueError("decoder.joint_ctc_weight rescores the NRTR decoder's beam: decoder.type 'CTCDecoder' has none")
+            return 0.0, None
+        if joint is not None and not aux > 0:
+            raise ValueError("decoder.joint_ctc_weight needs decoder.aux_ctc_weight > 0: the auxiliary CTC head gives the prefix scores")
+        return float(aux), joint
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        """A checkpoint of the NRTR recogniser alone loads into the hybrid model: the auxiliary CTC head stays as it was initialised."""
+        keys = [prefix + "ctc_decoder.fc.weight", prefix + "ctc_decoder.fc.bias"]
+        if self.aux_ctc_weight > 0 and not any(k in state_dict for k in keys):
+            logging.info("the checkpoint holds no auxiliary CTC head (ctc_decoder.fc.*): it stays at its initialisation")
+            state_dict[keys[0]], state_dict[keys[1]] = self.ctc_decoder.fc.weight.detach(), self.ctc_decoder.fc.bias.detach()
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
 
     def _init_ctc(self, config):
         from ..convertor.ctc import CTCConvertor
@@ -216,7 +273,10 @@ class DINO_Finetune(ArenaModule):
         names = ["backbone." + n for n in self.backbone._transposed_names()]
         if not self.ctc:
             names += ["encoder." + n for n in self.encoder._transposed_names()]
-        return names + ["decoder." + n for n in self.decoder._transposed_names()]
+        names += ["decoder." + n for n in self.decoder._transposed_names()]
+        if self.aux_ctc_weight > 0:
+            names += ["ctc_decoder." + n for n in self.ctc_decoder._transposed_names()]
+        return names
 
     def attach_arena(self, arena, prefix):
         super().attach_arena(arena, prefix)
@@ -224,6 +284,8 @@ class DINO_Finetune(ArenaModule):
         if not self.ctc:
             self.encoder.attach_arena(arena, prefix + "encoder.")
         self.decoder.attach_arena(arena, prefix + "decoder.")
+        if self.aux_ctc_weight > 0:
+            self.ctc_decoder.attach_arena(arena, prefix + "ctc_decoder.")
 
     def unused_parameter_names(self):
         """cls_token and the three norm_seg LayerNorms never take part in this forward pass (their .grad stays None in
@@ -253,7 +315,28 @@ class DINO_Finetune(ArenaModule):
             return self.loss(self.decoder.forward_train(feat), targets_dict), None
         out_enc = self.encoder(feat)
         out_dec, attn = self.decoder(feat, out_enc, targets_dict, train_mode=True)
-        return self.loss(out_dec, targets_dict), attn
+        if not self.aux_ctc_weight > 0:
+            return self.loss(out_dec, targets_dict), attn
+        a = self.aux_ctc_weight                            # the hybrid objective: (1 - a) CE + a CTC over the same tokens
+        tf = self.loss(out_dec, targets_dict)
+        ctc = self.ctc_loss(self.ctc_decoder.forward_train(feat), {'padded_targets': self.ctc_targets(img_metas.to(feat.device))})
+        self.last_losses = {"tf": tf.detach(), "ctc": ctc.detach()}
+        return (1.0 - a) * tf + a * ctc, attn
+
+    def ctc_targets(self, padded_targets):
+        """The NRTR target rows int64 [N, T] = <BOS> chars <EOS> <PAD>.. -> the CTC targets int64 [N, T - 1], zero-padded: positions 1
+        onward, the classes in front of the first <EOS> as class + 1 (the blank is class 0), everything else 0.  On the rows' device."""
+        conv = self.label_convertor
+        body = padded_targets[:, 1:].long()
+        word = ((body == conv.end_idx).cumsum(dim=1) == 0) & (body != conv.padding_idx)
+        return torch.where(word, body + 1, torch.zeros_like(body)).contiguous()
+
+    def forward_ctc(self, img):
+        """img [N,3,32,128] -> the auxiliary CTC head's frame probabilities fp32 [N, 32, 92] (class 0 the blank, class c + 1 the NRTR
+        class c): what a CTCConvertor built beside the model decodes with any of its decoders."""
+        if not self.aux_ctc_weight > 0:
+            raise ValueError("forward_ctc: the model has no auxiliary CTC head (decoder.aux_ctc_weight)")
+        return self.ctc_decoder.forward_test(self.extract_feat(img))
 
     def forward_test(self, img):
         feat = self.extract_feat(img)
@@ -261,14 +344,26 @@ class DINO_Finetune(ArenaModule):
             return self.decoder.forward_test(feat)
         return self.decoder(feat, self.encoder(feat), None, train_mode=False)
 
-    def forward_beam(self, img, beam_width=None):
+    def forward_beam(self, img, beam_width=None, joint_ctc_weight=None):
         """img [N,3,32,128] -> (paths int32 [N, W, max_seq_len] by rank, -1-padded; lengths int32 [N, W]; scores fp32 [N, W]): the W
         best words of the NRTR decoder's beam search and their log-probabilities (NRTRDecoder.forward_beam; W defaults to
-        `decoder.beam_width`).  AttnConvertor.paths2nbest turns them into index lists."""
+        `decoder.beam_width`).  AttnConvertor.paths2nbest turns them into index lists.
+        joint_ctc_weight (default: `decoder.joint_ctc_weight`) = w in [0, 1] decodes jointly with the auxiliary CTC head: the beam runs
+        over S = (1 - w) log p_att + w log p_ctc, the CTC part being the prefix probability of a live hypothesis and the word's
+        probability of a finished one; `scores` is S and `last_att_scores` keeps the attention parts, fp32 [N, W]."""
         if self.ctc:
             raise NotImplementedError("forward_beam is the NRTR head's; the CTC head's beam is CTCConvertor.tensor2nbest on forward_test")
+        w = self.joint_ctc_weight if joint_ctc_weight is None else self._checked_joint_weight(joint_ctc_weight)
+        if w is not None and not self.aux_ctc_weight > 0:
+            raise ValueError("forward_beam: joint_ctc_weight needs the auxiliary CTC head (decoder.aux_ctc_weight)")
         feat = self.extract_feat(img)
-        return self.decoder.forward_beam(feat, self.encoder(feat), beam_width)
+        if w is None:
+            return self.decoder.forward_beam(feat, self.encoder(feat), beam_width)
+        with torch.no_grad():
+            frames = self.ctc_decoder.forward_train(feat)      # the head's logits [N, 32, 92], rows of a 128-wide buffer
+        paths, lengths, scores, self.last_att_scores = self.decoder.forward_beam(feat, self.encoder(feat), beam_width, ctc_frames=frames,
+                                                                                 ctc_weight=w)
+        return paths, lengths, scores
 
     def forward_lexicon(self, img, lexicon_beam=None):
         """img [N,3,32,128] -> (word_ids int32 [N, W], log_probs fp32 [N, W], paths int32 [N, W, max_seq_len], lengths int32 [N, W]), best

@@ -1270,9 +1270,10 @@ def nrtr_beam_state(B, beam_width, seq_len, start_idx, pad_idx, device):
     return seq, score, state, torch.full((B, W), -1, dtype=I32, device=device)
 
 
-def _nrtr_beam_step(who, logits, C, step, end_idx, pad_idx, seq, score, state, parent, final, node=None, trie=None, class_offset=1):
-    """The body of nrtr_beam_step (trie None) and nrtr_beam_step_trie: the checks under the caller's name `who`, the outputs of the
-    final step, the launch."""
+def _nrtr_beam_step(who, logits, C, step, end_idx, pad_idx, seq, score, state, parent, final, node=None, trie=None, class_offset=1,
+                    joint=None, weight=0.0):
+    """The body of nrtr_beam_step (trie None, joint None), nrtr_beam_step_trie and nrtr_beam_step_joint: the checks under the caller's
+    name `who`, the outputs of the final step, the launch."""
     if score.dim() != 2 or not 1 <= score.shape[1] <= NRTR_MAX_BEAM:
         raise ValueError(f"{who}: score must be [B, W] with W in 1..{NRTR_MAX_BEAM}, got {list(score.shape)}")
     B, W = score.shape
@@ -1296,7 +1297,11 @@ def _nrtr_beam_step(who, logits, C, step, end_idx, pad_idx, seq, score, state, p
         raise ValueError(f"{who}: class_offset must be 0 or 1, got {class_offset!r}")
     out = _beam_outputs(B, W, seq_len - 1, seq.device) if final else (None, None, None)
     args = (logits, logits.stride(0), B, W, int(C), int(step), int(end_idx), int(pad_idx), seq, seq_len, score, state, parent, *out)
-    if trie is None:
+    if joint is not None:
+        out += (torch.empty((B, W), dtype=F32, device=seq.device) if final else None,)
+        _call("ccd_nrtr_beam_step_joint", *args, joint.log_probs, joint.Tc, joint.Cc, int(class_offset), weight, joint.prefix, joint.att,
+              out[3])
+    elif trie is None:
         _call("ccd_nrtr_beam_step", *args)
     else:
         out += (torch.empty((B, W), dtype=I32, device=seq.device) if final else None,)
@@ -1327,6 +1332,59 @@ def nrtr_beam_step_trie(logits, C, step, end_idx, pad_idx, seq, score, state, pa
     if not isinstance(trie, CTCLexiconTrie):                         # (None included: it would select the plain step)
         raise TypeError(f"nrtr_beam_step_trie: trie must come from ctc_lexicon_trie, got {type(trie).__name__}")
     return _nrtr_beam_step("nrtr_beam_step_trie", logits, C, step, end_idx, pad_idx, seq, score, state, parent, final, node, trie, class_offset)
+
+
+NRTR_JOINT_MAX_STEPS = 64                                 # ccd_hip.h: CCD_NRTR_JOINT_MAX_STEPS
+
+
+class NRTRJointState:
+    """The CTC side of a joint CTC / attention beam (nrtr_joint_state): log_probs fp64 [B, Tc, Cc], the workspace every step reads;
+    prefix fp64 [B, W, 2, Tc], the prefix state of every slot; att fp64 [B, W], its attention score."""
+
+    def __init__(self, log_probs, prefix, att):
+        self.log_probs, self.prefix, self.att = log_probs, prefix, att
+        self.B, self.W, _, self.Tc = prefix.shape
+        self.Cc = log_probs.shape[2]
+
+
+def nrtr_joint_state(frames, beam_width, normalized=False):
+    """The CTC side of joint CTC / attention decoding in front of step 0 (kernels/nrtr_joint.h: ccd_nrtr_joint_begin): frames fp32
+    [B, Tc, Cc] of an auxiliary CTC head (any sample / step stride; blank = class 0), logits or - normalized=True - probabilities ->
+    an NRTRJointState handle: the fp64 frame log-probabilities, the root prefix state in every one of the W slots, and att = 0,
+    -inf, .. as nrtr_beam_state's score.  Tc in 1..64, Cc in 1..128."""
+    B, Tc, Cc = _frame_scores("nrtr_joint_state", frames, "frames")
+    W = _beam_width("nrtr_joint_state", beam_width, NRTR_MAX_BEAM)
+    if frames.dtype != F32:
+        raise ValueError(f"nrtr_joint_state: frames must be {F32}, got {frames.dtype}")
+    if not 1 <= Tc <= NRTR_JOINT_MAX_STEPS or not 1 <= Cc <= NRTR_MAX_CLASSES:
+        raise ValueError(f"nrtr_joint_state: expects frames [B, 1..{NRTR_JOINT_MAX_STEPS}, 1..{NRTR_MAX_CLASSES}], got {list(frames.shape)}")
+    dev = frames.device
+    log_probs = torch.empty((B, Tc, Cc), dtype=F64, device=dev)
+    prefix = torch.empty((B, W, 2, Tc), dtype=F64, device=dev)
+    att = torch.full((B, W), float("-inf"), dtype=F64, device=dev)
+    att[:, 0] = 0.0
+    _call("ccd_nrtr_joint_begin", frames, frames.stride(0), frames.stride(1), B, Tc, Cc, 1 if normalized else 0, W, log_probs, prefix)
+    return NRTRJointState(log_probs, prefix, att)
+
+
+def nrtr_beam_step_joint(logits, C, step, end_idx, pad_idx, seq, score, state, parent, joint, weight, class_offset=1, final=False):
+    """nrtr_beam_step with every candidate rescored by the CTC prefix probability of an auxiliary CTC head (kernels/nrtr_joint.h), in
+    place: joint is nrtr_joint_state's handle (its prefix states and attention scores are updated like score and state), weight w in
+    [0, 1], decoder class c is CTC class c + class_offset (1: the CTC head's classes are the decoder's + 1 behind the blank).  score
+    holds S = (1 - w) attention + w CTC; at weight 0 the step is nrtr_beam_step's, bit for bit.  final=True returns (paths, lengths,
+    hyp_scores, att_scores): nrtr_beam_step's three with the joint scores, and att_scores fp32 [B, W], the attention scores alone."""
+    who = "nrtr_beam_step_joint"
+    if not isinstance(joint, NRTRJointState):
+        raise TypeError(f"{who}: joint must come from nrtr_joint_state, got {type(joint).__name__}")
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0.0 <= float(weight) <= 1.0:      # (a NaN fails both)
+        raise ValueError(f"{who}: weight must lie in [0, 1], got {weight!r}")
+    if isinstance(class_offset, bool) or class_offset not in (0, 1):
+        raise ValueError(f"{who}: class_offset must be 0 or 1, got {class_offset!r}")
+    if tuple(score.shape) != (joint.B, joint.W) or joint.att.device != score.device:
+        raise ValueError(f"{who}: joint was made for [{joint.B}, {joint.W}] slots on {joint.att.device}, score is {list(score.shape)} on "
+                         f"{score.device}")
+    return _nrtr_beam_step(who, logits, C, step, end_idx, pad_idx, seq, score, state, parent, final, joint=joint, weight=float(weight),
+                           class_offset=class_offset)
 
 
 def nrtr_beam_reorder(cache, parent, positions, step):

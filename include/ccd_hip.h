@@ -667,6 +667,41 @@ int ccd_nrtr_beam_reorder(ccd_bf16* cache, const int* parent, int layers, int ba
 int ccd_nrtr_beam_step_trie(const float* logits, long ldl, int batch, int beam, int classes, int step, int end_idx, int pad_idx,
                             int64_t* seq, int seq_len, double* score, int* state, int* parent, int* paths, int* lengths,
                             float* hyp_scores, const int* nodes, int n_nodes, int class_offset, int* node, int* word_ids, void* stream);
+/* Joint CTC / attention decoding (ABI 29; kernels/nrtr_joint.h, restated in numpy in tests/nrtr_joint_np.py): ccd_nrtr_beam_step whose
+ * candidates are rescored with the CTC prefix probability an auxiliary CTC head gives them.  Everything ccd_nrtr_beam_step takes means
+ * what it means there; `score` holds the joint score S.
+ * ccd_nrtr_joint_begin, once per batch, one wavefront per sample:
+ *   frames     fp32, frame t of sample b at frames + b * sample_stride + t * step_stride, ctc_classes dense values: logits, or -
+ *              normalized = 1 - probabilities.  Class 0 is the blank.
+ *   log_probs  fp64 [batch, ctc_steps, ctc_classes], written: the log-probabilities of every frame, in fp64 with the class sum in
+ *              ascending order (-inf for a -inf logit or a probability <= 0).  A workspace the caller owns and hands to every step.
+ *   prefix     fp64 [batch, beam, 2, ctc_steps], written: the prefix state of every slot, rn = prefix[b, r, 0], rb = prefix[b, r, 1] - the
+ *              log-probability that the frames 0..t spell exactly the slot's prefix and end in a non-blank / in a blank.  Here the
+ *              root's: rn = -inf, rb[t] = log_probs[b, 0, 0] + .. + log_probs[b, t, 0], added in that order.
+ * ccd_nrtr_beam_step_joint, one wavefront per sample, in place:
+ *   att        fp64 [batch, beam], in and out like score: the attention score A of every slot, ccd_nrtr_beam_step's score.  Before step
+ *              0 as score: 0, -inf, ..
+ *   weight     w in [0, 1].  Decoder class c != end_idx is CTC class k = c + class_offset (class_offset in {0, 1}).
+ *   A live slot r with prefix g gives (r, c), c != end_idx: S = (1 - w) (A_r + la[c]) + w psi(g.k), and (r, end_idx): S = (1 - w) (A_r +
+ *              la[end_idx]) + w full(g); la = log_softmax(logits[r]) as in ccd_nrtr_beam_step, psi the log-probability that the CTC
+ *              output starts with g.k, full that it is g (the recursion: kernels/nrtr_joint.h).  A candidate exists iff its attention
+ *              part is finite and (w == 0 or its CTC part > -inf); a class with k >= ctc_classes has no CTC part.  At w == 0 S is the
+ *              attention part: the bits of ccd_nrtr_beam_step.  A finished slot gives (r, end_idx) with S and A unchanged.  Selection
+ *              and ties are ccd_nrtr_beam_step's, over S.  A selected extension takes the extended prefix state, a finished or carried
+ *              slot keeps its parent's, an unused slot holds -inf.
+ *   att_scores fp32 [batch, beam], written with paths / lengths / hyp_scores (all four or none): A rounded once, -inf for an unused slot;
+ *              hyp_scores is S.
+ * No atomics: the same input gives the same bits.  batch == 0 is a no-op.  CCD_EINVAL: a missing pointer, a negative size, stride or
+ * step, the four outputs given in part; CCD_ESHAPE: everything ccd_nrtr_beam_step refuses, ctc_steps outside 1..CCD_NRTR_JOINT_MAX_STEPS,
+ * ctc_classes outside 1..128, class_offset outside 0..1, weight outside [0, 1] or not finite, normalized not 0 or 1.  Nothing is
+ * launched on an error. */
+#define CCD_NRTR_JOINT_MAX_STEPS 64
+int ccd_nrtr_joint_begin(const float* frames, long sample_stride, long step_stride, int batch, int ctc_steps, int ctc_classes, int normalized,
+                         int beam, double* log_probs, double* prefix, void* stream);
+int ccd_nrtr_beam_step_joint(const float* logits, long ldl, int batch, int beam, int classes, int step, int end_idx, int pad_idx,
+                             int64_t* seq, int seq_len, double* score, int* state, int* parent, int* paths, int* lengths,
+                             float* hyp_scores, const double* log_probs, int ctc_steps, int ctc_classes, int class_offset, double weight,
+                             double* prefix, double* att, float* att_scores, void* stream);
 /* Scoring GIVEN words with the NRTR decoder (ABI 28; kernels/nrtr_score.h, the second kernel restated in numpy in
  * tests/nrtr_score_np.py).  Inference only: no dropout, no mask, no backward.
  *

@@ -4,6 +4,7 @@
     python tools/nrtr_beam_bench.py [--iters 30] [--rounds 5] [--out profiles/nrtr_beam.json]
     python tools/nrtr_beam_bench.py --cases trie --out profiles/nrtr_beam_trie.json
     python tools/nrtr_beam_bench.py --cases score --out profiles/nrtr_score.json
+    python tools/nrtr_beam_bench.py --cases joint --out profiles/nrtr_beam_joint.json
 
 The cases, each in a process of its own under its own time limit; the next one starts only if the one before ended well:
   kernels  ccd_nrtr_beam_step and ccd_nrtr_beam_reorder per launch at B = 512, T = 25, C = 92 (logits rows 128 wide), D = 512,
@@ -26,6 +27,11 @@ The cases, each in a process of its own under its own time limit; the next one s
            B = 512 x 50 (R = 25 600) alone, with and without moments; ccd_nrtr_word_score at R = 25 600, T = 26, C = 92, per launch and
            per row; then evaluation images/s at B = 512, vit_small: forward_words with 50 words per image against forward_lexicon at
            lexicon_beam 16 over the same 50 words, rounds alternating.
+  joint    (not part of a default run) joint CTC / attention decoding (kernels/nrtr_joint.h): ccd_nrtr_beam_step_joint per launch at
+           widths 4, 8, 16 with Tc = 32 frames of Cc = 92 classes and weight 0.3, next to ccd_nrtr_beam_step in the same process on the
+           same logits, both on a state eight steps into their own decode (with how many slots are still live); ccd_nrtr_joint_begin
+           per launch; then evaluation images/s at B = 512, vit_small with an auxiliary CTC head: forward_beam with joint_ctc_weight
+           0.3 against the plain forward_beam at widths 4, 8 and 16, rounds alternating.
 Warm-up first, HIP events around every timed call, a figure is the median of the round medians with the lowest and highest
 round.  No threshold is set; the file records what was measured.  `--case NAME` runs one case and prints its JSON line."""
 import argparse
@@ -40,7 +46,7 @@ sys.path.insert(0, ROOT)
 
 B, T, C, D, L = 512, 25, 92, 512, 6
 WIDTHS = (1, 4, 8, 16)
-LIMITS = {"kernels": 240, "eval": 420, "rescore": 180, "trie": 600, "score": 420}      # seconds per case
+LIMITS = {"kernels": 240, "eval": 420, "rescore": 180, "trie": 600, "score": 420, "joint": 420}      # seconds per case
 TRIE_WIDTHS, TRIE_LEXICONS = (4, 8, 16), (1000, 10000, 90000)
 
 
@@ -361,7 +367,91 @@ def case_score(a):
     return out
 
 
-CASES = {"kernels": case_kernels, "eval": case_eval, "rescore": case_rescore, "trie": case_trie, "score": case_score}
+JOINT_WIDTHS, JOINT_TC, JOINT_WEIGHT = (4, 8, 16), 32, 0.3
+
+
+def case_joint(a):
+    import torch
+    from ccd_amd import finetune as ft, ops
+    dev = torch.device("cuda")
+    out = {"shape": {"B": B, "T": T, "C": C, "Tc": JOINT_TC, "Cc": C, "weight": JOINT_WEIGHT}}
+    g = torch.Generator().manual_seed(5)
+    frames = torch.randn(B, JOINT_TC, 128, generator=g) * 2.0                     # rows of a 128-wide buffer, as the CTC head's logits
+    frames[:, :, 0] += 5.0
+    frames = frames.to(dev)[:, :, :C]
+    for W in JOINT_WIDTHS:
+        g = torch.Generator().manual_seed(W)
+        logits = torch.randn(B * W, 128, generator=g) * 2.0
+        logits.scatter_add_(1, torch.randint(0, C, (B * W, 1), generator=g), torch.full((B * W, 1), 6.0))
+        logits = logits.to(dev)
+        sides = {}
+        for name in ("plain", "joint"):
+            seq, score, state, parent = ops.nrtr_beam_state(B, W, T + 1, C - 1, C, dev)
+            joint = ops.nrtr_joint_state(frames, W) if name == "joint" else None
+
+            def launch(s, rows, seq=seq, score=score, state=state, parent=parent, joint=joint):
+                if joint is None:
+                    ops.nrtr_beam_step(rows, C, s, C - 1, C, seq, score, state, parent)
+                else:
+                    ops.nrtr_beam_step_joint(rows, C, s, C - 1, C, seq, score, state, parent, joint, JOINT_WEIGHT)
+
+            for s in range(8):                                                    # eight steps into its own decode
+                launch(s, logits.roll(s, 0))
+            live = int((state == ops.NRTR_LIVE).sum())
+            used = int((state != ops.NRTR_UNUSED).sum())
+            tensors = (seq, score, state) + ((joint.prefix, joint.att) if joint is not None else ())
+            saved = [t.clone() for t in tensors]
+
+            def restore(tensors=tensors, saved=saved):
+                for t, keep in zip(tensors, saved):
+                    t.copy_(keep)
+
+            def step(restore=restore, launch=launch):
+                restore()
+                launch(8, logits)
+
+            sides[name] = {"step": step, "restore": restore, "with_copy": [], "copies": [], "live": live, "used": used}
+        begin = []
+        for _ in range(a.rounds):                                                 # rounds alternate between the sides
+            for side in sides.values():
+                side["with_copy"].append(event_ms(side["step"], a.iters))
+                side["copies"].append(event_ms(side["restore"], a.iters))
+            begin.append(event_ms(lambda: ops.nrtr_joint_state(frames, W), a.iters))
+        entry = {}
+        for name, side in sides.items():
+            e = {"step_with_state_restore": summary(side["with_copy"]), "state_restore_alone": summary(side["copies"])}
+            e["step_kernel_ms"] = round(e["step_with_state_restore"]["median_ms"] - e["state_restore_alone"]["median_ms"], 4)
+            e["slots_live_at_the_timed_step"] = f"{side['live']} of {B * W} ({side['used']} in use)"
+            entry["ccd_nrtr_beam_step" if name == "plain" else "ccd_nrtr_beam_step_joint"] = e
+        entry["nrtr_joint_state (ccd_nrtr_joint_begin and three allocations)"] = summary(begin)
+        out[f"w{W}"] = entry
+    # evaluation images/s: the joint beam against the plain beam of the same width, on a model with the auxiliary head
+    torch.manual_seed(0)
+    cfg = ft.FinetuneConfig()
+    cfg.decoder_aux_ctc_weight = 0.3
+    model = ft.build_model(cfg, dev, dropout=0.0).eval()
+    with torch.no_grad():
+        model.arena.w("ctc_decoder.fc.bias")[0] += 5.0                            # (an untrained head is uniform: nothing would finish)
+    model.arena.refresh_mirrors()
+    img = torch.randn(B, 3, 32, 128, generator=torch.Generator().manual_seed(4)).to(dev)
+    sides = {(kind, width): [] for width in JOINT_WIDTHS for kind in ("beam_width", "joint_beam_width")}
+    iters = max(3, a.iters // 6)
+    with torch.no_grad():
+        for _ in range(a.rounds):
+            for kind, width in sides:
+                fn = (lambda: model.forward_beam(img, width)) if kind == "beam_width" else \
+                     (lambda: model.forward_beam(img, width, joint_ctc_weight=JOINT_WEIGHT))
+                sides[(kind, width)].append(event_ms(fn, iters))
+    ev = {"batch": B, "arch": "vit_small", "joint_ctc_weight": JOINT_WEIGHT, "decode_graph": os.environ.get("CCD_DECODE_GRAPH", "1") != "0"}
+    for (kind, width), rounds in sides.items():
+        name = f"{kind}_{width}"
+        ev[name] = summary(rounds)
+        ev[name + "_images_per_s"] = round(B / (ev[name]["median_ms"] * 1e-3))
+    out["eval"] = ev
+    return out
+
+
+CASES = {"joint": case_joint, "kernels": case_kernels, "eval": case_eval, "rescore": case_rescore, "trie": case_trie, "score": case_score}
 
 
 def main():

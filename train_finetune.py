@@ -180,6 +180,10 @@ def main(config):
         if iteration % config.training_show_iters == 0:
             avg = (running / nrun).item()
             logging.info(f"iteration:{iteration}--> train loss:{avg}")
+            parts = model.module.last_losses                # the hybrid CTC / attention model: the last iteration's two parts
+            if parts is not None:
+                logging.info(f"iteration:{iteration}--> attention loss:{parts['tf'].item()} ctc loss:{parts['ctc'].item()} "
+                             f"(aux_ctc_weight {model.module.aux_ctc_weight})")
             if config.writer is not None:
                 config.writer.add_scalar("metric/train_loss", avg, iteration)
                 config.writer.add_scalar("metric/lr", optimizer.param_groups[0]["lr"], iteration)
