@@ -25,10 +25,13 @@ class AttnConvertor(BaseConvertor):
     that walks the lexicon's prefix tree (DINO_Finetune.forward_lexicon); a finished hypothesis is a word of the lexicon and its score
     the exact log p(word <EOS> | image).  Either of the two alone is refused: exhaustive scoring of ONE lexicon for the whole batch
     exists for the CTC head only.  Words GIVEN per image - a 50-word lexicon for every image, an n-best to rescore, a transcription -
-    need no configuration: words2rows / scores2words / scores2chars below, with DINO_Finetune.forward_score / forward_words."""
+    need no configuration: words2rows / scores2words / scores2chars below, with DINO_Finetune.forward_score / forward_words.
+    `twopass_beam` in 1..16 (with `twopass_ctc_weight` in [0, 1], default 0.5 - WeNet's, untuned here) asks for two-pass decoding where
+    words are scored: the auxiliary CTC head's beam proposes, the decoder rescores (DINO_Finetune.forward_twopass); it excludes
+    beam_width > 0 and a lexicon.  The two values are kept as attributes."""
 
     def __init__(self, dict_type="DICT90", dict_file=None, dict_list=None, with_unknown=True, max_seq_len=40, lower=False,
-                 start_end_same=True, beam_width=0, lexicon=None, lm=None, lexicon_beam=0, **_ignored):
+                 start_end_same=True, beam_width=0, lexicon=None, lm=None, lexicon_beam=0, twopass_beam=0, twopass_ctc_weight=None, **_ignored):
         if lm is not None:
             raise NotImplementedError("AttnConvertor: language-model fusion is for the CTC head only - the NRTR decoder conditions every "
                                       "character on the ones before it already, and its beam takes no additive table term (use "
@@ -43,6 +46,10 @@ class AttnConvertor(BaseConvertor):
         self.lower, self.start_end_same = bool(lower), bool(start_end_same)
         from ..ops import NRTR_MAX_BEAM
         self.beam_width = checked_beam_width(beam_width, NRTR_MAX_BEAM)
+        self.twopass_beam, self.twopass_ctc_weight = self._checked_twopass(twopass_beam, twopass_ctc_weight, NRTR_MAX_BEAM)
+        if self.twopass_beam and (self.beam_width > 0 or lexicon is not None):
+            raise ValueError(f"twopass_beam = {self.twopass_beam} excludes beam_width > 0 and lexicon / lexicon_beam: two-pass decoding "
+                             "takes its proposals from the CTC prefix beam and ranks them itself")
         # special classes behind the alphabet, in the reference's order
         self.idx2char = list(alphabet)
         self.unknown_idx = self._append("<UKN>") if self.with_unknown else None
@@ -53,6 +60,22 @@ class AttnConvertor(BaseConvertor):
         self.lexicon, self.lexicon_words, self.lexicon_stats, self.lexicon_trie, self.lexicon_beam = None, None, None, None, 0
         if lexicon is not None:
             self.set_lexicon(lexicon, beam=lexicon_beam)
+
+    TWOPASS_DEFAULT_WEIGHT = 0.5       # WeNet's default for attention rescoring; untuned here (no trained hybrid model exists)
+
+    @staticmethod
+    def _checked_twopass(beam, weight, limit):
+        """(twopass_beam, 0: off; twopass_ctc_weight, None without a beam, absent: TWOPASS_DEFAULT_WEIGHT)."""
+        beam = 0 if beam is None else beam
+        if isinstance(beam, bool) or not isinstance(beam, (int, np.integer)) or not 0 <= int(beam) <= limit:
+            raise ValueError(f"twopass_beam must lie in 1..{limit} (the width of the CTC beam that proposes; 0 or absent: off), got {beam!r}")
+        if weight is not None and (isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0.0 <= float(weight) <= 1.0):
+            raise ValueError(f"twopass_ctc_weight must lie in [0, 1], got {weight!r}")
+        if not beam:
+            if weight is not None:
+                raise ValueError(f"twopass_ctc_weight = {weight!r} needs twopass_beam in 1..{limit}: it weighs the scores of its proposals")
+            return 0, None
+        return int(beam), AttnConvertor.TWOPASS_DEFAULT_WEIGHT if weight is None else float(weight)
 
     @staticmethod
     def _checked_lexicon_beam(beam):
@@ -80,6 +103,9 @@ class AttnConvertor(BaseConvertor):
         if self.beam_width > 0:
             raise ValueError(f"a lexicon and beam_width = {self.beam_width} exclude each other: the lexicon's beam is lexicon_beam, set "
                              "beam_width to 0")
+        if self.twopass_beam:
+            raise ValueError(f"a lexicon and twopass_beam = {self.twopass_beam} exclude each other: two-pass decoding ranks the CTC beam's "
+                             "proposals (a lexicon's proposals go through DINO_Finetune.forward_twopass(proposals=))")
         words, kept, stats = self._lexicon_rows(strings_or_path, min(self.max_seq_len - 1, ops.CTC_MAX_LABELS), 1)
         self.lexicon = ops.ctc_lexicon(torch.from_numpy(words))
         self.lexicon_words, self.lexicon_beam = kept, width

@@ -41,6 +41,7 @@
 #include "kernels/decoder.h"
 #include "kernels/decoder_xattn.h"
 #include "kernels/nrtr_score.h"
+#include "kernels/nrtr_twopass.h"
 
 #define CCD_CHECK(cond, code) \
     do {                      \
@@ -344,7 +345,7 @@ static int ccd_seg_prepare(int images, long pixels, int* cm, int* status, int* c
 
 extern "C" {
 
-int ccd_abi_version(void) { return 29; }   // 29: ccd_nrtr_joint_begin, ccd_nrtr_beam_step_joint (joint CTC / attention decoding: the NRTR beam rescored with CTC prefix probabilities); 28: ccd_xattn_rows_fwd, ccd_xattn_rows_chunk, ccd_nrtr_word_score (scoring given words with the NRTR decoder: per-image lexicons, character positions); 27: ccd_nrtr_beam_step_trie (lexicon-constrained beam search over the NRTR decoder); 26: ccd_ctc_beam_search_trie (trie beam search over a lexicon in the CTC beam search); 25: ccd_ctc_align (CTC forced alignment); 24: ccd_ctc_beam_search_lm (character n-gram language-model fusion in the CTC beam search); 23: ccd_ctc_lexicon_score, ccd_ctc_lexicon_best (lexicon-constrained decoding of the CTC head); 22: ccd_nrtr_beam_step, ccd_nrtr_beam_reorder (beam search over the NRTR decoder); 21: ccd_ctc_beam_search, ccd_text_score_paths (CTC prefix beam search, n-best word scores); 20: ccd_ctc_pool_fwd / _bwd, ccd_ctc_loss_fwd / _bwd, ccd_ctc_greedy, ccd_text_score_ctc (the CTC recognition head); 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
+int ccd_abi_version(void) { return 30; }   // 30: ccd_nrtr_twopass_rows, ccd_nrtr_twopass_select (two-pass decoding: CTC beam proposals rescored by the NRTR decoder); 29: ccd_nrtr_joint_begin, ccd_nrtr_beam_step_joint (joint CTC / attention decoding: the NRTR beam rescored with CTC prefix probabilities); 28: ccd_xattn_rows_fwd, ccd_xattn_rows_chunk, ccd_nrtr_word_score (scoring given words with the NRTR decoder: per-image lexicons, character positions); 27: ccd_nrtr_beam_step_trie (lexicon-constrained beam search over the NRTR decoder); 26: ccd_ctc_beam_search_trie (trie beam search over a lexicon in the CTC beam search); 25: ccd_ctc_align (CTC forced alignment); 24: ccd_ctc_beam_search_lm (character n-gram language-model fusion in the CTC beam search); 23: ccd_ctc_lexicon_score, ccd_ctc_lexicon_best (lexicon-constrained decoding of the CTC head); 22: ccd_nrtr_beam_step, ccd_nrtr_beam_reorder (beam search over the NRTR decoder); 21: ccd_ctc_beam_search, ccd_text_score_paths (CTC prefix beam search, n-best word scores); 20: ccd_ctc_pool_fwd / _bwd, ccd_ctc_loss_fwd / _bwd, ccd_ctc_greedy, ccd_text_score_ctc (the CTC recognition head); 19: ccd_sinkhorn_colpass / _rescale / _finish / _rowpass / _assign, ccd_sinkhorn_ws_floats (DINOLoss.sinkhorn_knopp_teacher); 17: ccd_seg_confusion, ccd_seg_confusion_logits, ccd_seg_scores (Dino/metric/eval_IOU.py); 16: ccd_seg_moments, ccd_sgd_momentum, ccd_lars (optimizer: sgd / lars); 15: ccd_attention_probs (get_last_selfattention); 14: ccd_ssim_fwd / _reduce / _bwd, ccd_psnr_fwd (Dino/metric/eval_superpixel.py); 13: ccd_dbscan_label, ccd_region_boxes, ccd_idmap_to_planes_u8, ccd_boxes_to_planes_u8 (Dino/utils/DBSCAN.py clusterers); 12: ccd_mlp_bwd_fused (gelu'(u) product + fc1 data gradient + LayerNorm-2 backward in one launch), ccd_proj_mlp_fused_gact (the forward block half also stores gelu(u)); 11: ccd_gemm_nt_lnbwd_tap_g16 (a segmentation tap's LayerNorm backward inside the qkv data-gradient product's epilogue); 10: ccd_head_loss_fwd / _bwd (last layer + distillation loss, logits never written), ccd_*_g16 (bf16 residual-gradient stream); 9: ccd_cls_tail_fwd / _bwd_reduce / _bwd_apply (BatchNorm + ReLU + classifier conv of the segmentation head fused); 8: ccd_proj_mlp_fused (proj + residual + LayerNorm-2 in front of the fused MLP), ccd_matvec_bf16; 7: ccd_gemm_tn_pair_ws (split-K workspace instead of fp32 atomics); 6: device-side momentum / DropPath seed (HIP graph of the training step); 5: ccd_mlp_fused can store gelu(u); 4: ccd_attention_bwd emits the qkv-bias gradient; 3: ccd_policy_set / _get, ccd_mlp_fused; 2: finetune-path entry points
 const char* ccd_build_info(void) { return "ccd_hip gfx950 bf16-mfma abi16"; }
 int ccd_policy_set(const char* key, int value) {
     CCD_CHECK(key, CCD_EINVAL);
@@ -2331,6 +2332,48 @@ int ccd_nrtr_word_score(const float* logits, long ldl, int classes, const int64_
     CCD_LAUNCH(ccd::nrtr_word_score_kernel, dim3((unsigned)((rows + ccd::NWS_WAVES - 1) / ccd::NWS_WAVES)), dim3(64 * ccd::NWS_WAVES), 0,
                stream, logits, ldl, classes, reinterpret_cast<const long long*>(seq), rows, seq_len, end_idx, pad_idx, moments, heads,
                char_logp, score, length, char_pos);
+    return ccd_rt_last_error();
+}
+
+// ------------------------------------------------------------------------------- two-pass decoding (nrtr_twopass.h)
+static int ccd_twopass_paths(const int* paths, long sample_stride, long slot_stride, const int* lengths, int batch, int beam, int path_len,
+                             int class_offset, ccd::NrtrTwopassPaths* p) {
+    CCD_CHECK(batch >= 0 && sample_stride >= 0 && slot_stride >= 0, CCD_EINVAL);
+    CCD_CHECK(beam >= 1 && beam <= ccd::NRTR_MAX_BEAM && path_len >= 1 && path_len <= ccd::NTP_MAX_PATH && class_offset >= 0 &&
+              class_offset <= 1, CCD_ESHAPE);
+    *p = ccd::NrtrTwopassPaths{paths, sample_stride, slot_stride, lengths, batch, beam, path_len, class_offset};
+    return CCD_OK;
+}
+int ccd_nrtr_twopass_rows(const int* paths, long sample_stride, long slot_stride, const int* lengths, int batch, int beam, int path_len,
+                          int class_offset, int classes, int start_idx, int end_idx, int pad_idx, int64_t* seq, int seq_len,
+                          int64_t* targets, int max_labels, int* subset, void* stream) {
+    ccd::NrtrTwopassPaths p;
+    const int rc = ccd_twopass_paths(paths, sample_stride, slot_stride, lengths, batch, beam, path_len, class_offset, &p);
+    if (rc != CCD_OK) return rc;
+    const int lowest = seq ? 0 : -1;                                       // without seq: -1 is "no such class"
+    CCD_CHECK(classes >= 1 && classes <= ccd::NRTR_MAX_C && seq_len >= 2 && seq_len <= ccd::NRTR_MAX_LEN && max_labels >= 1 &&
+              max_labels <= ccd::CTC_MAX_L && start_idx >= lowest && start_idx < 65536 && end_idx >= lowest && end_idx < 65536 &&
+              pad_idx >= lowest && pad_idx < 65536, CCD_ESHAPE);
+    if (batch == 0) return CCD_OK;
+    CCD_CHECK(paths && lengths && targets && subset, CCD_EINVAL);
+    CCD_LAUNCH(ccd::nrtr_twopass_rows_kernel, dim3((unsigned)((batch + ccd::NTP_WAVES - 1) / ccd::NTP_WAVES)), dim3(64 * ccd::NTP_WAVES), 0,
+               stream, p, classes, start_idx, end_idx, pad_idx, reinterpret_cast<long long*>(seq), seq_len,
+               reinterpret_cast<long long*>(targets), max_labels, subset);
+    return ccd_rt_last_error();
+}
+int ccd_nrtr_twopass_select(const int* paths, long sample_stride, long slot_stride, const int* lengths, int batch, int beam, int path_len,
+                            int class_offset, const float* att, const float* ctc, const int* subset, double weight, int max_seq_len,
+                            int* out_paths, int* out_lengths, float* scores, float* att_scores, float* ctc_scores, int* source,
+                            void* stream) {
+    ccd::NrtrTwopassPaths p;
+    const int rc = ccd_twopass_paths(paths, sample_stride, slot_stride, lengths, batch, beam, path_len, class_offset, &p);
+    if (rc != CCD_OK) return rc;
+    CCD_CHECK(max_seq_len >= 1 && max_seq_len <= ccd::NRTR_MAX_LEN && weight >= 0.0 && weight <= 1.0, CCD_ESHAPE);      // (a NaN weight fails both)
+    if (batch == 0) return CCD_OK;
+    CCD_CHECK(paths && lengths && att && ctc && subset && out_paths && out_lengths && scores && att_scores && ctc_scores && source,
+              CCD_EINVAL);
+    CCD_LAUNCH(ccd::nrtr_twopass_select_kernel, dim3((unsigned)((batch + ccd::NTP_WAVES - 1) / ccd::NTP_WAVES)), dim3(64 * ccd::NTP_WAVES),
+               0, stream, p, att, ctc, subset, weight, max_seq_len, out_paths, out_lengths, scores, att_scores, ctc_scores, source);
     return ccd_rt_last_error();
 }
 

@@ -237,6 +237,24 @@ class NRTRDecoder(ArenaModule, _DropoutSeeds):
         self._ready()
         return fe.score_words(self, out_enc.to(torch.bfloat16), seq.to(out_enc.device, non_blocking=True), row_ptr)
 
+    def forward_twopass(self, feat, out_enc, frames, paths, lengths, weight, normalized=False):
+        """Two-pass decoding (fe.twopass_decode; kernels/nrtr_twopass.h): frames fp32 [N, Tc, Cc] of an auxiliary CTC head (class c + 1
+        is the decoder's class c), paths int32 [N, W, Tp] / lengths int32 [N, W] the W words per image a CTC decoder proposes from
+        them, in CTC classes, weight w in [0, 1] -> (paths int32 [N, W, max_seq_len] by rank, -1-padded; lengths int32 [N, W]; scores
+        fp32 [N, W] = (1 - w) log p_att + w log p_ctc, both parts exact; att_scores, ctc_scores fp32 [N, W]; source int32 [N, W], the
+        proposal slot of every rank).  Eager launches, no HIP graph, no host synchronisation."""
+        from ..ops import NRTR_MAX_BEAM
+        if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0.0 <= float(weight) <= 1.0:
+            raise ValueError(f"forward_twopass: weight must lie in [0, 1], got {weight!r}")
+        N = out_enc.shape[0]
+        if frames.dim() != 3 or frames.shape[0] != N or frames.dtype != torch.float32:
+            raise ValueError(f"forward_twopass: frames must be float32 [{N}, Tc, Cc], got {frames.dtype} {list(frames.shape)}")
+        if paths.dim() != 3 or paths.shape[0] != N or not 1 <= paths.shape[1] <= NRTR_MAX_BEAM or tuple(lengths.shape) != tuple(paths.shape[:2]):
+            raise ValueError(f"forward_twopass: proposals must be paths [{N}, 1..{NRTR_MAX_BEAM}, Tp] with lengths [{N}, W], got "
+                             f"{list(paths.shape)} and {list(lengths.shape)}")
+        self._ready()
+        return fe.twopass_decode(self, out_enc.to(torch.bfloat16), frames, paths, lengths, float(weight), normalized=normalized)
+
     def forward_test_speed(self, feat, out_enc, img_metas=None):
         self._ready()
         return fe.greedy_decode(self, out_enc.to(torch.bfloat16), stop_on_eos_of_first=True)

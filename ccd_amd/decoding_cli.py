@@ -1,11 +1,12 @@
-"""The decoding flags of test.py and train_finetune.py, declared once: --beam_width, --lexicon, --lexicon_beam, the --lm group and
---joint_ctc_weight, their copy into `config.decoder_*`, and the log lines that say which lexicon and language model the built model
+"""The decoding flags of test.py and train_finetune.py, declared once: --beam_width, --lexicon, --lexicon_beam, the --lm group,
+--joint_ctc_weight and --twopass_beam / --twopass_ctc_weight, their copy into `config.decoder_*`, and the log lines that say which lexicon and language model the built model
 decodes with."""
 from __future__ import annotations
 
 import logging
 
-DECODING_FLAGS = ("beam_width", "lexicon", "lexicon_beam", "lm", "lm_weight", "lm_bonus", "joint_ctc_weight")      # flag `--x` sets `config.decoder_x`
+DECODING_FLAGS = ("beam_width", "lexicon", "lexicon_beam", "lm", "lm_weight", "lm_bonus", "joint_ctc_weight", "twopass_beam",
+                  "twopass_ctc_weight")      # flag `--x` sets `config.decoder_x`
 
 
 def add_decoding_flags(parser, training=False):
@@ -31,6 +32,12 @@ def add_decoding_flags(parser, training=False):
                         help="NRTR head with an auxiliary CTC head (decoder.aux_ctc_weight): joint CTC / attention decoding - the beam over the "
                              "decoder is rescored with the CTC prefix probability of every candidate at this weight, 0..1; needs --beam_width "
                              "1..16, excludes a lexicon")
+    parser.add_argument("--twopass_beam", type=int, default=None,
+                        help="NRTR head with an auxiliary CTC head (decoder.aux_ctc_weight): two-pass decoding - the CTC prefix beam of this "
+                             "width, 1..16, proposes words, the NRTR decoder scores all of them in one teacher-forced pass and the two exact "
+                             "scores rank them again; excludes --beam_width, a lexicon and --joint_ctc_weight")
+    parser.add_argument("--twopass_ctc_weight", type=float, default=None,
+                        help="with --twopass_beam: the weight of the CTC score in (1 - w) attention + w CTC, 0..1 (default 0.5, untuned)")
 
 
 def apply_decoding_flags(args, config):
@@ -41,6 +48,9 @@ def apply_decoding_flags(args, config):
 
 
 def log_decoding(convertor, config):
+    if getattr(convertor, "twopass_beam", 0):
+        logging.info(f"two-pass decoding: the CTC beam of width {convertor.twopass_beam} proposes, the NRTR decoder rescores at "
+                     f"twopass_ctc_weight {convertor.twopass_ctc_weight}")
     if getattr(convertor, "lexicon_stats", None):
         logging.info(f"lexicon {config.decoder_lexicon} (lexicon_beam {getattr(convertor, 'lexicon_beam', 0)}): {convertor.lexicon_stats}")
     if getattr(convertor, "lm_stats", None):

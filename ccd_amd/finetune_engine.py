@@ -456,7 +456,7 @@ def beam_decode(module, out_enc, beam_width, trie=None, ctc_frames=None, ctc_wei
 
 
 @torch.no_grad()
-def score_words(module, out_enc, seq, row_ptr):
+def score_words(module, out_enc, seq, row_ptr, want_moments=True):
     """Teacher-forced scores of GIVEN words: out_enc bf16 [B, 256, D], seq int64 [R, max_seq_len + 1] = <BOS> c1 .. cn <EOS> <PAD> ..
     (AttnConvertor.words2rows; the layout of beam_decode's sequences), row_ptr an ops.csr_rows handle (or B + 1 host integers): the
     rows row_ptr[b] .. row_ptr[b + 1] - 1 are words asked of image b -> a dict of device tensors: score fp32 [R] = log p(word <EOS> |
@@ -466,7 +466,8 @@ def score_words(module, out_enc, seq, row_ptr):
     classifier does not have, is an infeasible row: -inf, -1, zeros (ops.nrtr_word_score).
     The encoder keys and values are computed once for the B images and never replicated: the decoder layers of `decoder_states` run
     over the R rows - the self-attention with rows as samples, the encoder-decoder attention through ops.xattn_rows_fwd, which maps
-    every row onto its image's keys and values.  Dropout 0, nothing saved, no host synchronisation."""
+    every row onto its image's keys and values.  Dropout 0, nothing saved, no host synchronisation.
+    want_moments=False: the last layer writes no attention moments and char_pos is None (twopass_decode asks for scores only)."""
     arena, pre, spec, packed = module.arena, module.arena_prefix, module.dec_spec, module.packed
     D, H, L, C = spec.D, spec.H, spec.L, spec.C
     T = spec.max_seq_len + 1
@@ -479,8 +480,8 @@ def score_words(module, out_enc, seq, row_ptr):
     if R == 0:                                                                                   # no words: empty outputs, no launch
         dev = out_enc.device
         return {"score": torch.empty(0, dtype=F32, device=dev), "length": torch.empty(0, dtype=torch.int32, device=dev),
-                "char_logp": torch.empty((0, T - 1), dtype=F32, device=dev), "char_pos": torch.empty((0, T - 1, 4), dtype=F32, device=dev),
-                "row_ptr": rows.on(dev)}
+                "char_logp": torch.empty((0, T - 1), dtype=F32, device=dev),
+                "char_pos": torch.empty((0, T - 1, 4), dtype=F32, device=dev) if want_moments else None, "row_ptr": rows.on(dev)}
     scale = 64 ** -0.5
     packed.refresh(arena, pre, spec)
     kv = encoder_kv(arena, pre, spec, out_enc.reshape(-1, D))
@@ -496,7 +497,7 @@ def score_words(module, out_enc, seq, row_ptr):
         y, _, _ = ops.ln_fwd(x, arena.w(b + "norm2.weight"), arena.w(b + "norm2.bias"), 1e-5)
         q2 = ops.gemm_nt(y, arena.wb(b + "enc_attn.linear_q.weight"))
         att, mom = ops.xattn_rows_fwd(q2, kv[:, l * 2 * D:l * 2 * D + D], kv[:, l * 2 * D + D:(l + 1) * 2 * D], rows, H, T, scale,
-                                      want_moments=l == L - 1)
+                                      want_moments=want_moments and l == L - 1)
         moments = mom if mom is not None else moments
         x = _resid(x, att, arena.wb(b + "enc_attn.fc.weight"), None, 0.0, 0)
         y, _, _ = ops.ln_fwd(x, arena.w(b + "norm3.weight"), arena.w(b + "norm3.bias"), 1e-5)
@@ -506,3 +507,24 @@ def score_words(module, out_enc, seq, row_ptr):
     logits = ops.gemm_nt(y, packed.cls, epilogue=ops.EPI_F32, bias=packed.cls_bias)
     char_logp, score, length, char_pos = ops.nrtr_word_score(logits, C, seq, spec.start_idx, spec.padding_idx, moments=moments, H=H)
     return {"score": score, "length": length, "char_logp": char_logp, "char_pos": char_pos, "row_ptr": rows.on(seq.device)}
+
+
+@torch.no_grad()
+def twopass_decode(module, out_enc, frames, paths, lengths, weight, normalized=False):
+    """Two-pass decoding ("attention rescoring"; INTEGRATION.md, "Two-pass decoding: CTC proposals, attention rescoring";
+    kernels/nrtr_twopass.h): out_enc bf16 [B, 256, D]; frames fp32 [B, Tc, Cc] of the auxiliary CTC head (logits, or - normalized -
+    probabilities; class c + 1 is the decoder's class c); paths int32 [B, W, Tp] / lengths int32 [B, W], W proposals per image in CTC
+    classes (ops.ctc_beam_search's outputs, or any other decoder's); weight w in [0, 1] -> (paths int32 [B, W, max_seq_len] in decoder
+    classes, lengths int32 [B, W], scores fp32 [B, W] = (1 - w) att + w ctc, att_scores, ctc_scores fp32 [B, W], source int32 [B, W]),
+    best first.  Four stages: ops.nrtr_twopass_rows (the proposals as decoder rows and as a CTC word table), ops.ctc_score_paths
+    (the exact log p(word | frames)), score_words without the attention moments (one teacher-forced pass over the B * W rows, the
+    exact log p(word <EOS> | image); row_ptr is the host-known 0, W, 2 W, ..), ops.nrtr_twopass_select.  Neither score is the
+    proposer's own.  Eager launches, no host synchronisation."""
+    spec = module.dec_spec
+    B, W = paths.shape[0], paths.shape[1]
+    T = spec.max_seq_len
+    seq, targets, subset = ops.nrtr_twopass_rows(paths, lengths, spec.C, spec.start_idx, spec.start_idx, spec.padding_idx, T + 1,
+                                                 class_offset=1)
+    ctc = ops.ctc_score_paths(frames, paths, lengths, normalized=normalized, rows=(targets, subset))
+    att = score_words(module, out_enc, seq, list(range(0, (B + 1) * W, W)), want_moments=False)["score"]
+    return ops.nrtr_twopass_select(att, ctc, paths, lengths, subset, weight, T, class_offset=1)

@@ -25,6 +25,8 @@ makes `compute` decode by beam search over the NRTR decoder (`DINO_Finetune.forw
 (`update_paths`; on the host path: `idx2str` of `paths2nbest`); `forward_test` itself stays greedy.
 An AttnConvertor with a lexicon (and its `lexicon_beam`) makes `compute` decode over that closed vocabulary instead: rank 0 of
 `DINO_Finetune.forward_lexicon`'s paths through `update_paths` - no host synchronisation (host path: `paths2lexicon`).
+An AttnConvertor with `twopass_beam` > 0 makes `compute` score rank 0 of `DINO_Finetune.forward_twopass` - CTC proposals rescored by
+the decoder - through `update_paths`, again without a host synchronisation (host path: `paths2nbest` on the same outputs).
 """
 from __future__ import annotations
 
@@ -176,12 +178,15 @@ class TextAccuracy:
         convertor = net.label_convertor
         attn_beam = not is_ctc(convertor) and getattr(convertor, "beam_width", 0) > 0     # beam search over the NRTR decoder, rank 0 scored
         attn_lexicon = not is_ctc(convertor) and getattr(convertor, "lexicon", None) is not None     # ... along the lexicon's prefix tree
+        attn_twopass = not is_ctc(convertor) and getattr(convertor, "twopass_beam", 0) > 0     # CTC proposals rescored by the decoder, rank 0
         if device.type == "cuda" and not self.case_sensitive and convertor.score_table() is not None:
             for image_tensors, label_tensors in dataloader:
                 image_tensors = image_tensors.to(device)
                 span = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 span[0].record()
-                if attn_lexicon:
+                if attn_twopass:
+                    self.update_paths(net.forward_twopass(image_tensors)[0][:, 0], list(label_tensors[0]), convertor)
+                elif attn_lexicon:
                     self.update_paths(net.forward_lexicon(image_tensors)[2][:, 0], list(label_tensors[0]), convertor)
                 elif attn_beam:
                     self.update_paths(net.forward_beam(image_tensors, convertor.beam_width)[0][:, 0], list(label_tensors[0]), convertor)
@@ -190,13 +195,15 @@ class TextAccuracy:
                     self.update_scores(out_dec.float(), list(label_tensors[0]), convertor)
                 span[1].record()
                 self._spans.append(span)                                      # read in result(), behind its copy
-                if on_batch is not None and not attn_beam and not attn_lexicon:
+                if on_batch is not None and not attn_beam and not attn_lexicon and not attn_twopass:
                     on_batch(out_dec.float(), list(label_tensors[0]))
             return self.result()
         for image_tensors, label_tensors in dataloader:
             image_tensors = image_tensors.to(device)
             start = time.time()
-            if attn_lexicon:
+            if attn_twopass:
+                nbest = convertor.paths2nbest(*net.forward_twopass(image_tensors))[0]
+            elif attn_lexicon:
                 nbest = convertor.paths2lexicon(*net.forward_lexicon(image_tensors)[:2], nbest=1)[0]
             elif attn_beam:
                 nbest = convertor.paths2nbest(*net.forward_beam(image_tensors, convertor.beam_width))[0]
@@ -208,6 +215,6 @@ class TextAccuracy:
             pt_text = convertor.idx2str(label_indexes)
             self.inference_time += time.time() - start
             self.update(list(label_tensors[0]), pt_text)
-            if on_batch is not None and not attn_beam and not attn_lexicon:
+            if on_batch is not None and not attn_beam and not attn_lexicon and not attn_twopass:
                 on_batch(out_dec.float(), list(label_tensors[0]))
         return self.result()

@@ -165,17 +165,22 @@ class DINO_Finetune(ArenaModule):
     `ctc_decoder = CTCDecoder(embed_dim, 92)` on the same backbone tokens, trained under (1 - a) TFLoss + a CTCLoss (the parts:
     `last_losses`), read through `forward_ctc`; absent or 0 is the model without it, key for key.  `decoder.joint_ctc_weight: w` in
     [0, 1] - it needs that head and `decoder.beam_width` in 1..16, and excludes a lexicon - makes `forward_beam` rescore every
-    candidate with the CTC prefix probability of its characters (kernels/nrtr_joint.h)."""
+    candidate with the CTC prefix probability of its characters (kernels/nrtr_joint.h).  `decoder.twopass_beam: N` (1..16, with
+    `decoder.twopass_ctc_weight: w` in [0, 1], default 0.5) needs that head too and excludes the three other decoders: evaluation
+    scores rank 0 of `forward_twopass` - the CTC beam proposes N words, the decoder rescores them in one pass (kernels/nrtr_twopass.h)."""
 
     aux_ctc_weight = 0.0               # decoder.aux_ctc_weight; > 0: the model owns ctc_decoder and ctc_loss
     joint_ctc_weight = None            # decoder.joint_ctc_weight; a number: forward_beam decodes jointly
     last_losses = None                 # hybrid: {'tf', 'ctc'}, the two parts of the last forward_train as device scalars
-    last_att_scores = None             # joint decoding: the attention scores of the last forward_beam, fp32 [N, W]
+    last_att_scores = None             # joint decoding: the attention scores of the last forward_beam, fp32 [N, W]; two-pass too
+    last_ctc_scores = None             # two-pass decoding: the CTC scores of the last forward_twopass, fp32 [N, W]
+    last_sources = None                # ... and the proposal slot of every rank, int32 [N, W]
 
     def __init__(self, config):
         super().__init__()
         self.ctc = getattr(config, "decoder_type", None) == "CTCDecoder"
         aux, joint = self._checked_hybrid_keys(config)
+        twopass = self._checked_twopass_keys(config, aux, joint)
         if self.ctc:
             self._init_ctc(config)
             return
@@ -187,7 +192,8 @@ class DINO_Finetune(ArenaModule):
                                              beam_width=int(getattr(config, "decoder_beam_width", 0) or 0),     # absent or 0: greedy
                                              lexicon=getattr(config, "decoder_lexicon", None) or None,          # absent: no lexicon; with
                                              lexicon_beam=int(getattr(config, "decoder_lexicon_beam", 0) or 0),  # its beam (alone: refused)
-                                             lm=getattr(config, "decoder_lm", None) or None)                    # (refused as well)
+                                             lm=getattr(config, "decoder_lm", None) or None,                    # (refused as well)
+                                             twopass_beam=twopass[0], twopass_ctc_weight=twopass[1])            # absent: 0, None
         config.arch = config.arch.replace("deit", "vit")
         if config.arch not in vits.__dict__:
             raise NotImplementedError(f"Unknow architecture: {config.arch} (HIP kernels cover vit_tiny / vit_small / vit_base)")
@@ -237,6 +243,29 @@ class DINO_Finetune(ArenaModule):
         if joint is not None and not aux > 0:
             raise ValueError("decoder.joint_ctc_weight needs decoder.aux_ctc_weight > 0: the auxiliary CTC head gives the prefix scores")
         return float(aux), joint
+
+    def _checked_twopass_keys(self, config, aux, joint):
+        """(decoder.twopass_beam, absent: 0; decoder.twopass_ctc_weight, absent: None - the convertor's default), checked against the
+        head and the other decoders' keys."""
+        beam, weight = getattr(config, "decoder_twopass_beam", None), getattr(config, "decoder_twopass_ctc_weight", None)
+        if not beam and weight is None:                    # (a weight without a beam: the convertor refuses it)
+            return 0, None
+        if self.ctc:
+            raise ValueError("decoder.twopass_beam / decoder.twopass_ctc_weight rescore CTC proposals with the NRTR decoder: decoder.type "
+                             "'CTCDecoder' has none")
+        if beam:
+            if not aux > 0:
+                raise ValueError("decoder.twopass_beam needs decoder.aux_ctc_weight > 0: the auxiliary CTC head proposes the words")
+            if int(getattr(config, "decoder_beam_width", 0) or 0) > 0:
+                raise ValueError("decoder.twopass_beam excludes decoder.beam_width > 0: the proposals come from the CTC beam of width "
+                                 "twopass_beam, and one decoder is scored")
+            if getattr(config, "decoder_lexicon", None) or getattr(config, "decoder_lexicon_beam", None):
+                raise ValueError("decoder.twopass_beam excludes decoder.lexicon / decoder.lexicon_beam: rescoring a lexicon's proposals "
+                                 "goes through forward_twopass(proposals=)")
+            if joint is not None:
+                raise ValueError("decoder.twopass_beam excludes decoder.joint_ctc_weight: joint decoding rescores inside the attention "
+                                 "beam, two-pass decoding behind the CTC beam")
+        return beam, weight
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         """A checkpoint of the NRTR recogniser alone loads into the hybrid model: the auxiliary CTC head stays as it was initialised."""
@@ -363,6 +392,43 @@ class DINO_Finetune(ArenaModule):
             frames = self.ctc_decoder.forward_train(feat)      # the head's logits [N, 32, 92], rows of a 128-wide buffer
         paths, lengths, scores, self.last_att_scores = self.decoder.forward_beam(feat, self.encoder(feat), beam_width, ctc_frames=frames,
                                                                                  ctc_weight=w)
+        return paths, lengths, scores
+
+    @torch.no_grad()
+    def forward_twopass(self, img, beam=None, ctc_weight=None, proposals=None):
+        """Two-pass decoding ("attention rescoring"): img [N,3,32,128] -> (paths int32 [N, W, max_seq_len] by rank, -1-padded; lengths
+        int32 [N, W]; scores fp32 [N, W]), the shapes of forward_beam.  The auxiliary CTC head's prefix beam of width `beam` (default:
+        `decoder.twopass_beam`) proposes W words per image; the decoder scores all of them in one teacher-forced pass; S = (1 - w) log
+        p(word <EOS> | image) + w log p(word | frames), both exact (forward_score's and ops.ctc_score_paths' numbers, not the
+        proposer's), w = `ctc_weight` (default: `decoder.twopass_ctc_weight`, 0.5 where the model has none - untuned); ranks go by (S
+        descending, proposal slot ascending).  `last_att_scores`, `last_ctc_scores` (fp32 [N, W]) and `last_sources` (int32 [N, W]: the
+        proposal slot of every rank) keep the parts.  A proposal that is unused, longer than max_seq_len - 1 characters, holds a class
+        the decoder cannot write, or has no finite score is dropped; a rank left over is (-1.., -1, -inf).
+        proposals=(paths int32 [N, W, Tp], lengths int32 [N, W]): any decoder's hypotheses on forward_ctc(img), in CTC classes -
+        ops.ctc_beam_search_lm, the paths of ops.ctc_beam_search_trie, a CTCConvertor's n-best; their own scores are not used.
+        Nothing is read back."""
+        if self.ctc:
+            raise NotImplementedError("forward_twopass is the NRTR head's (its decoder rescores CTC proposals); the CTC head's beam is "
+                                      "CTCConvertor.tensor2nbest on forward_test")
+        if not self.aux_ctc_weight > 0:
+            raise ValueError("forward_twopass: the model has no auxiliary CTC head to propose words (decoder.aux_ctc_weight)")
+        from .. import ops
+        conv = self.label_convertor
+        w = ctc_weight if ctc_weight is not None else (conv.twopass_ctc_weight if conv.twopass_ctc_weight is not None
+                                                        else conv.TWOPASS_DEFAULT_WEIGHT)
+        if isinstance(w, bool) or not isinstance(w, (int, float)) or not 0.0 <= float(w) <= 1.0:
+            raise ValueError(f"forward_twopass: ctc_weight must lie in [0, 1], got {w!r}")
+        if proposals is None:
+            width = conv.twopass_beam if beam is None else beam
+            if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= ops.NRTR_MAX_BEAM:
+                raise ValueError(f"forward_twopass: beam must lie in 1..{ops.NRTR_MAX_BEAM} (decoder.twopass_beam), got {width!r}")
+        elif beam is not None:
+            raise ValueError("forward_twopass: beam is the width of the default proposals; proposals= bring their own")
+        feat = self.extract_feat(img)
+        probs = self.ctc_decoder.forward_test(feat)            # the head's frame probabilities [N, 32, 92]
+        paths, lengths = ops.ctc_beam_search(probs, width, normalized=True)[:2] if proposals is None else proposals
+        paths, lengths, scores, self.last_att_scores, self.last_ctc_scores, self.last_sources = self.decoder.forward_twopass(
+            feat, self.encoder(feat), probs, paths, lengths, float(w), normalized=True)
         return paths, lengths, scores
 
     def forward_lexicon(self, img, lexicon_beam=None):

@@ -1525,6 +1525,120 @@ def nrtr_word_score(logits, C, seq, end_idx, pad_idx, moments=None, H=None):
     return char_logp, score, length, char_pos
 
 
+# ------------------------------------------------------------------------------------------ two-pass decoding (kernels/nrtr_twopass.h)
+NRTR_TWOPASS_MAX_PATH = 128                               # nrtr_twopass.h: NTP_MAX_PATH
+
+
+def _twopass_proposals(who, paths, lengths):
+    """The check both two-pass kernels start with: paths int32 [B, W, Tp] with dense entries (any sample / slot stride), lengths
+    contiguous int32 [B, W] on the same device, W in 1..NRTR_MAX_BEAM, Tp in 1..NRTR_TWOPASS_MAX_PATH -> (B, W, Tp, sample stride, slot
+    stride)."""
+    for name, t in (("paths", paths), ("lengths", lengths)):
+        if not isinstance(t, torch.Tensor) or t.dtype != I32:
+            raise TypeError(f"{who}: {name} must be an int32 tensor, got {t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if paths.dim() != 3 or (paths.shape[2] > 1 and paths.stride(2) != 1):
+        raise ValueError(f"{who}: expects paths [B, W, Tp] with dense entries, got {list(paths.shape)}, strides {paths.stride()}")
+    B, W, Tp = paths.shape
+    if not 1 <= W <= NRTR_MAX_BEAM or not 1 <= Tp <= NRTR_TWOPASS_MAX_PATH:
+        raise ValueError(f"{who}: expects paths [B, 1..{NRTR_MAX_BEAM}, 1..{NRTR_TWOPASS_MAX_PATH}], got {list(paths.shape)}")
+    if tuple(lengths.shape) != (B, W) or not lengths.is_contiguous() or lengths.device != paths.device:
+        raise ValueError(f"{who}: expects contiguous lengths [{B}, {W}] on {paths.device}, got {list(lengths.shape)} on {lengths.device}")
+    return B, W, Tp, paths.stride(0) if B > 1 else W * Tp, paths.stride(1) if W > 1 else Tp
+
+
+def _class_offset(who, class_offset):
+    if isinstance(class_offset, bool) or class_offset not in (0, 1):
+        raise ValueError(f"{who}: class_offset must be 0 or 1, got {class_offset!r}")
+    return int(class_offset)
+
+
+def nrtr_twopass_rows(paths, lengths, classes, start_idx, end_idx, pad_idx, seq_len, max_labels=None, class_offset=1, want_seq=True):
+    """The words a CTC decoder proposes -> the rows of the NRTR decoder's teacher-forced pass and the CTC scorer's word table, in one
+    launch (kernels/nrtr_twopass.h: ccd_nrtr_twopass_rows; tests/nrtr_twopass_np.py is the specification): paths int32 [B, W, Tp],
+    -1-padded CTC classes, lengths int32 [B, W] (-1: an unused slot), as ctc_beam_search(_lm / _trie) returns them -> (seq int64 [B * W,
+    seq_len] = <BOS> d1 .. dn <EOS> <PAD>.. with d = c - class_offset, AttnConvertor.words2rows' layout; targets int64 [B * W,
+    max_labels] = c1 .. cn 0.., ctc_paths_to_targets' layout; subset int32 [B, W] = b * W + k, or -1).  A slot is INELIGIBLE - <BOS>
+    <PAD>.., zeros, -1 - when it is unused, longer than min(Tp, seq_len - 2, max_labels), or holds a class with c < 1, d outside [0,
+    classes), d == end_idx or d == pad_idx: seq holds no token but start_idx, end_idx, pad_idx and classes in [0, classes).  max_labels
+    defaults to min(Tp, CTC_MAX_LABELS).  want_seq=False: the CTC side alone (seq is None; end_idx / pad_idx may be -1: no such class)."""
+    who = "nrtr_twopass_rows"
+    B, W, Tp, s0, s1 = _twopass_proposals(who, paths, lengths)
+    off = _class_offset(who, class_offset)
+    classes, seq_len = int(classes), int(seq_len)
+    Lmax = min(Tp, CTC_MAX_LABELS) if max_labels is None else int(max_labels)
+    if not 1 <= classes <= NRTR_MAX_CLASSES or not 2 <= seq_len <= NRTR_MAX_POSITIONS or not 1 <= Lmax <= CTC_MAX_LABELS:
+        raise ValueError(f"{who}: expects classes in 1..{NRTR_MAX_CLASSES}, seq_len in 2..{NRTR_MAX_POSITIONS} and max_labels in "
+                         f"1..{CTC_MAX_LABELS}, got {classes}, {seq_len}, {Lmax}")
+    lowest = 0 if want_seq else -1
+    for name, v in (("start_idx", start_idx), ("end_idx", end_idx), ("pad_idx", pad_idx)):
+        if not lowest <= int(v) < 65536:
+            raise ValueError(f"{who}: {name} must lie in [{lowest}, 65536), got {v}")
+    dev = paths.device
+    seq = torch.empty((B * W, seq_len), dtype=I64, device=dev) if want_seq else None
+    targets = torch.empty((B * W, Lmax), dtype=I64, device=dev)
+    subset = torch.empty((B, W), dtype=I32, device=dev)
+    _call("ccd_nrtr_twopass_rows", paths if B else None, s0, s1, lengths if B else None, B, W, Tp, off, classes, int(start_idx),
+          int(end_idx), int(pad_idx), seq if B else None, seq_len, targets if B else None, Lmax, subset if B else None)
+    return seq, targets, subset
+
+
+def nrtr_twopass_select(att, ctc, paths, lengths, subset, weight, max_seq_len, class_offset=1):
+    """Combine, rank, gather (kernels/nrtr_twopass.h: ccd_nrtr_twopass_select): att fp32 [B * W] (nrtr_word_score's score of
+    nrtr_twopass_rows' seq), ctc fp32 [B, W] (ctc_score_paths), the proposals and nrtr_twopass_rows' subset -> (paths int32 [B, W,
+    max_seq_len] in decoder classes, -1-padded; lengths int32 [B, W]; scores, att_scores, ctc_scores fp32 [B, W]; source int32 [B, W]),
+    best first.  A slot is eligible iff subset >= 0, its length lies in 0..min(Tp, max_seq_len) and both scores are finite; S = (1 -
+    weight) att + weight ctc in fp64, a term whose weight is exactly 0 left out; ranks go by (S descending, slot ascending); a rank
+    left over holds (-1.., -1, -inf, -inf, -inf, -1)."""
+    who = "nrtr_twopass_select"
+    B, W, Tp, s0, s1 = _twopass_proposals(who, paths, lengths)
+    off = _class_offset(who, class_offset)
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0.0 <= float(weight) <= 1.0:      # (a NaN fails both)
+        raise ValueError(f"{who}: weight must lie in [0, 1], got {weight!r}")
+    T = int(max_seq_len)
+    if not 1 <= T <= NRTR_MAX_POSITIONS:
+        raise ValueError(f"{who}: max_seq_len must lie in 1..{NRTR_MAX_POSITIONS}, got {max_seq_len}")
+    dev = paths.device
+    for name, t, dtype, shape in (("att", att, F32, (B * W,)), ("ctc", ctc, F32, (B, W)), ("subset", subset, I32, (B, W))):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise TypeError(f"{who}: {name} must be a {dtype} tensor, got {t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{who}: expects contiguous {name} {list(shape)} on {dev}, got {list(t.shape)} on {t.device}")
+    out_paths, out_lengths, scores = _beam_outputs(B, W, T, dev)
+    att_scores, ctc_scores = torch.empty((B, W), dtype=F32, device=dev), torch.empty((B, W), dtype=F32, device=dev)
+    source = torch.empty((B, W), dtype=I32, device=dev)
+    if B:
+        _call("ccd_nrtr_twopass_select", paths, s0, s1, lengths, B, W, Tp, off, att, ctc, subset, float(weight), T, out_paths, out_lengths,
+              scores, att_scores, ctc_scores, source)
+    return out_paths, out_lengths, scores, att_scores, ctc_scores, source
+
+
+def ctc_score_paths(scores, paths, lengths, normalized=False, rows=None):
+    """The exact log p(word | frames) of ANY decoder's hypotheses: scores fp32 [B, T, C] (any sample / step stride), logits or -
+    normalized=True - probabilities; paths int32 [B, W, Tp] -1-padded CTC classes and lengths int32 [B, W], as ctc_beam_search(_lm /
+    _trie) returns them -> fp32 [B, W], the CTC forward log-likelihood summed over ALL alignments (a beam's own score sums only the
+    alignments the beam kept).  No new scoring kernel and no host copy: nrtr_twopass_rows writes the device word table and `subset`
+    that ctc_lexicon_score's kernel takes (V = B * W words, sample b scoring its own W).  -inf for an unused slot, a class outside [1,
+    C), a word no alignment spells, and a path longer than CTC_MAX_LABELS = 31 characters - the lexicon scorer's own limit on a word.
+    rows: (targets, subset) of an nrtr_twopass_rows call on the same proposals, to save the launch (slots ineligible there are -inf)."""
+    B, T, C = _frame_scores("ctc_score_paths", scores)
+    Bp, W, Tp, _, _ = _twopass_proposals("ctc_score_paths", paths, lengths)
+    if Bp != B or paths.device != scores.device:
+        raise ValueError(f"ctc_score_paths: scores are {list(scores.shape)} on {scores.device}, paths {list(paths.shape)} on {paths.device}")
+    if rows is None:
+        _, targets, subset = nrtr_twopass_rows(paths, lengths, NRTR_MAX_CLASSES, -1, -1, -1, NRTR_MAX_POSITIONS, want_seq=False)
+    else:
+        targets, subset = rows
+        if targets.dtype != I64 or targets.dim() != 2 or targets.shape[0] != B * W or not 1 <= targets.shape[1] <= CTC_MAX_LABELS or \
+                not targets.is_contiguous() or subset.dtype != I32 or tuple(subset.shape) != (B, W) or not subset.is_contiguous():
+            raise ValueError(f"ctc_score_paths: rows must be nrtr_twopass_rows' (targets int64 [{B * W}, 1..{CTC_MAX_LABELS}], subset int32 "
+                             f"[{B}, {W}]), got {list(targets.shape)} and {list(subset.shape)}")
+    out = torch.full((B, W), float("-inf"), dtype=F32, device=scores.device)
+    if B:
+        _call("ccd_ctc_lexicon_score", scores, scores.stride(0), scores.stride(1), B, T, C, 1 if normalized else 0, targets, B * W,
+              targets.shape[1], None, subset, W, out, W)
+    return out
+
+
 class SsimFn(torch.autograd.Function):
     """apply(window, taps, size_average, img1, img2[, img3]) -> mean (0-dim) or per-image means [N]; backward on the kernels."""
 

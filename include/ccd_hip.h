@@ -744,6 +744,38 @@ int ccd_xattn_rows_fwd(const ccd_bf16* q, long ldq, const ccd_bf16* k, long ldk,
                        void* stream);
 int ccd_nrtr_word_score(const float* logits, long ldl, int classes, const int64_t* seq, int rows, int seq_len, int end_idx, int pad_idx,
                         const float* moments, int heads, float* char_logp, float* score, int* length, float* char_pos, void* stream);
+/* Two-pass decoding (ABI 30; kernels/nrtr_twopass.h, restated in numpy in tests/nrtr_twopass_np.py): the words a CTC decoder proposes
+ * become rows of the NRTR decoder's teacher-forced pass and of ccd_ctc_lexicon_score's word table, and the two exact scores rank them
+ * again.  One wavefront per image, no workspace, no atomics: the same input gives the same bits.
+ * Both take the proposals as ccd_ctc_beam_search returns them: paths int32, slot k of image b at paths + b * sample_stride + k *
+ * slot_stride, path_len dense entries, -1-padded CTC classes (class 0, the blank, is never part of a word); lengths int32 [batch, beam],
+ * -1 for an unused slot.  CTC class c is decoder class d = c - class_offset (class_offset in {0, 1}).
+ * ccd_nrtr_twopass_rows: slot k of image b is ELIGIBLE iff its length n lies in 0..min(path_len, seq_len - 2, max_labels) and every one
+ *   of its n classes has c >= 1, 0 <= d < classes, d != end_idx, d != pad_idx.  Row b * beam + k of
+ *   seq      int64 [batch * beam, seq_len]: <BOS> d1 .. dn <EOS> <PAD>.. when eligible, <BOS> <PAD>.. when not (ccd_nrtr_word_score reports
+ *            that row as -inf, -1).  May be null: the CTC side alone; end_idx and pad_idx may then be -1 (no such class).
+ *   targets  int64 [batch * beam, max_labels]: c1 .. cn 0.. when eligible, zeros when not - ccd_ctc_lexicon_score's `words`
+ *   subset   int32 [batch, beam]: b * beam + k when eligible, -1 when not - ccd_ctc_lexicon_score's `subset`
+ *   The proposals are not trusted: a class is read only in front of a length that fits, and seq holds nothing but start_idx, end_idx,
+ *   pad_idx and classes in [0, classes).  The empty word (n = 0) is eligible.
+ * ccd_nrtr_twopass_select: att fp32 [batch * beam] (ccd_nrtr_word_score's score of the rows above), ctc fp32 [batch, beam]
+ *   (ccd_ctc_lexicon_score's), subset as above.  Slot k is eligible iff subset >= 0, its length lies in 0..min(path_len, max_seq_len) and
+ *   att and ctc are both finite.  S = (1 - weight) att + weight ctc in fp64; a term whose weight is exactly 0 is left out.  Rank by (S
+ *   descending, slot ascending), ccd_nrtr_beam_step's comparison.  Rank r of image b:
+ *   out_paths int32 [batch, beam, max_seq_len] the word in decoder classes, -1-padded; out_lengths int32 [batch, beam]; scores fp32 [batch,
+ *   beam] = S rounded once; att_scores, ctc_scores fp32 [batch, beam] its two parts; source int32 [batch, beam] its proposal slot.  A rank
+ *   left over holds (-1.., -1, -inf, -inf, -inf, -1).
+ * batch == 0 is a no-op.  CCD_EINVAL: a missing pointer, a negative size or stride; CCD_ESHAPE: beam outside 1..CCD_NRTR_MAX_BEAM,
+ * path_len outside 1..128, class_offset outside 0..1, classes outside 1..128, seq_len outside 2..128, max_labels outside
+ * 1..CCD_CTC_MAX_LABELS, start_idx / end_idx / pad_idx outside [0, 65536) (end_idx, pad_idx: [-1, 65536) without seq), max_seq_len
+ * outside 1..128, weight outside [0, 1] or not finite.  Nothing is launched on an error. */
+int ccd_nrtr_twopass_rows(const int* paths, long sample_stride, long slot_stride, const int* lengths, int batch, int beam, int path_len,
+                          int class_offset, int classes, int start_idx, int end_idx, int pad_idx, int64_t* seq, int seq_len,
+                          int64_t* targets, int max_labels, int* subset, void* stream);
+int ccd_nrtr_twopass_select(const int* paths, long sample_stride, long slot_stride, const int* lengths, int batch, int beam, int path_len,
+                            int class_offset, const float* att, const float* ctc, const int* subset, double weight, int max_seq_len,
+                            int* out_paths, int* out_lengths, float* scores, float* att_scores, float* ctc_scores, int* source,
+                            void* stream);
 
 /* ---------------------------------------------------------------- DINOHead pieces, vit.py:313,326 */
 int ccd_l2norm_fwd(const ccd_bf16* x, ccd_bf16* y, float* inv, int max_rows, const int* d_rows, int rows_mul, int D,

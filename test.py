@@ -63,10 +63,12 @@ def alignment_writer(convertor, out, name, image_width=128):
 
 def decoded_words(net, images):
     """The word the NRTR head's configured decoder returns for every image, as class indices (None: the lexicon's beam ended without
-    a word): rank 0 of forward_lexicon (a lexicon and its lexicon_beam), of forward_beam at beam_width, or of the beam of width 1,
-    which is greedy decoding."""
+    a word): rank 0 of forward_twopass (twopass_beam), of forward_lexicon (a lexicon and its lexicon_beam), of forward_beam at
+    beam_width, or of the beam of width 1, which is greedy decoding."""
     conv = net.label_convertor
-    if conv.lexicon is not None:
+    if getattr(conv, "twopass_beam", 0) > 0:
+        paths, lengths, _ = net.forward_twopass(images)
+    elif conv.lexicon is not None:
         _, _, paths, lengths = net.forward_lexicon(images)
     else:
         paths, lengths, _ = net.forward_beam(images, conv.beam_width if conv.beam_width > 0 else 1)

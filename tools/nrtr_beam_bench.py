@@ -5,6 +5,7 @@
     python tools/nrtr_beam_bench.py --cases trie --out profiles/nrtr_beam_trie.json
     python tools/nrtr_beam_bench.py --cases score --out profiles/nrtr_score.json
     python tools/nrtr_beam_bench.py --cases joint --out profiles/nrtr_beam_joint.json
+    python tools/nrtr_beam_bench.py --cases twopass --out profiles/nrtr_twopass.json
 
 The cases, each in a process of its own under its own time limit; the next one starts only if the one before ended well:
   kernels  ccd_nrtr_beam_step and ccd_nrtr_beam_reorder per launch at B = 512, T = 25, C = 92 (logits rows 128 wide), D = 512,
@@ -32,6 +33,11 @@ The cases, each in a process of its own under its own time limit; the next one s
            same logits, both on a state eight steps into their own decode (with how many slots are still live); ccd_nrtr_joint_begin
            per launch; then evaluation images/s at B = 512, vit_small with an auxiliary CTC head: forward_beam with joint_ctc_weight
            0.3 against the plain forward_beam at widths 4, 8 and 16, rounds alternating.
+  twopass  (not part of a default run) two-pass decoding (kernels/nrtr_twopass.h): at B = 512, vit_small with an auxiliary CTC head and
+           widths 4, 8, 16, on the proposals ops.ctc_beam_search makes of the model's own frames: ccd_nrtr_twopass_rows and
+           ccd_nrtr_twopass_select per launch (through their wrappers, allocations included), ops.ctc_score_paths, the teacher-forced
+           pass (finetune_engine.score_words without moments over the B * W rows) and forward_twopass end to end; in the same process
+           and rounds forward_beam plain and with joint_ctc_weight at the same widths.
 Warm-up first, HIP events around every timed call, a figure is the median of the round medians with the lowest and highest
 round.  No threshold is set; the file records what was measured.  `--case NAME` runs one case and prints its JSON line."""
 import argparse
@@ -46,7 +52,7 @@ sys.path.insert(0, ROOT)
 
 B, T, C, D, L = 512, 25, 92, 512, 6
 WIDTHS = (1, 4, 8, 16)
-LIMITS = {"kernels": 240, "eval": 420, "rescore": 180, "trie": 600, "score": 420, "joint": 420}      # seconds per case
+LIMITS = {"kernels": 240, "eval": 420, "rescore": 180, "trie": 600, "score": 420, "joint": 420, "twopass": 420}      # seconds per case
 TRIE_WIDTHS, TRIE_LEXICONS = (4, 8, 16), (1000, 10000, 90000)
 
 
@@ -451,7 +457,62 @@ def case_joint(a):
     return out
 
 
-CASES = {"joint": case_joint, "kernels": case_kernels, "eval": case_eval, "rescore": case_rescore, "trie": case_trie, "score": case_score}
+TWOPASS_WIDTHS, TWOPASS_WEIGHT = (4, 8, 16), 0.5
+
+
+def case_twopass(a):
+    import torch
+    from ccd_amd import finetune as ft, finetune_engine as fe, ops
+    dev = torch.device("cuda")
+    torch.manual_seed(0)
+    cfg = ft.FinetuneConfig()
+    cfg.decoder_aux_ctc_weight = 0.3
+    model = ft.build_model(cfg, dev, dropout=0.0).eval()
+    with torch.no_grad():
+        model.arena.w("ctc_decoder.fc.bias")[0] += 5.0                            # (an untrained head is uniform: nothing would finish)
+    model.arena.refresh_mirrors()
+    img = torch.randn(B, 3, 32, 128, generator=torch.Generator().manual_seed(4)).to(dev)
+    dec, spec = model.decoder, model.decoder.dec_spec
+    out = {"batch": B, "arch": "vit_small", "decoder_layers": spec.L, "ctc_weight": TWOPASS_WEIGHT,
+           "decode_graph": os.environ.get("CCD_DECODE_GRAPH", "1") != "0"}
+    iters = max(3, a.iters // 6)
+    with torch.no_grad():
+        feat = model.extract_feat(img)
+        probs = model.ctc_decoder.forward_test(feat)
+        out_enc = model.encoder(feat).to(torch.bfloat16)
+        dec._ready()
+        for W in TWOPASS_WIDTHS:
+            paths, lengths, _ = ops.ctc_beam_search(probs, W, normalized=True)
+            rows = lambda: ops.nrtr_twopass_rows(paths, lengths, spec.C, spec.start_idx, spec.start_idx, spec.padding_idx, T + 1)      # noqa: E731
+            seq, targets, subset = rows()
+            row_ptr = ops.csr_rows(list(range(0, (B + 1) * W, W)))
+            att = fe.score_words(dec, out_enc, seq, row_ptr, want_moments=False)["score"]
+            ctc = ops.ctc_score_paths(probs, paths, lengths, normalized=True, rows=(targets, subset))
+            stages = {"ccd_nrtr_twopass_rows": rows,
+                      "ccd_nrtr_twopass_select": lambda: ops.nrtr_twopass_select(att, ctc, paths, lengths, subset, TWOPASS_WEIGHT, T),
+                      "ctc_score_paths (given the rows)": lambda: ops.ctc_score_paths(probs, paths, lengths, normalized=True, rows=(targets, subset)),
+                      "ctc_score_paths (with its own rows launch)": lambda: ops.ctc_score_paths(probs, paths, lengths, normalized=True),
+                      "ctc_beam_search (the proposals)": lambda: ops.ctc_beam_search(probs, W, normalized=True),
+                      "teacher_forced_pass (score_words, no moments)": lambda: fe.score_words(dec, out_enc, seq, row_ptr, want_moments=False)}
+            ends = {"forward_twopass": lambda: model.forward_twopass(img, beam=W, ctc_weight=TWOPASS_WEIGHT),
+                    "forward_beam": lambda: model.forward_beam(img, W),
+                    "forward_beam_joint": lambda: model.forward_beam(img, W, joint_ctc_weight=JOINT_WEIGHT)}
+            times = {name: [] for name in list(stages) + list(ends)}
+            for _ in range(a.rounds):                                             # rounds alternate between all sides
+                for name, fn in stages.items():
+                    times[name].append(event_ms(fn, a.iters))
+                for name, fn in ends.items():
+                    times[name].append(event_ms(fn, iters))
+            entry = {"rows": B * W, "eligible_rows": int((subset >= 0).sum())}
+            for name, rounds in times.items():
+                entry[name] = summary(rounds)
+                if name in ends:
+                    entry[name + "_images_per_s"] = round(B / (entry[name]["median_ms"] * 1e-3))
+            out[f"w{W}"] = entry
+    return out
+
+
+CASES = {"joint": case_joint, "twopass": case_twopass, "kernels": case_kernels, "eval": case_eval, "rescore": case_rescore, "trie": case_trie, "score": case_score}
 
 
 def main():
