@@ -342,6 +342,21 @@ static int ccd_seg_prepare(int images, long pixels, int* cm, int* status, int* c
     }
     return CCD_OK;
 }
+// The three CTC beam entry points: their common contract in the order of its return codes - `own_shape` and `own_pointers` are the
+// clauses of the caller's mode - and the launch of its instance.
+template <int kMode>
+static int ccd_ctc_beam(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized, int beam,
+                        int* paths, int* lengths, float* hyp_scores, bool own_shape, bool own_pointers, ccd::CtcBeamLm lm,
+                        ccd::CtcBeamTrie trie, void* stream) {
+    CCD_CHECK(batch >= 0 && sample_stride >= 0 && step_stride >= 0, CCD_EINVAL);
+    CCD_CHECK(beam >= 1 && beam <= ccd::CTC_MAX_BEAM && steps >= 1 && steps <= ccd::CTC_MAX_T && classes >= 2 && classes <= ccd::CTC_MAX_C &&
+              (normalized == 0 || normalized == 1) && own_shape, CCD_ESHAPE);
+    if (batch == 0) return CCD_OK;
+    CCD_CHECK(scores && paths && lengths && hyp_scores && own_pointers, CCD_EINVAL);
+    CCD_LAUNCH(ccd::ctc_beam_kernel<kMode>, dim3((unsigned)((batch + ccd::CTC_WAVES - 1) / ccd::CTC_WAVES)), dim3(ccd::CTC_THREADS), 0, stream,
+               scores, sample_stride, step_stride, batch, steps, classes, normalized, beam, paths, lengths, hyp_scores, lm, trie);
+    return ccd_rt_last_error();
+}
 
 extern "C" {
 
@@ -1422,43 +1437,24 @@ int ccd_ctc_greedy(const float* logits, long sample_stride, long step_stride, in
 }
 int ccd_ctc_beam_search(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
                         int beam, int* paths, int* lengths, float* hyp_scores, void* stream) {
-    CCD_CHECK(batch >= 0 && sample_stride >= 0 && step_stride >= 0, CCD_EINVAL);
-    CCD_CHECK(beam >= 1 && beam <= ccd::CTC_MAX_BEAM && steps >= 1 && steps <= ccd::CTC_MAX_T && classes >= 2 && classes <= ccd::CTC_MAX_C &&
-              (normalized == 0 || normalized == 1), CCD_ESHAPE);
-    if (batch == 0) return CCD_OK;
-    CCD_CHECK(scores && paths && lengths && hyp_scores, CCD_EINVAL);
-    CCD_LAUNCH(ccd::ctc_beam_kernel<ccd::CTC_BEAM_PLAIN>, dim3((unsigned)((batch + ccd::CTC_WAVES - 1) / ccd::CTC_WAVES)), dim3(ccd::CTC_THREADS), 0, stream,
-               scores, sample_stride, step_stride, batch, steps, classes, normalized, beam, paths, lengths, hyp_scores, ccd::CtcBeamLm{},
-               ccd::CtcBeamTrie{});
-    return ccd_rt_last_error();
+    return ccd_ctc_beam<ccd::CTC_BEAM_PLAIN>(scores, sample_stride, step_stride, batch, steps, classes, normalized, beam, paths, lengths,
+                                             hyp_scores, true, true, ccd::CtcBeamLm{}, ccd::CtcBeamTrie{}, stream);
 }
 int ccd_ctc_beam_search_lm(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
                            int beam, const float* lm, int order, float weight, float bonus, int eos, int* paths, int* lengths,
                            float* hyp_scores, void* stream) {
-    CCD_CHECK(batch >= 0 && sample_stride >= 0 && step_stride >= 0, CCD_EINVAL);
-    CCD_CHECK(beam >= 1 && beam <= ccd::CTC_MAX_BEAM && steps >= 1 && steps <= ccd::CTC_MAX_T && classes >= 2 && classes <= ccd::CTC_MAX_C &&
-              (normalized == 0 || normalized == 1) && order >= 1 && order <= CCD_CTC_LM_MAX_ORDER && (eos == 0 || eos == 1) &&
-              __builtin_isfinite(weight) && __builtin_isfinite(bonus), CCD_ESHAPE);
-    if (batch == 0) return CCD_OK;
-    CCD_CHECK(scores && lm && paths && lengths && hyp_scores, CCD_EINVAL);
-    const ccd::CtcBeamLm model{lm, order, eos, (double)weight, (double)bonus};
-    CCD_LAUNCH(ccd::ctc_beam_kernel<ccd::CTC_BEAM_LM>, dim3((unsigned)((batch + ccd::CTC_WAVES - 1) / ccd::CTC_WAVES)), dim3(ccd::CTC_THREADS), 0, stream,
-               scores, sample_stride, step_stride, batch, steps, classes, normalized, beam, paths, lengths, hyp_scores, model,
-               ccd::CtcBeamTrie{});
-    return ccd_rt_last_error();
+    const bool shape = order >= 1 && order <= CCD_CTC_LM_MAX_ORDER && (eos == 0 || eos == 1) && __builtin_isfinite(weight) &&
+                       __builtin_isfinite(bonus);
+    return ccd_ctc_beam<ccd::CTC_BEAM_LM>(scores, sample_stride, step_stride, batch, steps, classes, normalized, beam, paths, lengths,
+                                          hyp_scores, shape, lm != nullptr, ccd::CtcBeamLm{lm, order, eos, (double)weight, (double)bonus},
+                                          ccd::CtcBeamTrie{}, stream);
 }
 int ccd_ctc_beam_search_trie(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
                              int beam, const int* nodes, int n_nodes, int* paths, int* lengths, float* hyp_scores, int* word_ids,
                              void* stream) {
-    CCD_CHECK(batch >= 0 && sample_stride >= 0 && step_stride >= 0, CCD_EINVAL);
-    CCD_CHECK(beam >= 1 && beam <= ccd::CTC_MAX_BEAM && steps >= 1 && steps <= ccd::CTC_MAX_T && classes >= 2 && classes <= ccd::CTC_MAX_C &&
-              (normalized == 0 || normalized == 1) && n_nodes >= 1, CCD_ESHAPE);
-    if (batch == 0) return CCD_OK;
-    CCD_CHECK(scores && nodes && paths && lengths && hyp_scores && word_ids, CCD_EINVAL);
-    CCD_LAUNCH(ccd::ctc_beam_kernel<ccd::CTC_BEAM_TRIE>, dim3((unsigned)((batch + ccd::CTC_WAVES - 1) / ccd::CTC_WAVES)),
-               dim3(ccd::CTC_THREADS), 0, stream, scores, sample_stride, step_stride, batch, steps, classes, normalized, beam, paths, lengths,
-               hyp_scores, ccd::CtcBeamLm{}, ccd::CtcBeamTrie{nodes, n_nodes, word_ids});
-    return ccd_rt_last_error();
+    return ccd_ctc_beam<ccd::CTC_BEAM_TRIE>(scores, sample_stride, step_stride, batch, steps, classes, normalized, beam, paths, lengths,
+                                            hyp_scores, n_nodes >= 1, nodes && word_ids, ccd::CtcBeamLm{}, ccd::CtcBeamTrie{nodes, n_nodes, word_ids},
+                                            stream);
 }
 
 int ccd_ctc_lexicon_score(const float* scores, long sample_stride, long step_stride, int batch, int steps, int classes, int normalized,
@@ -1510,15 +1506,26 @@ int ccd_ctc_align(const float* scores, long sample_stride, long step_stride, int
     return ccd_rt_last_error();
 }
 
-int ccd_nrtr_beam_step(const float* logits, long ldl, int batch, int beam, int classes, int step, int end_idx, int pad_idx, int64_t* seq,
-                       int seq_len, double* score, int* state, int* parent, int* paths, int* lengths, float* hyp_scores, void* stream) {
+// The contract the three NRTR step entry points share, in the order of its return codes: `own_shape` and `own_pointers` are the
+// clauses of the caller's mode, `own_output` the output that comes and goes with the paths (the plain step: the paths themselves).
+// CCD_OK: go on, unless batch == 0.
+static int ccd_nrtr_step_check(const void* logits, long ldl, int batch, int beam, int classes, int step, int end_idx, int pad_idx,
+                               const void* seq, int seq_len, const void* score, const void* state, const void* parent, const void* paths,
+                               const void* lengths, const void* hyp_scores, const void* own_output, bool own_shape, bool own_pointers) {
     CCD_CHECK(batch >= 0 && ldl >= 0 && step >= 0, CCD_EINVAL);
     CCD_CHECK(beam >= 1 && beam <= ccd::NRTR_MAX_BEAM && classes >= 1 && classes <= ccd::NRTR_MAX_C && ldl >= classes && seq_len >= 2 &&
-              seq_len <= ccd::NRTR_MAX_LEN && step + 2 <= seq_len && end_idx >= 0 && end_idx < classes && pad_idx >= 0 && pad_idx < 65536,
-              CCD_ESHAPE);
+              seq_len <= ccd::NRTR_MAX_LEN && step + 2 <= seq_len && end_idx >= 0 && end_idx < classes && pad_idx >= 0 && pad_idx < 65536 &&
+              own_shape, CCD_ESHAPE);
     if (batch == 0) return CCD_OK;
-    CCD_CHECK(logits && seq && score && state && parent, CCD_EINVAL);
-    CCD_CHECK((paths && lengths && hyp_scores) || (!paths && !lengths && !hyp_scores), CCD_EINVAL);
+    CCD_CHECK(logits && seq && score && state && parent && own_pointers, CCD_EINVAL);
+    CCD_CHECK((paths && lengths && hyp_scores && own_output) || (!paths && !lengths && !hyp_scores && !own_output), CCD_EINVAL);
+    return CCD_OK;
+}
+int ccd_nrtr_beam_step(const float* logits, long ldl, int batch, int beam, int classes, int step, int end_idx, int pad_idx, int64_t* seq,
+                       int seq_len, double* score, int* state, int* parent, int* paths, int* lengths, float* hyp_scores, void* stream) {
+    const int rc = ccd_nrtr_step_check(logits, ldl, batch, beam, classes, step, end_idx, pad_idx, seq, seq_len, score, state, parent, paths,
+                                       lengths, hyp_scores, paths, true, true);
+    if (rc != CCD_OK || batch == 0) return rc;
     CCD_LAUNCH(ccd::nrtr_beam_step_kernel<false>, dim3((unsigned)batch), dim3(64), 0, stream, logits, ldl, beam, classes, step, end_idx,
                pad_idx, reinterpret_cast<long long*>(seq), seq_len, score, state, parent, paths, lengths, hyp_scores, ccd::NrtrBeamTrie{});
     return ccd_rt_last_error();
@@ -1526,13 +1533,9 @@ int ccd_nrtr_beam_step(const float* logits, long ldl, int batch, int beam, int c
 int ccd_nrtr_beam_step_trie(const float* logits, long ldl, int batch, int beam, int classes, int step, int end_idx, int pad_idx,
                             int64_t* seq, int seq_len, double* score, int* state, int* parent, int* paths, int* lengths,
                             float* hyp_scores, const int* nodes, int n_nodes, int class_offset, int* node, int* word_ids, void* stream) {
-    CCD_CHECK(batch >= 0 && ldl >= 0 && step >= 0, CCD_EINVAL);
-    CCD_CHECK(beam >= 1 && beam <= ccd::NRTR_MAX_BEAM && classes >= 1 && classes <= ccd::NRTR_MAX_C && ldl >= classes && seq_len >= 2 &&
-              seq_len <= ccd::NRTR_MAX_LEN && step + 2 <= seq_len && end_idx >= 0 && end_idx < classes && pad_idx >= 0 && pad_idx < 65536 &&
-              n_nodes >= 1 && class_offset >= 0 && class_offset <= 1, CCD_ESHAPE);
-    if (batch == 0) return CCD_OK;
-    CCD_CHECK(logits && seq && score && state && parent && nodes && node, CCD_EINVAL);
-    CCD_CHECK((paths && lengths && hyp_scores && word_ids) || (!paths && !lengths && !hyp_scores && !word_ids), CCD_EINVAL);
+    const int rc = ccd_nrtr_step_check(logits, ldl, batch, beam, classes, step, end_idx, pad_idx, seq, seq_len, score, state, parent, paths,
+                                       lengths, hyp_scores, word_ids, n_nodes >= 1 && class_offset >= 0 && class_offset <= 1, nodes && node);
+    if (rc != CCD_OK || batch == 0) return rc;
     CCD_LAUNCH(ccd::nrtr_beam_step_kernel<true>, dim3((unsigned)batch), dim3(64), 0, stream, logits, ldl, beam, classes, step, end_idx,
                pad_idx, reinterpret_cast<long long*>(seq), seq_len, score, state, parent, paths, lengths, hyp_scores,
                ccd::NrtrBeamTrie{nodes, n_nodes, class_offset, node, word_ids});
@@ -1553,14 +1556,11 @@ int ccd_nrtr_beam_step_joint(const float* logits, long ldl, int batch, int beam,
                              int64_t* seq, int seq_len, double* score, int* state, int* parent, int* paths, int* lengths,
                              float* hyp_scores, const double* log_probs, int ctc_steps, int ctc_classes, int class_offset, double weight,
                              double* prefix, double* att, float* att_scores, void* stream) {
-    CCD_CHECK(batch >= 0 && ldl >= 0 && step >= 0, CCD_EINVAL);
-    CCD_CHECK(beam >= 1 && beam <= ccd::NRTR_MAX_BEAM && classes >= 1 && classes <= ccd::NRTR_MAX_C && ldl >= classes && seq_len >= 2 &&
-              seq_len <= ccd::NRTR_MAX_LEN && step + 2 <= seq_len && end_idx >= 0 && end_idx < classes && pad_idx >= 0 && pad_idx < 65536 &&
-              ctc_steps >= 1 && ctc_steps <= ccd::NRTR_JOINT_MAX_T && ctc_classes >= 1 && ctc_classes <= ccd::NRTR_MAX_C &&
-              class_offset >= 0 && class_offset <= 1 && weight >= 0.0 && weight <= 1.0, CCD_ESHAPE);      // (a NaN weight fails both)
-    if (batch == 0) return CCD_OK;
-    CCD_CHECK(logits && seq && score && state && parent && log_probs && prefix && att, CCD_EINVAL);
-    CCD_CHECK((paths && lengths && hyp_scores && att_scores) || (!paths && !lengths && !hyp_scores && !att_scores), CCD_EINVAL);
+    const bool shape = ctc_steps >= 1 && ctc_steps <= ccd::NRTR_JOINT_MAX_T && ctc_classes >= 1 && ctc_classes <= ccd::NRTR_MAX_C &&
+                       class_offset >= 0 && class_offset <= 1 && weight >= 0.0 && weight <= 1.0;             // (a NaN weight fails both)
+    const int rc = ccd_nrtr_step_check(logits, ldl, batch, beam, classes, step, end_idx, pad_idx, seq, seq_len, score, state, parent, paths,
+                                       lengths, hyp_scores, att_scores, shape, log_probs && prefix && att);
+    if (rc != CCD_OK || batch == 0) return rc;
     CCD_LAUNCH(ccd::nrtr_beam_step_joint_kernel, dim3((unsigned)batch), dim3(64), 0, stream, logits, ldl, beam, classes, step, end_idx,
                pad_idx, reinterpret_cast<long long*>(seq), seq_len, score, state, parent, paths, lengths, hyp_scores,
                ccd::NrtrJoint{log_probs, ctc_steps, ctc_classes, class_offset, weight, prefix, att, att_scores});

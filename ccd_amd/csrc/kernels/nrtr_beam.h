@@ -20,7 +20,9 @@
 //   3. W rounds of the wave arg-max of beam_wave.h over the table; the owner of the winner overwrites it with -inf.  Lane r keeps
 //      rank r;
 //   4. the new rows: positions 0..step from the parent's row in LDS, position step + 1 the new token; score, state, parent by lane r.
-// Every loop that shuffles has a wave-uniform trip count (W, the slots).  fp64 throughout (ctc_real).
+// Every loop that shuffles has a wave-uniform trip count (W, the slots).  fp64 throughout (ctc_real).  Phases 1, 3 and 4 and the
+// finished slot of phase 2 are nrtr_beam_stage / _select / _store / _carry below: one copy for this kernel, its trie instance and the
+// joint kernel of nrtr_joint.h.
 //
 // Beam search over a lexicon's prefix tree (ccd_nrtr_beam_step_trie, nrtr_beam_step_kernel<true>; tests/nrtr_trie_np.py is the
 // specification): the same kernel - `template <bool kTrie>`, whose `false` instance is the code above and nothing else - with a trie
@@ -38,8 +40,9 @@
 // six-word record of that node (ctc_trie_fetch: one 24-byte request per slot and step, next to the score and the state) and parks
 // the mask as two 64-bit words, first_child, word_id and the node in LDS - 28 B per slot, 448 B beside the 20.2 KB above.  Phase 2
 // reads the two mask words of slot r at a wave-uniform address (a broadcast) and writes -inf instead of the sum where the lane's bit
-// is clear.  In phase 3 lane r derives its new node from the winner's record, which still stands; a slot that finishes takes the word
-// id from there too, so the last step needs no second fetch.  The cost is a beam step's, whatever the size of the lexicon.
+// is clear.  Behind phase 3 lane r derives its new node from the record of its winner's parent, which still stands (the selection
+// overwrites candidates only); a slot that finishes takes the word id from there too, so the last step needs no second fetch.  The
+// cost is a beam step's, whatever the size of the lexicon.
 //
 // Reorder kernel: pure data movement.  One thread owns the same 16-byte piece of the K | V columns of one (layer, sample, position)
 // in all W rows: it loads the piece of row parent[r] for every r whose parent differs (compile-time register index r, the gather is
@@ -71,6 +74,8 @@ struct NrtrBeamTrieWave<true> {
     int node[NRTR_MAX_BEAM], first[NRTR_MAX_BEAM], word[NRTR_MAX_BEAM];    // the node of slot r, its first child, the word that ends there
 };
 
+static_assert(sizeof(NrtrBeamWave) == 20672 && sizeof(NrtrBeamTrieWave<true>) == 448, "the LDS layout of the step kernels is fixed");
+
 struct NrtrBeamTrie {                                              // the lexicon trie of a launch (unused without one)
     const int* nodes;                                              // int32 [n_nodes, 8]: ccd_ctc_beam_search_trie's table
     int n_nodes, class_offset;                                     // class c of the decoder is bit c + class_offset of a mask
@@ -83,24 +88,17 @@ __device__ __forceinline__ bool nrtr_trie_bit(unsigned long long m0, unsigned lo
     return k <= 127 && (((k < 64 ? m0 >> k : m1 >> (k - 64)) & 1ull) != 0ull);
 }
 
-// grid = B, block = 64.  The launcher has checked 1 <= W <= 16, 1 <= C <= 128, 0 <= step, step + 2 <= seq_len <= 128, end_idx in
-// [0, C), pad_idx in [0, 65536).  paths / lengths / hyp_scores: all three or none.  Every line the trie adds sits behind `if constexpr
-// (kTrie)` (`trie` is not looked at without one; with one the launcher has checked n_nodes >= 1, class_offset in {0, 1}, and word_ids
-// comes with the paths): the `false` instance is the kernel as it was.
-template <bool kTrie>
-__global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restrict__ logits, long ldl, int W, int C, int step, int end_idx,
-                                                            int pad_idx, long long* seq, int seq_len, ctc_real* score, int* state,
-                                                            int* __restrict__ parent, int* __restrict__ paths, int* __restrict__ lengths,
-                                                            float* __restrict__ hyp_scores, NrtrBeamTrie trie) {
-    __shared__ NrtrBeamWave s;
-    __shared__ NrtrBeamTrieWave<kTrie> tr;
-    const int lane = lane_id(), b = blockIdx.x;
-    const int c0 = lane, c1 = lane + 64;
-    const bool has0 = c0 < C, has1 = c1 < C;
-    const long row0 = (long)b * W;
-    const float ninf = -__builtin_inff();
+// ---- the parts every step kernel runs (the two instances below, nrtr_joint.h's nrtr_beam_step_joint_kernel): ALL 64 LANES CALL THEM,
+// the `__shared__` table comes by reference.  They keep the contracts of the decoder in one place: the tie rule, "a lane only stores
+// what it loaded", wave-uniform trip counts (W) around every shuffle and ballot, fp64 compared and never re-rounded (the operation
+// order of a score is the caller's, under -ffp-contract=off), registers and LDS only - nothing here indexes a private array.  None
+// of them fences on entry or exit: the fences between the phases stay in the kernels, next to the staging and the candidates a
+// kernel adds of its own; the one fence inside, behind every round of the selection, orders the knock-out against the next scan.
 
-    // ---- 1. the old state
+// Phase 1: lane r < W parks score and state of slot r; every lane stages its positions (<= step) of the W token rows as 16-bit.
+__device__ __forceinline__ void nrtr_beam_stage(NrtrBeamWave& s, const long long* seq, int seq_len, const ctc_real* score, const int* state,
+                                                long row0, int W, int step) {
+    const int lane = lane_id(), c0 = lane, c1 = lane + 64;
     ctc_real my_score = ctc_neg_inf();
     int my_state = NRTR_UNUSED;
     if (lane < W) {
@@ -111,58 +109,33 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restr
         s.score[lane] = my_score;
         s.state[lane] = my_state;
     }
-    if constexpr (kTrie) {
-        int rec[CTC_TRIE_RECORD] = {0, 0, 0, 0, 0, -1}, my_node = 0;       // (a slot behind W: no edge, no word)
-        if (lane < W) {
-            const int n = trie.node[row0 + lane];
-            my_node = n < 0 ? 0 : (n >= trie.n_nodes ? trie.n_nodes - 1 : n);
-            ctc_trie_fetch(trie.nodes, my_node, rec);
-        }
-        if (lane < NRTR_MAX_BEAM) {
-            tr.allow[lane][0] = (unsigned long long)(unsigned)rec[0] | ((unsigned long long)(unsigned)rec[1] << 32);
-            tr.allow[lane][1] = (unsigned long long)(unsigned)rec[2] | ((unsigned long long)(unsigned)rec[3] << 32);
-            tr.first[lane] = rec[4];
-            tr.word[lane] = rec[5];
-            tr.node[lane] = my_node;
-        }
-    }
     for (int r = 0; r < W; ++r) {
         const long long* const q = seq + (row0 + r) * seq_len;
         if (c0 <= step) s.tok[r][c0] = (unsigned short)q[c0];
         if (c1 <= step) s.tok[r][c1] = (unsigned short)q[c1];
     }
-    wave_lds_fence();
+}
 
-    // ---- 2. the candidates
-    for (int r = 0; r < W; ++r) {
-        const int st = s.state[r];                                         // wave-uniform
-        const ctc_real sc = s.score[r];
-        if (st == NRTR_LIVE) {
-            const float* const x = logits + (row0 + r) * ldl;
-            const CtcReal2 lp = beam_wave_log_probs(has0 ? x[c0] : ninf, has1 ? x[c1] : ninf, has0, has1, false, s.cand[r], C);
-            if constexpr (kTrie) {                                         // an extension the trie has no edge for, an end where no
-                const unsigned long long m0 = tr.allow[r][0], m1 = tr.allow[r][1];             // word ends: no candidate
-                const bool word = tr.word[r] >= 0;
-                const bool ok0 = c0 == end_idx ? word : nrtr_trie_bit(m0, m1, c0 + trie.class_offset);
-                const bool ok1 = c1 == end_idx ? word : nrtr_trie_bit(m0, m1, c1 + trie.class_offset);
-                if (has0) s.cand[r][c0] = ok0 ? sc + lp.c0 : ctc_neg_inf();
-                if (has1) s.cand[r][c1] = ok1 ? sc + lp.c1 : ctc_neg_inf();
-            } else {
-                if (has0) s.cand[r][c0] = sc + lp.c0;                      // (-inf stays -inf: a score is finite or -inf)
-                if (has1) s.cand[r][c1] = sc + lp.c1;
-            }
-        } else {
-            const bool carry = st == NRTR_FINISHED;
-            if (has0) s.cand[r][c0] = carry && c0 == end_idx ? sc : ctc_neg_inf();
-            if (has1) s.cand[r][c1] = carry && c1 == end_idx ? sc : ctc_neg_inf();
-        }
-    }
-    wave_lds_fence();
+// Phase 2, a slot that is not live (state st, score sc): a finished one offers (r, end_idx) alone, an unused one nothing.
+__device__ __forceinline__ void nrtr_beam_carry(ctc_real* cand, int st, ctc_real sc, int end_idx, int C) {
+    const int c0 = lane_id(), c1 = c0 + 64;
+    const bool carry = st == NRTR_FINISHED;
+    if (c0 < C) cand[c0] = carry && c0 == end_idx ? sc : ctc_neg_inf();
+    if (c1 < C) cand[c1] = carry && c1 == end_idx ? sc : ctc_neg_inf();
+}
 
-    // ---- 3. the W best, one per round; lane r keeps the slot of rank r
-    ctc_real new_score = ctc_neg_inf();
-    int new_state = NRTR_UNUSED, new_parent = -1, new_tok = pad_idx;
-    int new_node = 0, new_word = -1;                                       // kTrie: the node of the new slot; its word, if it has finished
+struct NrtrBeamPick {                                              // what lane r knows about the winner of rank r
+    ctc_real score;                                                // -inf, unused, -1, 0, pad_idx: there was none
+    int state, parent, c, tok;                                     // the winner is candidate (parent, c) of the table
+};
+
+// Phase 3: the W best of s.cand, one per round; lane r keeps rank r.  Only s.cand is overwritten (fenced after every round), so what
+// a kernel parked per slot or per candidate beside it still stands afterwards: the mode-specific follow-ups read it out of
+// (pick.parent, pick.c) behind the call.
+__device__ __forceinline__ NrtrBeamPick nrtr_beam_select(NrtrBeamWave& s, int W, int C, int end_idx, int pad_idx) {
+    const int lane = lane_id(), c0 = lane, c1 = lane + 64;
+    const bool has0 = c0 < C, has1 = c1 < C;
+    NrtrBeamPick pick = {ctc_neg_inf(), NRTR_UNUSED, -1, 0, pad_idx};
     for (int r = 0; r < W; ++r) {
         ctc_real best = ctc_neg_inf();
         int best_k = 0x7fffffff;
@@ -188,38 +161,34 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restr
             if (lane == (c & 63)) s.cand[i][c] = ctc_neg_inf();            // (only this lane ever reads the entry again)
             if (lane == r) {
                 const bool was_finished = s.state[i] == NRTR_FINISHED;
-                new_score = best;
-                new_parent = i;
-                new_state = was_finished || c == end_idx ? NRTR_FINISHED : NRTR_LIVE;
-                new_tok = was_finished ? pad_idx : c;
-                if constexpr (kTrie) {                                     // the parent's record, which phase 1 left standing
-                    if (new_state == NRTR_FINISHED) {
-                        new_node = tr.node[i];
-                        new_word = tr.word[i];
-                    } else {
-                        const int child = ctc_trie_child(tr.first[i], tr.allow[i][0], tr.allow[i][1], c + trie.class_offset);
-                        new_node = child < 0 ? 0 : (child >= trie.n_nodes ? trie.n_nodes - 1 : child);
-                    }
-                }
+                pick.score = best;
+                pick.parent = i;
+                pick.c = c;
+                pick.state = was_finished || c == end_idx ? NRTR_FINISHED : NRTR_LIVE;
+                pick.tok = was_finished ? pad_idx : c;
             }
         }
         wave_lds_fence();
     }
+    return pick;
+}
 
-    // ---- 4. the new state, in place: a lane stores what it loaded in phase 1 (positions) or owns (slot `lane`)
+// Phase 4, in place: score, state, parent (and hyp_scores) of slot `lane` by lane < W, then the W rows - positions 0..step from the
+// parent's row in LDS, position step + 1 the new token.  A lane stores the positions it loaded in nrtr_beam_stage and nothing else,
+// which is what makes one buffer enough.  paths / lengths (all or none, with hyp_scores): the n-best lists.
+__device__ __forceinline__ void nrtr_beam_store(const NrtrBeamWave& s, const NrtrBeamPick& pick, long long* seq, int seq_len, ctc_real* score,
+                                                int* state, int* __restrict__ parent, int* __restrict__ paths, int* __restrict__ lengths,
+                                                float* __restrict__ hyp_scores, long row0, int W, int step, int end_idx) {
+    const int lane = lane_id(), c0 = lane, c1 = lane + 64;
     if (lane < W) {
-        score[row0 + lane] = new_score;
-        state[row0 + lane] = new_state;
-        parent[row0 + lane] = new_parent;
-        if (hyp_scores) hyp_scores[row0 + lane] = new_state == NRTR_UNUSED ? ninf : (float)new_score;
-        if constexpr (kTrie) {
-            trie.node[row0 + lane] = new_node;
-            if (paths) trie.word_ids[row0 + lane] = new_word;              // (a live or an unused slot is no word: -1)
-        }
+        score[row0 + lane] = pick.score;
+        state[row0 + lane] = pick.state;
+        parent[row0 + lane] = pick.parent;
+        if (hyp_scores) hyp_scores[row0 + lane] = pick.state == NRTR_UNUSED ? -__builtin_inff() : (float)pick.score;
     }
     const int T = seq_len - 1;
     for (int r = 0; r < W; ++r) {
-        const int p = shfl(new_parent, r), tk = shfl(new_tok, r);          // wave-uniform
+        const int p = shfl(pick.parent, r), tk = shfl(pick.tok, r);        // wave-uniform
         long long* const q = seq + (row0 + r) * seq_len;
         int t0 = -1, t1 = -1;                                              // the new row's tokens at this lane's positions
         if (p >= 0) {
@@ -245,6 +214,90 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restr
             if (lane == 0) lengths[row0 + r] = len;
         }
     }
+}
+
+// grid = B, block = 64.  The launcher has checked 1 <= W <= 16, 1 <= C <= 128, 0 <= step, step + 2 <= seq_len <= 128, end_idx in
+// [0, C), pad_idx in [0, 65536).  paths / lengths / hyp_scores: all three or none.  Every line the trie adds sits behind `if constexpr
+// (kTrie)` (`trie` is not looked at without one; with one the launcher has checked n_nodes >= 1, class_offset in {0, 1}, and word_ids
+// comes with the paths): the `false` instance is the four shared parts, its own live candidates and nothing else.
+template <bool kTrie>
+__global__ __launch_bounds__(64) void nrtr_beam_step_kernel(const float* __restrict__ logits, long ldl, int W, int C, int step, int end_idx,
+                                                            int pad_idx, long long* seq, int seq_len, ctc_real* score, int* state,
+                                                            int* __restrict__ parent, int* __restrict__ paths, int* __restrict__ lengths,
+                                                            float* __restrict__ hyp_scores, NrtrBeamTrie trie) {
+    __shared__ NrtrBeamWave s;
+    __shared__ NrtrBeamTrieWave<kTrie> tr;
+    const int lane = lane_id(), b = blockIdx.x;
+    const int c0 = lane, c1 = lane + 64;
+    const bool has0 = c0 < C, has1 = c1 < C;
+    const long row0 = (long)b * W;
+    const float ninf = -__builtin_inff();
+
+    // ---- 1. the old state
+    nrtr_beam_stage(s, seq, seq_len, score, state, row0, W, step);
+    if constexpr (kTrie) {
+        int rec[CTC_TRIE_RECORD] = {0, 0, 0, 0, 0, -1}, my_node = 0;       // (a slot behind W: no edge, no word)
+        if (lane < W) {
+            const int n = trie.node[row0 + lane];
+            my_node = n < 0 ? 0 : (n >= trie.n_nodes ? trie.n_nodes - 1 : n);
+            ctc_trie_fetch(trie.nodes, my_node, rec);
+        }
+        if (lane < NRTR_MAX_BEAM) {
+            tr.allow[lane][0] = (unsigned long long)(unsigned)rec[0] | ((unsigned long long)(unsigned)rec[1] << 32);
+            tr.allow[lane][1] = (unsigned long long)(unsigned)rec[2] | ((unsigned long long)(unsigned)rec[3] << 32);
+            tr.first[lane] = rec[4];
+            tr.word[lane] = rec[5];
+            tr.node[lane] = my_node;
+        }
+    }
+    wave_lds_fence();
+
+    // ---- 2. the candidates
+    for (int r = 0; r < W; ++r) {
+        const int st = s.state[r];                                         // wave-uniform
+        const ctc_real sc = s.score[r];
+        if (st == NRTR_LIVE) {
+            const float* const x = logits + (row0 + r) * ldl;
+            const CtcReal2 lp = beam_wave_log_probs(has0 ? x[c0] : ninf, has1 ? x[c1] : ninf, has0, has1, false, s.cand[r], C);
+            if constexpr (kTrie) {                                         // an extension the trie has no edge for, an end where no
+                const unsigned long long m0 = tr.allow[r][0], m1 = tr.allow[r][1];             // word ends: no candidate
+                const bool word = tr.word[r] >= 0;
+                const bool ok0 = c0 == end_idx ? word : nrtr_trie_bit(m0, m1, c0 + trie.class_offset);
+                const bool ok1 = c1 == end_idx ? word : nrtr_trie_bit(m0, m1, c1 + trie.class_offset);
+                if (has0) s.cand[r][c0] = ok0 ? sc + lp.c0 : ctc_neg_inf();
+                if (has1) s.cand[r][c1] = ok1 ? sc + lp.c1 : ctc_neg_inf();
+            } else {
+                if (has0) s.cand[r][c0] = sc + lp.c0;                      // (-inf stays -inf: a score is finite or -inf)
+                if (has1) s.cand[r][c1] = sc + lp.c1;
+            }
+        } else {
+            nrtr_beam_carry(s.cand[r], st, sc, end_idx, C);
+        }
+    }
+    wave_lds_fence();
+
+    // ---- 3. the W best, one per round; lane r keeps the slot of rank r
+    const NrtrBeamPick pick = nrtr_beam_select(s, W, C, end_idx, pad_idx);
+
+    // ---- 4. the new state, in place: a lane stores what it loaded in phase 1 (positions) or owns (slot `lane`)
+    if constexpr (kTrie) {
+        int new_node = 0, new_word = -1;                                   // the node of the new slot; its word, if it has finished
+        if (pick.parent >= 0) {                                            // the parent's record, which phase 1 left standing
+            const int i = pick.parent;
+            if (pick.state == NRTR_FINISHED) {
+                new_node = tr.node[i];
+                new_word = tr.word[i];
+            } else {
+                const int child = ctc_trie_child(tr.first[i], tr.allow[i][0], tr.allow[i][1], pick.c + trie.class_offset);
+                new_node = child < 0 ? 0 : (child >= trie.n_nodes ? trie.n_nodes - 1 : child);
+            }
+        }
+        if (lane < W) {
+            trie.node[row0 + lane] = new_node;
+            if (paths) trie.word_ids[row0 + lane] = new_word;              // (a live or an unused slot is no word: -1)
+        }
+    }
+    nrtr_beam_store(s, pick, seq, seq_len, score, state, parent, paths, lengths, hyp_scores, row0, W, step, end_idx);
 }
 
 // One thread per 16-byte piece of the K | V columns of (layer, sample, position <= step): total = L * B * (step + 1) * chunks threads,

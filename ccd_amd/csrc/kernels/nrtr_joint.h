@@ -17,16 +17,20 @@
 //              A finished slot gives (r, end_idx) with S and A unchanged.  Selection, ties, tokens, parents, states: nrtr_beam.h's, on S.
 //              A selected extension takes (n, b) as its prefix state, everything else keeps its parent's; an unused slot holds -inf.
 //
-// Step kernel: ONE WAVEFRONT PER SAMPLE, its own kernel beside nrtr_beam_step_kernel (whose two instances stay as they are), on the
-// primitives of beam_wave.h.  Lane l owns the classes l and l + 64, the positions l and l + 64 of a sequence, and frame l of a state.
-//   1. nrtr_beam.h's staging, and the W parents' prefix states (lane t loads rn[t], rb[t] of every slot: W * 2 * Tc * 8 B <= 16 KB) and
+// Step kernel: ONE WAVEFRONT PER SAMPLE, a kernel of its own beside nrtr_beam_step_kernel - NrtrJointWave is LDS the two instances
+// there never allocate.  What the three share is called, not copied: nrtr_beam.h's nrtr_beam_stage, _carry, _select and _store, which
+// hold the tie rule, the in-place update and the n-best lists.  Its own are the CTC parts of the phases below.  Lane l owns the
+// classes l and l + 64, the positions l and l + 64 of a sequence, and frame l of a state.
+//   1. nrtr_beam_stage, and the W parents' prefix states (lane t loads rn[t], rb[t] of every slot: W * 2 * Tc * 8 B <= 16 KB) and
 //      attention scores: phase 4 overwrites `prefix` and `att` in place, after every load of the wave has landed in LDS.
 //   2. per live slot: la by beam_wave_log_probs; lane t prepares phi[t] of the slot in both variants (k == last, k != last) in LDS;
 //      then every lane runs the Tc frames for its two classes: phi[t] read at a wave-uniform address (both variants, a select picks),
 //      lp[t, k] from the workspace, coalesced across the lanes.  Two passes (the maximum, then the sum of exp in ascending t): one
-//      exp per term.  The joint score goes to the candidate table, the attention part to a second table of the same shape.
-//   3. nrtr_beam.h's selection over S; lane r also takes the attention part of its winner.
-//   4. lane r < W runs the Tc-step recursion of its new slot from the parent's staged state (or copies it) and stores it, with att.
+//      exp per term.  The joint score goes to the candidate table, the attention part to a second table of the same shape.  A slot
+//      that is not live: nrtr_beam_carry, its attention score in the second table.
+//   3. nrtr_beam_select over S; lane r then takes the attention part of its winner (i, c) from the second table, which stands.
+//   4. lane r < W runs the Tc-step recursion of its new slot from the parent's staged state (or copies it) and stores it, with att;
+//      nrtr_beam_store does the rest.
 // Loops that shuffle run over W or have none inside (the frame loops are lane-local, trip count Tc); fp64 throughout.  LDS: 20.2 KB
 // (nrtr_beam.h) + 16 KB attention parts + 16 KB staged states + 1.2 KB = 53.6 KB.
 #pragma once
@@ -43,6 +47,7 @@ struct NrtrJointWave {
     ctc_real att[NRTR_MAX_BEAM];
     ctc_real phi[2][NRTR_JOINT_MAX_T];                             // of the slot at hand: [0] k != last, [1] k == last
 };
+static_assert(sizeof(NrtrJointWave) == 33920, "with NrtrBeamWave: 54 592 B of LDS, the layout is fixed");
 
 struct NrtrJoint {
     const ctc_real* lp;                                            // fp64 [B, Tc, Cc]: ccd_nrtr_joint_begin's workspace
@@ -125,23 +130,10 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_joint_kernel(const float* _
     ctc_real* const prefix = j.prefix + row0 * 2 * Tc;
 
     // ---- 1. the old state
-    ctc_real my_score = ctc_neg_inf(), my_att = ctc_neg_inf();
-    int my_state = NRTR_UNUSED;
-    if (lane < W) {
-        my_score = score[row0 + lane];
-        my_state = state[row0 + lane];
-        my_att = j.att[row0 + lane];
-    }
-    if (lane < NRTR_MAX_BEAM) {
-        s.score[lane] = my_score;
-        s.state[lane] = my_state;
-        jw.att[lane] = my_att;
-    }
-    for (int r = 0; r < W; ++r) {
-        const long long* const q = seq + (row0 + r) * seq_len;
-        if (c0 <= step) s.tok[r][c0] = (unsigned short)q[c0];
-        if (c1 <= step) s.tok[r][c1] = (unsigned short)q[c1];
-        if (lane < Tc) {
+    nrtr_beam_stage(s, seq, seq_len, score, state, row0, W, step);
+    if (lane < NRTR_MAX_BEAM) jw.att[lane] = lane < W ? j.att[row0 + lane] : ctc_neg_inf();
+    if (lane < Tc) {
+        for (int r = 0; r < W; ++r) {
             jw.pre[r][0][lane] = prefix[(long)r * 2 * Tc + lane];
             jw.pre[r][1][lane] = prefix[(long)r * 2 * Tc + Tc + lane];
         }
@@ -188,70 +180,24 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_joint_kernel(const float* _
                 jw.attc[r][c1] = a1;
             }
         } else {
-            const bool carry = st == NRTR_FINISHED;
-            if (has0) {
-                s.cand[r][c0] = carry && c0 == end_idx ? sc : ctc_neg_inf();
-                jw.attc[r][c0] = at;
-            }
-            if (has1) {
-                s.cand[r][c1] = carry && c1 == end_idx ? sc : ctc_neg_inf();
-                jw.attc[r][c1] = at;
-            }
+            nrtr_beam_carry(s.cand[r], st, sc, end_idx, C);
+            if (has0) jw.attc[r][c0] = at;
+            if (has1) jw.attc[r][c1] = at;
         }
     }
     wave_lds_fence();
 
-    // ---- 3. the W best, one per round; lane r keeps the slot of rank r
-    ctc_real new_score = ctc_neg_inf(), new_att = ctc_neg_inf();
-    int new_state = NRTR_UNUSED, new_parent = -1, new_tok = pad_idx;
-    for (int r = 0; r < W; ++r) {
-        ctc_real best = ctc_neg_inf();
-        int best_k = 0x7fffffff;
-        for (int i = 0; i < W; ++i) {                                      // k ascends along the scan: `>` keeps the lowest k of equals
-            if (has0) {
-                const ctc_real v = s.cand[i][c0];
-                if (v > best) {
-                    best = v;
-                    best_k = i * C + c0;
-                }
-            }
-            if (has1) {
-                const ctc_real v = s.cand[i][c1];
-                if (v > best) {
-                    best = v;
-                    best_k = i * C + c1;
-                }
-            }
-        }
-        beam_wave_best(best, best_k);
-        if (best > ctc_neg_inf()) {                                        // wave-uniform: every lane holds the same winner
-            const int i = best_k / C, c = best_k - i * C;
-            if (lane == (c & 63)) s.cand[i][c] = ctc_neg_inf();            // (only this lane ever reads the entry again)
-            if (lane == r) {
-                const bool was_finished = s.state[i] == NRTR_FINISHED;
-                new_score = best;
-                new_att = jw.attc[i][c];
-                new_parent = i;
-                new_state = was_finished || c == end_idx ? NRTR_FINISHED : NRTR_LIVE;
-                new_tok = was_finished ? pad_idx : c;
-            }
-        }
-        wave_lds_fence();
-    }
+    // ---- 3. the W best by S; the attention part of lane r's winner still stands in the second table
+    const NrtrBeamPick pick = nrtr_beam_select(s, W, C, end_idx, pad_idx);
+    const ctc_real new_att = pick.parent >= 0 ? jw.attc[pick.parent][pick.c] : ctc_neg_inf();
 
     // ---- 4. the new state, in place: the prefix states come from LDS, which holds every old one
     if (lane < W) {
-        score[row0 + lane] = new_score;
-        state[row0 + lane] = new_state;
-        parent[row0 + lane] = new_parent;
         j.att[row0 + lane] = new_att;
-        if (hyp_scores) {
-            hyp_scores[row0 + lane] = new_state == NRTR_UNUSED ? ninf : (float)new_score;
-            j.att_scores[row0 + lane] = new_state == NRTR_UNUSED ? ninf : (float)new_att;
-        }
-        const int p = new_parent < 0 ? 0 : new_parent;
-        const int k = new_tok + j.class_offset;
-        const bool extend = new_state == NRTR_LIVE, keep = new_state == NRTR_FINISHED;
+        if (hyp_scores) j.att_scores[row0 + lane] = pick.state == NRTR_UNUSED ? ninf : (float)new_att;
+        const int p = pick.parent < 0 ? 0 : pick.parent;
+        const int k = pick.tok + j.class_offset;
+        const bool extend = pick.state == NRTR_LIVE, keep = pick.state == NRTR_FINISHED;
         const bool known = extend && k < Cc;                               // (a class without a CTC class: -inf throughout)
         const bool same = step > 0 && k == (int)s.tok[p][step] + j.class_offset;
         const ctc_real* const lk = lp + (known ? k : 0);
@@ -270,34 +216,7 @@ __global__ __launch_bounds__(64) void nrtr_beam_step_joint_kernel(const float* _
             o[Tc + t] = keep ? rb : bl;
         }
     }
-    const int T = seq_len - 1;
-    for (int r = 0; r < W; ++r) {
-        const int p = shfl(new_parent, r), tk = shfl(new_tok, r);          // wave-uniform
-        long long* const q = seq + (row0 + r) * seq_len;
-        int t0 = -1, t1 = -1;                                              // the new row's tokens at this lane's positions
-        if (p >= 0) {
-            if (c0 <= step) t0 = s.tok[p][c0];
-            if (c1 <= step) t1 = s.tok[p][c1];
-            if (c0 == step + 1) t0 = tk;
-            if (c1 == step + 1) t1 = tk;
-            if (p != r) {
-                if (c0 <= step) q[c0] = t0;
-                if (c1 <= step) q[c1] = t1;
-            }
-        }
-        if (c0 == step + 1) q[c0] = tk;                                    // (an unused slot: padding_idx)
-        if (c1 == step + 1) q[c1] = tk;
-        if (paths) {                                                       // the classes in front of the first end_idx behind position 0
-            const bool e0 = p >= 0 && c0 >= 1 && c0 <= step + 1 && t0 == end_idx, e1 = p >= 0 && c1 <= step + 1 && t1 == end_idx;
-            const unsigned long long m0 = ballot(e0), m1 = ballot(e1);
-            const int first = m0 ? __builtin_ctzll(m0) : (m1 ? 64 + __builtin_ctzll(m1) : step + 2);
-            const int len = p >= 0 ? first - 1 : -1;
-            int* const o = paths + (row0 + r) * T;
-            if (c0 >= 1 && c0 <= T) o[c0 - 1] = c0 - 1 < len ? t0 : -1;
-            if (c1 <= T) o[c1 - 1] = c1 - 1 < len ? t1 : -1;
-            if (lane == 0) lengths[row0 + r] = len;
-        }
-    }
+    nrtr_beam_store(s, pick, seq, seq_len, score, state, parent, paths, lengths, hyp_scores, row0, W, step, end_idx);
 }
 
 }  // namespace ccd
