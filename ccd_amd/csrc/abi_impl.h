@@ -33,6 +33,7 @@
 #include "kernels/embed.h"
 #include "kernels/head.h"
 #include "kernels/loss.h"
+#include "kernels/seg_sup_loss.h"
 #include "kernels/sinkhorn.h"
 #include "kernels/headloss.h"
 #include "kernels/optim.h"
@@ -1814,6 +1815,48 @@ int ccd_seg_loss(const float* logits, const float* mask_a, const uint8_t* idmap_
     const long per_block = 256L * ccd::SEG_LOSS_PER_THREAD;
     CCD_LAUNCH(ccd::seg_loss_kernel, dim3((unsigned)((npix + per_block - 1) / per_block)), dim3(256), 0, stream, logits, mask_a, idmap_b,
                half, grad_scale, loss_out, d_logits);
+    return ccd_rt_last_error();
+}
+// the supervised segmentation loss (kernels/seg_sup_loss.h); every check comes before the first launch
+static_assert(CCD_SEG_SUP_MAX_PIXELS == ccd::SSL_MAX_PIX && CCD_SEG_SUP_MAX_RADIUS == ccd::SSL_MAX_R &&
+              CCD_SEG_SUP_WS_ROW == ccd::SSL_FIELDS && CCD_SEG_SUP_WS_TAIL == ccd::SSL_TAIL, "");
+static int ccd_seg_sup_check(const float* logits, long image_stride, long channel_stride, int channels, int images, int H, int W) {
+    CCD_CHECK(logits && image_stride >= 0 && channel_stride >= 0, CCD_EINVAL);
+    CCD_CHECK(channels == 2 && images >= 1 && H >= 1 && W >= 4 && W % 4 == 0 && (long)H * W <= ccd::SSL_MAX_PIX, CCD_ESHAPE);
+    CCD_CHECK(CCD_ALIGNED16(logits) && image_stride % 4 == 0 && channel_stride % 4 == 0, CCD_EINVAL);      // 16-byte loads along W
+    return CCD_OK;
+}
+long ccd_seg_sup_loss_ws_doubles(int images) {
+    return images < 1 ? 0 : (long)images * ccd::SSL_FIELDS + ccd::SSL_TAIL;
+}
+int ccd_seg_sup_loss_fwd(const float* logits, long image_stride, long channel_stride, int channels, const uint8_t* gt, long gt_stride,
+                         int images, int H, int W, int ignore_index, float weight_bg, float weight_text, float dice_weight,
+                         float edge_weight, int edge_radius, double* ws, uint8_t* code, float* loss, double* parts, long* confusion,
+                         void* stream) {
+    const int rc = ccd_seg_sup_check(logits, image_stride, channel_stride, channels, images, H, W);
+    if (rc != CCD_OK) return rc;
+    CCD_CHECK(gt && ws && loss && parts && confusion && gt_stride >= 0, CCD_EINVAL);
+    CCD_CHECK(edge_radius >= 0 && edge_radius <= ccd::SSL_MAX_R, CCD_ESHAPE);
+    CCD_CHECK(ignore_index >= 2 && ignore_index <= 255, CCD_EINVAL);               // 0 and 1 are the two classes
+    CCD_CHECK(weight_bg >= 0.f && weight_text >= 0.f && dice_weight >= 0.f && edge_weight >= 0.f, CCD_EINVAL);      // (a NaN fails too)
+    CCD_CHECK((((uintptr_t)ws) & 7u) == 0 && (((uintptr_t)parts) & 7u) == 0 && (((uintptr_t)confusion) & 7u) == 0 &&
+              (((uintptr_t)code) & 3u) == 0, CCD_EINVAL);
+    const int gvec = (((uintptr_t)gt) & 3u) == 0 && gt_stride % 4 == 0;
+    CCD_LAUNCH(ccd::seg_sup_loss_fwd_kernel, dim3((unsigned)images), dim3(ccd::SSL_THREADS), 0, stream, logits, image_stride, channel_stride,
+               gt, gt_stride, gvec, H, W, ignore_index, weight_bg, weight_text, edge_weight, edge_radius, ws, code);
+    CCD_LAUNCH(ccd::seg_sup_loss_finish_kernel, dim3(1), dim3(ccd::SSL_FIN_CHUNK), 0, stream, ws, images, dice_weight, loss, parts, confusion);
+    return ccd_rt_last_error();
+}
+int ccd_seg_sup_loss_bwd(const float* logits, long image_stride, long channel_stride, int channels, const uint8_t* code, int images,
+                         int H, int W, float weight_bg, float weight_text, float dice_weight, float edge_weight, const double* ws,
+                         float grad_scale, const float* d_grad, float* d_logits, void* stream) {
+    const int rc = ccd_seg_sup_check(logits, image_stride, channel_stride, channels, images, H, W);
+    if (rc != CCD_OK) return rc;
+    CCD_CHECK(code && ws && d_logits, CCD_EINVAL);
+    CCD_CHECK(CCD_ALIGNED16(d_logits) && (((uintptr_t)ws) & 7u) == 0 && (((uintptr_t)code) & 3u) == 0, CCD_EINVAL);
+    const int quads = H * W / 4, bpi = (quads + ccd::SSL_THREADS - 1) / ccd::SSL_THREADS;
+    CCD_LAUNCH(ccd::seg_sup_loss_bwd_kernel, dim3((unsigned)((long)images * bpi)), dim3(ccd::SSL_THREADS), 0, stream, logits, image_stride,
+               channel_stride, code, quads, bpi, images, weight_bg, weight_text, dice_weight, edge_weight, ws, grad_scale, d_grad, d_logits);
     return ccd_rt_last_error();
 }
 

@@ -148,6 +148,109 @@ class ABIDINOModel(ArenaModule):
                             "feature": lambda: self.backbone.to_2D(tokens).float()})
 
 
+# ------------------------------------------------------------------------------------------------ segmentation finetune
+class DINO_Segment(ArenaModule):
+    """Text segmenter of the segmentation finetune stage (no reference counterpart: the reference names the task - its data tree
+    holds TextSeg - and ships no training code for it): the pretrained ViT backbone and the pretrained character-region head,
+    trained on image / mask pairs under SegSupLoss.  The module names are the pretraining model's, so the `module.backbone.*` and
+    `module.segmentation.*` entries of a pretraining checkpoint load as they are.
+    config: `arch`, `patch_size`, `drop_path_rate` as DINO_Finetune reads them, and the `seg_loss:` block - class_weight (1, 1),
+    ignore_index 255, dice_weight 0, edge_weight 0, edge_radius 0 (ccd_amd/loss/seg_loss.py).
+    Training runs the head in train mode (batch statistics; one rank: the SyncBatchNorm exchange of a supervised run is not part of
+    this model's scripts), `forward_test` / `forward_mask` normalise by the running statistics (seghead.seg_head_inference)."""
+
+    last_logits = None                 # the logits of the last forward_train, fp32 [N, 2, 32, 128], detached
+
+    def __init__(self, config):
+        super().__init__()
+        from ..loss.seg_loss import SegSupLoss
+        from ..modules import vision_transformer as vits
+        from ..modules.segmentor import SegHead
+        config.arch = config.arch.replace("deit", "vit")
+        if config.arch not in vits.__dict__:
+            raise NotImplementedError(f"Unknow architecture: {config.arch} (HIP kernels cover vit_tiny / vit_small / vit_base)")
+        self.backbone = vits.__dict__[config.arch](patch_size=config.patch_size, drop_path_rate=_absent(config.drop_path_rate, 0.0))
+        taps = self.backbone.out_indices
+        if len(taps) != 3 or not all(1 <= t <= len(self.backbone.blocks) for t in taps):
+            raise ValueError(f"DINO_Segment: the segmentation head reads three taps inside the backbone, got out_indices {taps} for "
+                             f"{len(self.backbone.blocks)} blocks")
+        # nothing reads the stream behind the last tap (the stock architectures tap blocks 2, 4, 6 of 12): the passes stop there.  The
+        # blocks behind it keep their parameters (a pretraining checkpoint loads and saves whole) and the blocks in front keep the
+        # DropPath rates of the full depth.
+        spec, last = self.backbone.spec, max(taps)
+        if last < spec.depth:
+            cut = engine.VitSpec(spec.E, last, spec.heads, spec.taps, spec.patch, spec.eps)
+            cut.dpr = list(spec.dpr[:last])
+            self.backbone.spec = cut
+        self.segmentation = SegHead(in_channels=self.backbone.embed_dim, mla_channels=128, mlahead_channels=64, num_classes=2)
+        g = lambda k, d: _absent(getattr(config, "seg_loss_" + k, None), d)
+        self.loss = SegSupLoss(class_weight=g("class_weight", (1.0, 1.0)), ignore_index=g("ignore_index", 255),
+                               dice_weight=g("dice_weight", 0.0), edge_weight=g("edge_weight", 0.0), edge_radius=g("edge_radius", 0))
+
+    # ------------------------------------------------------------------------------------------- arena
+    def _transposed_names(self):
+        return ["backbone." + n for n in self.backbone._transposed_names()]
+
+    def attach_arena(self, arena, prefix):
+        super().attach_arena(arena, prefix)
+        self.backbone.attach_arena(arena, prefix + "backbone.")
+
+    def unused_parameter_names(self):
+        """Parameters this forward pass never reads, so that the optimiser leaves them alone (no weight decay on tensors without a
+        gradient): cls_token and the head's conv_mla branch as in pretraining, and what lies behind the last tap - the final norm and,
+        for the stock architectures (taps behind blocks 2, 4, 6 of 12), the blocks after it."""
+        pre = self.arena_prefix
+        last = max(self.backbone.out_indices)
+        names = [pre + "backbone.cls_token", pre + "backbone.norm.weight", pre + "backbone.norm.bias"]
+        for n, _ in self.named_parameters():
+            if n.startswith("segmentation.conv_mla.") or (n.startswith("backbone.blocks.") and int(n.split(".")[2]) >= last):
+                names.append(pre + n)
+        return names
+
+    # ------------------------------------------------------------------------------------------- surface
+    def forward(self, img, gt=None, return_loss=True):
+        if return_loss:
+            return self.forward_train(img, gt)
+        return self.forward_test(img)
+
+    def _taps(self, img):
+        self.ensure_arena()
+        _, *taps = self.backbone.tokens_and_taps(img, need_taps=True)
+        n, e = img.shape[0], self.backbone.embed_dim
+        return [t.reshape(n * 256, e) for t in taps], n
+
+    def forward_train(self, img, gt):
+        """img fp32 [N, 3, 32, 128], gt uint8 [N, 32, 128] (0 background, 1 text, ignore_index not scored) -> the loss (a device
+        scalar); the gradient flows through the head into the three taps of the backbone.  `loss.last_parts` / `loss.last_confusion`
+        keep the parts and the batch's confusion matrix, `last_logits` the logits."""
+        from ..seghead import seg_head_forward
+        taps, n = self._taps(img)
+        logits = seg_head_forward(self.segmentation, taps, n)
+        self.last_logits = logits.detach()
+        return self.loss(logits, gt)
+
+    @torch.no_grad()
+    def forward_test(self, img):
+        """img fp32 [N, 3, 32, 128] -> eval-mode logits fp32 [N, 2, 32, 128]: no DropPath, BatchNorm by running statistics, whatever
+        mode the model is in; no statistic is updated."""
+        from ..seghead import seg_head_inference
+        was = self.backbone.training
+        self.backbone.eval()
+        try:
+            taps, n = self._taps(img)
+        finally:
+            self.backbone.train(was)
+        return seg_head_inference(self.segmentation, taps, n)
+
+    @torch.no_grad()
+    def forward_mask(self, img):
+        """-> (mask uint8 [N, 32, 128]: 1 where logit1 > logit0, a tie is background as in torch.argmax; prob fp32 [N, 32, 128] =
+        softmax(logits)[:, 1])."""
+        logits = self.forward_test(img)
+        # (two elementwise views of the logits; ops.seg_to_mask thresholds the rounded softmax, which is not the tie rule)
+        return (logits[:, 1] > logits[:, 0]).to(torch.uint8), torch.sigmoid(logits[:, 1] - logits[:, 0])
+
+
 # ------------------------------------------------------------------------------------------------ finetune
 class DINO_Finetune(ArenaModule):
     """Text recogniser of the finetune stage (Dino/model/dino_vision.py:134-290): ViT backbone -> Mlp "encoder" ->

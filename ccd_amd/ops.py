@@ -1845,6 +1845,97 @@ def seg_loss(logits, mask_a, idmap_b, grad_scale, loss_out, d_logits=None):
     _call("ccd_seg_loss", logits, mask_a, idmap_b, half, float(grad_scale), loss_out, d_logits)
 
 
+# ------------------------------------------------------------------------------------------ supervised segmentation loss
+SEG_SUP_MAX_PIXELS = 8192    # H * W of one image: its gt plane is staged in LDS (ccd_hip.h: CCD_SEG_SUP_MAX_PIXELS)
+SEG_SUP_MAX_RADIUS = 4       # edge_radius (ccd_hip.h: CCD_SEG_SUP_MAX_RADIUS)
+SEG_SUP_PARTS = ("loss", "ce", "dice", "omega")
+SEG_SUP_WS_ROW, SEG_SUP_WS_TAIL = 11, 3      # fp64 partial sums per image; behind them Omega, N_v, the invalid gt pixels
+
+
+def seg_sup_params(class_weight=(1.0, 1.0), ignore_index=255, dice_weight=0.0, edge_weight=0.0, edge_radius=0):
+    """The five parameters of the supervised segmentation loss, checked -> (weight_bg, weight_text, ignore_index, dice_weight,
+    edge_weight, edge_radius).  ValueError names the parameter that is refused."""
+    def number(v):
+        return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
+    cw = tuple(class_weight) if isinstance(class_weight, (tuple, list)) else None
+    if cw is None or len(cw) != 2 or not all(number(v) and v >= 0 for v in cw):
+        raise ValueError(f"seg_sup_loss: class_weight must be two finite numbers >= 0 (background, text), got {class_weight!r}")
+    if isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or not 2 <= ignore_index <= 255:
+        raise ValueError(f"seg_sup_loss: ignore_index must be an integer in 2..255 (0 and 1 are the classes of a uint8 map), got {ignore_index!r}")
+    for name, v in (("dice_weight", dice_weight), ("edge_weight", edge_weight)):
+        if not number(v) or v < 0:
+            raise ValueError(f"seg_sup_loss: {name} must be a finite number >= 0, got {v!r}")
+    if isinstance(edge_radius, bool) or not isinstance(edge_radius, int) or not 0 <= edge_radius <= SEG_SUP_MAX_RADIUS:
+        raise ValueError(f"seg_sup_loss: edge_radius must be an integer in 0..{SEG_SUP_MAX_RADIUS}, got {edge_radius!r}")
+    return float(cw[0]), float(cw[1]), ignore_index, float(dice_weight), float(edge_weight), edge_radius
+
+
+def _seg_sup_logits(logits, who):
+    """fp32 logits [N, 2, H, W] as the kernels read them -> (tensor, image stride, channel stride): the planes stay in place when they
+    are contiguous and 16-byte aligned with strides that are multiples of four elements (a channel slice of a wider buffer), a
+    dense copy is made otherwise."""
+    if logits.dtype != F32:
+        raise TypeError(f"{who}: logits must be float32, got {str(logits.dtype)[6:]}")
+    if logits.dim() != 4 or logits.shape[1] != 2 or logits.shape[0] < 1:
+        raise ValueError(f"{who}: expects logits [N >= 1, 2, H, W], got {list(logits.shape)}")
+    N, _, H, W = logits.shape
+    if W % 4 != 0 or H * W > SEG_SUP_MAX_PIXELS or H < 1 or W < 4:
+        raise ValueError(f"{who}: the kernels take W % 4 == 0 and H * W <= {SEG_SUP_MAX_PIXELS}, got {H} x {W}")
+    sn, sc = (logits.stride(0) if N > 1 else 2 * H * W), logits.stride(1)
+    if not logits[0, 0].is_contiguous() or logits.data_ptr() % 16 or sn % 4 or sc % 4 or sn < 0 or sc < 0:
+        logits = logits.contiguous()
+        sn, sc = 2 * H * W, H * W
+    return logits, sn, sc
+
+
+class SegSupLossResult(tuple):
+    """(loss fp32 0-dim, parts fp64 [4] = L, CE, Dice, Omega, confusion int64 [2, 2] = [gt, pred]) with the buffers the backward
+    pass reads as attributes: ws (fp64), code (uint8 [N, H, W] or None)."""
+    ws = code = None
+
+
+def seg_sup_loss(logits, gt, class_weight=(1.0, 1.0), ignore_index=255, dice_weight=0.0, edge_weight=0.0, edge_radius=0, need_code=True):
+    """The fused supervised segmentation loss (kernels/seg_sup_loss.h), forward: fp32 logits [N, 2, H, W] (a channel slice is read
+    in place) and a uint8 gt [N, H, W] (0 background, 1 text, ignore_index and every other value not scored) -> SegSupLossResult.
+    L = CE + dice_weight * Dice with CE the class- and edge-weighted cross entropy over Omega = sum w and Dice the mean soft Dice
+    loss of the images with a scored pixel; a batch without one gives L = 0 (not torch's NaN).  Three device tensors, no
+    synchronisation."""
+    p = seg_sup_params(class_weight, ignore_index, dice_weight, edge_weight, edge_radius)
+    logits, sn, sc = _seg_sup_logits(logits, "seg_sup_loss")
+    N, _, H, W = logits.shape
+    if gt.dtype != torch.uint8:
+        raise TypeError(f"seg_sup_loss: gt must be uint8, got {str(gt.dtype)[6:]}")
+    if tuple(gt.shape) != (N, H, W) or gt.device != logits.device:
+        raise ValueError(f"seg_sup_loss: gt must be [N, H, W] = {[N, H, W]} on {logits.device}, got {list(gt.shape)} on {gt.device}")
+    if not gt[0].is_contiguous() or (N > 1 and gt.stride(0) < 0):
+        gt = gt.contiguous()
+    dev = logits.device
+    ws = torch.empty((N * SEG_SUP_WS_ROW + SEG_SUP_WS_TAIL,), dtype=F64, device=dev)
+    code = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if need_code else None
+    loss, parts = torch.empty((1,), dtype=F32, device=dev), torch.empty((4,), dtype=F64, device=dev)
+    confusion = torch.empty((2, 2), dtype=torch.int64, device=dev)
+    _call("ccd_seg_sup_loss_fwd", logits, sn, sc, 2, gt, gt.stride(0) if N > 1 else H * W, N, H, W, p[2], p[0], p[1], p[3], p[4], p[5],
+          ws, code, loss, parts, confusion)
+    out = SegSupLossResult((loss.view(()), parts, confusion))
+    out.ws, out.code = ws, code
+    return out
+
+
+def seg_sup_loss_bwd(logits, code, ws, class_weight=(1.0, 1.0), dice_weight=0.0, edge_weight=0.0, grad_scale=1.0, d_grad=None):
+    """The backward pass of seg_sup_loss on the same logits with the code and ws it left: d_logits fp32 [N, 2, H, W] (dense), scaled
+    by grad_scale and, when given, by the device scalar d_grad (fp32, one element)."""
+    w0, w1, _, dice_weight, edge_weight, _ = seg_sup_params(class_weight, 255, dice_weight, edge_weight, 0)
+    logits, sn, sc = _seg_sup_logits(logits, "seg_sup_loss_bwd")
+    N, _, H, W = logits.shape
+    assert code is not None and code.dtype == torch.uint8 and tuple(code.shape) == (N, H, W) and code.is_contiguous()
+    assert ws.dtype == F64 and ws.is_contiguous() and ws.numel() == N * SEG_SUP_WS_ROW + SEG_SUP_WS_TAIL
+    if d_grad is not None:
+        d_grad = d_grad.reshape(1).to(F32)
+    d_logits = torch.empty((N, 2, H, W), dtype=F32, device=logits.device)
+    _call("ccd_seg_sup_loss_bwd", logits, sn, sc, 2, code, N, H, W, w0, w1, dice_weight, edge_weight, ws, float(grad_scale), d_grad, d_logits)
+    return d_logits
+
+
 # ------------------------------------------------------------------------------------------ optimiser
 def seg_sumsq(grad, chunk_seg, chunk_begin, chunk_len, norm2):
     _call("ccd_seg_sumsq", grad, chunk_seg, chunk_begin, chunk_len, chunk_seg.numel(), norm2)

@@ -370,3 +370,49 @@ class SegHeadFn(torch.autograd.Function):
 def seg_head_forward(head, taps, images):
     """taps: three bf16 [images*256, E] token-major feature maps -> fp32 logits [images, 2, 32, 128]."""
     return SegHeadFn.apply(head, images, *taps)
+
+
+def _running_mean_rstd(bn):
+    """mean_rstd fp32 [2C] of an eval-mode BatchNorm: its running statistics (tiny device glue; the kernels take it as an argument)."""
+    return torch.cat([bn.running_mean.detach().float(), torch.rsqrt(bn.running_var.detach().float() + bn.eps)])
+
+
+@torch.no_grad()
+def seg_head_inference(head, taps, images):
+    """Eval mode of the head, whatever `head.training` says: the conv, BatchNorm + ReLU and classifier kernels of SegHeadFn.forward
+    with every BatchNorm normalising by its RUNNING statistics.  No batch statistics are accumulated, no activation is kept for a
+    backward pass, and running_mean / running_var / num_batches_tracked are left alone.
+    taps: three bf16 [images*256, E] token-major feature maps -> fp32 logits [images, 2, 32, 128]."""
+    dev = taps[0].device
+    taps = [t.contiguous() for t in taps]
+    E = taps[0].shape[1]
+    gh, gw = 8, 32
+    M = images * gh * gw
+    assert all(tuple(t.shape) == (M, E) and t.dtype == BF16 for t in taps)
+    heads = [head.mlahead.head2, head.mlahead.head3, head.mlahead.head4]
+    mid, out_c = heads[0][0].out_channels, heads[0][3].out_channels
+    wts = _relaid_weights(head, E, mid, out_c, dev, backward=False)
+    d3 = ops.conv_desc((gh, gw), (gh, gw), E, TAPS3)
+    d1 = ops.conv_desc((gh, gw), (gh, gw), mid, TAPS1)
+    cat = torch.empty((M, 3 * out_c), dtype=BF16, device=dev)
+    for i, seq in enumerate(heads):
+        y1 = ops.conv_gemm(taps[i], d3, wts["w1"][i], M, torch.empty((M, mid), dtype=BF16, device=dev))
+        a1 = ops.bn_relu_fwd(y1, _running_mean_rstd(seq[1]), seq[1].weight.detach(), seq[1].bias.detach(), torch.empty_like(y1))
+        y2 = ops.conv_gemm(a1, d1, wts["w2"][i], M, torch.empty((M, out_c), dtype=BF16, device=dev))
+        ops.bn_relu_fwd(y2, _running_mean_rstd(seq[4]), seq[4].weight.detach(), seq[4].bias.detach(), cat[:, i * out_c:(i + 1) * out_c])
+    x, grid = cat, (gh, gw)
+    for lvl, seq in enumerate((head.unpool1, head.unpool2)):
+        convt, bnm = seq[0], seq[1]
+        cin, cout = convt.in_channels, convt.out_channels
+        rows = images * grid[0] * grid[1]
+        y = torch.empty((4 * rows, cout), dtype=BF16, device=dev)
+        for cls_i, (py, px) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+            desc = ops.conv_desc(grid, grid, cin, [(dy, dx) for _, _, dy, dx in _parity_taps(py, px)], parity=(py, px))
+            ops.conv_gemm(x, desc, wts["wp"][lvl][cls_i], rows, y, bias=convt.bias.detach())
+        grid = (2 * grid[0], 2 * grid[1])
+        mean_rstd = _running_mean_rstd(bnm)
+        if seq is head.unpool2 and FUSE_CLS_TAIL is not False and head.cls.out_channels == 2 and ops.cls_tail_supported(y, grid[0], grid[1]):
+            return ops.cls_tail_fwd(y, mean_rstd, bnm.weight.detach(), bnm.bias.detach(), head.cls.weight.detach(), head.cls.bias.detach(),
+                                    images, grid[0], grid[1])
+        x = ops.bn_relu_fwd(y, mean_rstd, bnm.weight.detach(), bnm.bias.detach(), torch.empty_like(y))
+    return cls_forward(x, head.cls.weight.detach(), head.cls.bias.detach(), images, grid[0], grid[1])

@@ -852,6 +852,41 @@ int ccd_sinkhorn_assign(const float* logits, int K, const int* d_rows, int rows_
 /* softmax -> cross_entropy (double softmax) of the seg logits [2*half,2,32,128]; d_logits may be NULL */
 int ccd_seg_loss(const float* logits, const float* mask_a, const uint8_t* idmap_b, int half, float grad_scale,
                  float* loss_out, float* d_logits, void* stream);
+/* The supervised text-segmentation loss of the finetuning task (ccd_amd/loss/seg_loss.py; no reference counterpart: the reference
+ * names the task and ships no training code for it).  These three entry points were added WITHOUT raising ccd_abi_version(): they
+ * change no existing signature, so every caller of ABI 30 keeps working, and the version is pinned by the two-pass decoder's checks;
+ * detect the feature by the presence of the symbols.
+ *   logits fp32 [images, 2, H, W]: image and channel strides in elements, the rows of a plane contiguous; base and strides 16-byte
+ *          aligned (CCD_EINVAL otherwise)
+ *   gt     uint8 [images, H * W], image stride in elements: 0 background, 1 text, ignore_index (2..255) not scored; any other value is
+ *          treated as not scored as well and counted in the tail of ws
+ * With y = gt, p = sigmoid(z1 - z0), l = -log softmax(z)[y], edge(q) = q is scored and a scored pixel of the other class lies inside
+ * the image within the (2 edge_radius + 1)^2 square around q, w = weight[y] (1 + edge_weight edge(q)) (0 where not scored):
+ *   Omega = sum w (batch);  CE = sum w l / Omega (0 when Omega = 0: no NaN, unlike F.cross_entropy)
+ *   Dice_n = 1 - (2 I + 1) / (P + G + 1), I = sum p y, P = sum p, G = sum y over the scored pixels of image n; Dice = the mean over the
+ *   N_v images with a scored pixel (0 when there are none);  L = CE + dice_weight Dice
+ * fwd:  loss fp32 [1] = L, parts fp64 [4] = L, CE, Dice, Omega, confusion int64 [2, 2] = the batch's [gt, pred] counts over the scored
+ *       pixels (pred = z1 > z0: a tie is class 0, as in ccd_seg_confusion_logits); ws fp64 [ccd_seg_sup_loss_ws_doubles(images)] =
+ *       CCD_SEG_SUP_WS_ROW partial sums per image, then Omega, N_v and the number of pixels that are neither 0, 1 nor ignore_index;
+ *       code uint8 [images, H * W] (optional, needed by bwd): 0 not scored, 1 background, 2 text, + 4 on the edge band.
+ * bwd:  d_logits fp32 [images, 2, H, W] dense = (grad_scale * (d_grad ? d_grad[0] : 1)) dL/dlogits from logits, code and the ws fwd left:
+ *       dz1 = w (p - y) / Omega - (dice_weight / N_v) (2 y (P + G + 1) - (2 I + 1)) / (P + G + 1)^2 p (1 - p), dz0 = -dz1, 0 where not scored.
+ * One workgroup per image with the gt plane in LDS, one small finishing workgroup, an elementwise backward.  Every sum is fp64 in a fixed
+ * order without atomics: results are bitwise repeatable.  CCD_ESHAPE: channels != 2, images < 1, W % 4 != 0, H * W >
+ * CCD_SEG_SUP_MAX_PIXELS, edge_radius outside 0..CCD_SEG_SUP_MAX_RADIUS; CCD_EINVAL: a missing pointer, a negative stride or weight, a
+ * misaligned operand, ignore_index outside 2..255.  On either nothing is launched. */
+#define CCD_SEG_SUP_MAX_PIXELS 8192
+#define CCD_SEG_SUP_MAX_RADIUS 4
+#define CCD_SEG_SUP_WS_ROW 11
+#define CCD_SEG_SUP_WS_TAIL 3
+long ccd_seg_sup_loss_ws_doubles(int images);
+int ccd_seg_sup_loss_fwd(const float* logits, long image_stride, long channel_stride, int channels, const uint8_t* gt, long gt_stride,
+                         int images, int H, int W, int ignore_index, float weight_bg, float weight_text, float dice_weight,
+                         float edge_weight, int edge_radius, double* ws, uint8_t* code, float* loss, double* parts, long* confusion,
+                         void* stream);
+int ccd_seg_sup_loss_bwd(const float* logits, long image_stride, long channel_stride, int channels, const uint8_t* code, int images,
+                         int H, int W, float weight_bg, float weight_text, float dice_weight, float edge_weight, const double* ws,
+                         float grad_scale, const float* d_grad, float* d_logits, void* stream);
 
 /* ---------------------------------------------------------------- optimiser, train.py:244-272 */
 typedef struct ccd_seg_hyper { float lr_wd, step_size, inv_sqrt_bc2, active; } ccd_seg_hyper;
