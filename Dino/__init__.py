@@ -19,6 +19,7 @@ _ALIASES = {
     "Dino.loss.ce_loss": "ccd_amd.loss.ce_loss",
     "Dino.loss.ctc_loss": "ccd_amd.loss.ctc_loss",
     "Dino.loss.seg_loss": "ccd_amd.loss.seg_loss",
+    "Dino.loss.sr_loss": "ccd_amd.loss.sr_loss",
     "Dino.decoder": "ccd_amd.decoder",
     "Dino.decoder.nrtr_decoder": "ccd_amd.decoder.nrtr_decoder",
     "Dino.decoder.ctc_decoder": "ccd_amd.decoder.ctc_decoder",

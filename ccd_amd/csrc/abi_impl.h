@@ -39,6 +39,7 @@
 #include "kernels/optim.h"
 #include "kernels/conv.h"
 #include "kernels/cls_tail.h"
+#include "kernels/sr.h"
 #include "kernels/decoder.h"
 #include "kernels/decoder_xattn.h"
 #include "kernels/nrtr_score.h"
@@ -2071,6 +2072,73 @@ int ccd_cls_grad_cols(const float* dlogits, ccd_bf16* g, int images, int H, int 
     const long total = (long)images * H * W * 8;
     CCD_LAUNCH(ccd::cls_grad_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, dlogits, g, images,
                H, W);
+    return ccd_rt_last_error();
+}
+
+// ------------------------------------------------------------------------------- text super-resolution (kernels/sr.h)
+// every check comes before the first launch
+static_assert(CCD_SR_MAX_LR_PIXELS == ccd::SR_MAX_LR_PIX && CCD_SR_MAX_H == ccd::SR_MAX_H && CCD_SR_MAX_W == ccd::SR_MAX_W &&
+              CCD_SR_WS_IMAGE == ccd::SR_CH * ccd::SR_WS_PLANE && ccd::IMG_ZROWS == ccd::CLS_ZROWS && ccd::IMG_GCOLS == ccd::CLS_GCOLS && 9 * ccd::SR_CH <= ccd::IMG_ZROWS, "");
+int ccd_sr_upsample(const float* lr, int images, int h, int w, float mean0, float mean1, float mean2, float std0, float std1,
+                    float std2, float* base, float* xin, void* stream) {
+    CCD_CHECK(lr && base && xin, CCD_EINVAL);
+    CCD_CHECK(std0 > 0.f && std1 > 0.f && std2 > 0.f && mean0 == mean0 && mean1 == mean1 && mean2 == mean2, CCD_EINVAL);      // (no NaN)
+    const ccd::SrNorm nrm = {{mean0, mean1, mean2}, {std0, std1, std2}};
+    CCD_CHECK(CCD_ALIGNED16(base) && CCD_ALIGNED16(xin), CCD_EINVAL);              // 16-byte stores along the output rows
+    CCD_CHECK(images >= 0 && h >= 1 && w >= 2 && w % 2 == 0 && (long)h * w <= ccd::SR_MAX_LR_PIX, CCD_ESHAPE);
+    if (images == 0) return CCD_OK;
+    CCD_LAUNCH(ccd::sr_upsample_kernel, dim3((unsigned)(images * ccd::SR_CH)), dim3(ccd::SR_THREADS), 0, stream, lr, h, w, nrm, base, xin);
+    return ccd_rt_last_error();
+}
+
+int ccd_img_gather_fwd(const float* zT, long ldz, const float* bias, const float* base, float* sr, int images, int H, int W,
+                       void* stream) {
+    CCD_CHECK(zT && bias && base && sr, CCD_EINVAL);
+    if (images == 0) return CCD_OK;
+    CCD_CHECK(images > 0 && H > 0 && W > 0 && ldz >= (long)images * H * W, CCD_ESHAPE);
+    const long total = (long)images * H * W;
+    CCD_LAUNCH(ccd::img_gather_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, zT, ldz, bias, base, sr,
+               images, H, W);
+    return ccd_rt_last_error();
+}
+
+int ccd_img_grad_cols(const float* d_sr, ccd_bf16* g, int images, int H, int W, void* stream) {
+    CCD_CHECK(d_sr && g && CCD_ALIGNED16(g), CCD_EINVAL);
+    if (images == 0) return CCD_OK;
+    CCD_CHECK(images > 0 && H > 0 && W > 0, CCD_ESHAPE);
+    const long total = (long)images * H * W * 8;
+    CCD_LAUNCH(ccd::img_grad_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, d_sr, g, images, H, W);
+    return ccd_rt_last_error();
+}
+
+static int ccd_sr_loss_check(const float* sr, const float* hr, int images, int H, int W, float gp_weight) {
+    CCD_CHECK(((sr && hr) || images == 0) && gp_weight >= 0.f, CCD_EINVAL);         // (a NaN weight fails too; an empty batch has no planes)
+    CCD_CHECK(images >= 0 && H >= 1 && H <= ccd::SR_MAX_H && W >= 4 && W <= ccd::SR_MAX_W && W % 4 == 0, CCD_ESHAPE);
+    CCD_CHECK(CCD_ALIGNED16(sr) && CCD_ALIGNED16(hr), CCD_EINVAL);                  // 16-byte loads along W
+    return CCD_OK;
+}
+long ccd_sr_loss_ws_doubles(int images) {
+    return images < 1 ? 0 : (long)images * ccd::SR_CH * ccd::SR_WS_PLANE;
+}
+int ccd_sr_loss_fwd(const float* sr, const float* hr, int images, int H, int W, float gp_weight, double* ws, double* per_image,
+                    float* loss, double* parts, void* stream) {
+    const int rc = ccd_sr_loss_check(sr, hr, images, H, W, gp_weight);
+    if (rc != CCD_OK) return rc;
+    CCD_CHECK(loss && parts && (images == 0 || (ws && per_image)), CCD_EINVAL);
+    CCD_CHECK((((uintptr_t)ws) & 7u) == 0 && (((uintptr_t)per_image) & 7u) == 0 && (((uintptr_t)parts) & 7u) == 0, CCD_EINVAL);
+    if (images > 0)
+        CCD_LAUNCH(ccd::sr_loss_fwd_kernel, dim3((unsigned)(images * ccd::SR_CH)), dim3(ccd::SR_THREADS), 0, stream, sr, hr, H, W, ws);
+    CCD_LAUNCH(ccd::sr_loss_finish_kernel, dim3(1), dim3(ccd::SR_FIN), 0, stream, ws, images, H, W, gp_weight, per_image, loss, parts);
+    return ccd_rt_last_error();
+}
+int ccd_sr_loss_bwd(const float* sr, const float* hr, int images, int H, int W, float gp_weight, float grad_scale, const float* d_grad,
+                    float* d_sr, void* stream) {
+    const int rc = ccd_sr_loss_check(sr, hr, images, H, W, gp_weight);
+    if (rc != CCD_OK) return rc;
+    CCD_CHECK(d_sr || images == 0, CCD_EINVAL);
+    if (images == 0) return CCD_OK;
+    CCD_LAUNCH(ccd::sr_loss_bwd_kernel, dim3((unsigned)(images * ccd::SR_CH)), dim3(ccd::SR_THREADS), 0, stream, sr, hr, images, H, W,
+               gp_weight, grad_scale, d_grad, d_sr);
     return ccd_rt_last_error();
 }
 

@@ -163,9 +163,7 @@ class DINO_Segment(ArenaModule):
 
     def __init__(self, config):
         super().__init__()
-        from ..loss.seg_loss import SegSupLoss
         from ..modules import vision_transformer as vits
-        from ..modules.segmentor import SegHead
         config.arch = config.arch.replace("deit", "vit")
         if config.arch not in vits.__dict__:
             raise NotImplementedError(f"Unknow architecture: {config.arch} (HIP kernels cover vit_tiny / vit_small / vit_base)")
@@ -182,6 +180,12 @@ class DINO_Segment(ArenaModule):
             cut = engine.VitSpec(spec.E, last, spec.heads, spec.taps, spec.patch, spec.eps)
             cut.dpr = list(spec.dpr[:last])
             self.backbone.spec = cut
+        self._build_task(config)
+
+    def _build_task(self, config):
+        """The head and the loss (DINO_SuperRes builds its own on the same backbone)."""
+        from ..loss.seg_loss import SegSupLoss
+        from ..modules.segmentor import SegHead
         self.segmentation = SegHead(in_channels=self.backbone.embed_dim, mla_channels=128, mlahead_channels=64, num_classes=2)
         g = lambda k, d: _absent(getattr(config, "seg_loss_" + k, None), d)
         self.loss = SegSupLoss(class_weight=g("class_weight", (1.0, 1.0)), ignore_index=g("ignore_index", 255),
@@ -249,6 +253,79 @@ class DINO_Segment(ArenaModule):
         logits = self.forward_test(img)
         # (two elementwise views of the logits; ops.seg_to_mask thresholds the rounded softmax, which is not the tie rule)
         return (logits[:, 1] > logits[:, 0]).to(torch.uint8), torch.sigmoid(logits[:, 1] - logits[:, 0])
+
+
+# ------------------------------------------------------------------------------------------------ super-resolution finetune
+class DINO_SuperRes(DINO_Segment):
+    """Text image super-resolver of the super-resolution finetune stage (no reference counterpart: the reference names the task - its
+    data tree holds Super_Resolution - and ships the metrics, no training code): DINO_Segment's backbone (cut at the last tap, the
+    same unused parameters) under the pretrained MLA head, whose last convolution writes a residual image instead of two logits:
+
+        base = bicubic_x2(lr)                       fp32 [N, 3, 32, 128] from lr [N, 3, 16, 64] in [0, 1] (ops.sr_upsample)
+        sr   = base + segmentation((base - MEAN) / STD)
+
+    The head keeps the attribute name `segmentation`, so the `module.backbone.*` and `module.segmentation.*` entries of a
+    pretraining checkpoint load as they are - except `segmentation.cls.*`, which has three output channels here and starts at zero:
+    sr = base bit for bit at initialisation.  Training uses the unclamped sr under SRLoss; `forward_sr` returns clamp(sr, 0, 1).
+    config: `arch`, `patch_size`, `drop_path_rate`, and the `sr_loss:` block - gp_weight 1e-4, ssim_weight 0 (ccd_amd/loss/sr_loss.py)."""
+
+    LR_SIZE, HR_SIZE = ops.SR_LR_SIZE, ops.SR_HR_SIZE
+    last_sr = None                     # the unclamped sr of the last forward_train, fp32 [N, 3, 32, 128], detached
+
+    def _build_task(self, config):
+        from ..loss.sr_loss import SRLoss
+        from ..modules.segmentor import SegHead
+        self.segmentation = SegHead(in_channels=self.backbone.embed_dim, mla_channels=128, mlahead_channels=64, num_classes=3)
+        nn.init.zeros_(self.segmentation.cls.weight)
+        nn.init.zeros_(self.segmentation.cls.bias)
+        g = lambda k, d: _absent(getattr(config, "sr_loss_" + k, None), d)
+        self.loss = SRLoss(gp_weight=g("gp_weight", 1e-4), ssim_weight=g("ssim_weight", 0.0))
+
+    def forward(self, lr, hr=None, return_loss=True):
+        if return_loss:
+            return self.forward_train(lr, hr)
+        return self.forward_sr(lr)
+
+    def upsample(self, lr):
+        """lr fp32 [N, 3, 16, 64] -> (base, the normalised network input), both fp32 [N, 3, 32, 128]."""
+        from ..dataset.datasetsupervised_kmeans import MEAN, STD
+        if lr.dim() != 4 or tuple(lr.shape[1:]) != (3, *self.LR_SIZE):
+            raise ValueError(f"DINO_SuperRes: lr must be [N, 3, {self.LR_SIZE[0]}, {self.LR_SIZE[1]}] (TextZoom's sizes), got {list(lr.shape)}")
+        self.ensure_arena()               # (a model or batch that is not on the GPU is refused here: there is no CPU path)
+        return ops.sr_upsample(lr.float(), MEAN, STD)
+
+    def forward_train(self, lr, hr):
+        """lr fp32 [N, 3, 16, 64], hr fp32 [N, 3, 32, 128], both in [0, 1] -> the loss (a device scalar) of the unclamped sr; the
+        gradient flows through the head into the three taps of the backbone.  `loss.last_parts` / `loss.last_mse` keep the parts."""
+        from ..seghead import sr_head_forward
+        if hr is None or hr.dim() != 4 or tuple(hr.shape[1:]) != (3, *self.HR_SIZE) or hr.shape[0] != lr.shape[0]:
+            raise ValueError(f"DINO_SuperRes: hr must be [N, 3, {self.HR_SIZE[0]}, {self.HR_SIZE[1]}] with lr's N, got "
+                             f"{None if hr is None else list(hr.shape)}")
+        base, xin = self.upsample(lr)
+        taps, n = self._taps(xin)
+        sr = sr_head_forward(self.segmentation, taps, n, base)
+        self.last_sr = sr.detach()
+        return self.loss(sr, hr.float())
+
+    @torch.no_grad()
+    def forward_sr(self, lr, clamp=True):
+        """lr fp32 [N, 3, 16, 64] -> sr fp32 [N, 3, 32, 128] clamped to [0, 1]: eval mode whatever mode the model is in - no DropPath,
+        BatchNorm by running statistics, no statistic updated."""
+        from ..seghead import sr_head_inference
+        base, xin = self.upsample(lr)
+        was = self.backbone.training
+        self.backbone.eval()
+        try:
+            taps, n = self._taps(xin)
+        finally:
+            self.backbone.train(was)
+        sr = sr_head_inference(self.segmentation, taps, n, base)
+        return sr.clamp_(0.0, 1.0) if clamp else sr
+
+    forward_test = forward_sr
+
+    def forward_mask(self, img):
+        raise NotImplementedError("DINO_SuperRes writes images, not masks: forward_sr")
 
 
 # ------------------------------------------------------------------------------------------------ finetune

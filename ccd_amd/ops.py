@@ -1936,6 +1936,90 @@ def seg_sup_loss_bwd(logits, code, ws, class_weight=(1.0, 1.0), dice_weight=0.0,
     return d_logits
 
 
+# ------------------------------------------------------------------------------------------ text super-resolution (kernels/sr.h)
+SR_LR_SIZE, SR_HR_SIZE = (16, 64), (32, 128)     # TextZoom's sizes, the only ones the task takes
+SR_MAX_H, SR_MAX_W = 32, 128                     # one plane of the loss in LDS (ccd_hip.h: CCD_SR_MAX_H / CCD_SR_MAX_W)
+SR_MAX_LR_PIXELS = 2048                          # one LR plane of the upsample kernel (ccd_hip.h: CCD_SR_MAX_LR_PIXELS)
+SR_PARTS = ("loss", "mse", "gp")
+SR_WS_IMAGE = 6                                  # fp64 partial sums per image: (squared error, gradient-map error) x 3 planes
+
+
+def sr_weight(name, v):
+    """A weight of the super-resolution loss, checked -> float.  ValueError names the parameter that is refused."""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+        raise ValueError(f"sr_loss: {name} must be a finite number >= 0, got {v!r}")
+    return float(v)
+
+
+def sr_upsample(lr, mean, std):
+    """fp32 lr [N, 3, h, w] -> (base, xin) fp32 [N, 3, 2h, 2w]: base = F.interpolate(lr, scale_factor=2, mode="bicubic",
+    align_corners=False) (not clamped), xin = (base - mean[c]) / std[c], in one launch."""
+    if lr.dtype != F32:
+        raise TypeError(f"sr_upsample: lr must be float32, got {str(lr.dtype)[6:]}")
+    if lr.dim() != 4 or lr.shape[1] != 3:
+        raise ValueError(f"sr_upsample: expects lr [N, 3, h, w], got {list(lr.shape)}")
+    N, _, h, w = lr.shape
+    if w % 2 != 0 or h < 1 or w < 2 or h * w > SR_MAX_LR_PIXELS:
+        raise ValueError(f"sr_upsample: the kernel takes an even w and h * w <= {SR_MAX_LR_PIXELS}, got {h} x {w}")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3 or not all(math.isfinite(v) for v in mean) or not all(math.isfinite(v) and v > 0 for v in std):
+        raise ValueError(f"sr_upsample: mean / std must be three finite numbers each, std > 0, got {mean!r} / {std!r}")
+    lr = lr.contiguous()
+    base = torch.empty((N, 3, 2 * h, 2 * w), dtype=F32, device=lr.device)
+    xin = torch.empty_like(base)
+    _call("ccd_sr_upsample", lr, N, h, w, *mean, *std, base, xin)
+    return base, xin
+
+
+def _sr_pair(sr, hr, who):
+    for name, t in (("sr", sr), ("hr", hr)):
+        if t.dtype != F32:
+            raise TypeError(f"{who}: {name} must be float32, got {str(t.dtype)[6:]}")
+    if sr.dim() != 4 or sr.shape[1] != 3:
+        raise ValueError(f"{who}: expects sr [N, 3, H, W], got {list(sr.shape)}")
+    if tuple(hr.shape) != tuple(sr.shape) or hr.device != sr.device:
+        raise ValueError(f"{who}: hr must be {list(sr.shape)} on {sr.device}, got {list(hr.shape)} on {hr.device}")
+    N, _, H, W = sr.shape
+    if W % 4 != 0 or not 1 <= H <= SR_MAX_H or not 4 <= W <= SR_MAX_W:
+        raise ValueError(f"{who}: the kernels take H <= {SR_MAX_H}, W <= {SR_MAX_W} and W % 4 == 0, got {H} x {W}")
+    for name, t in (("sr", sr), ("hr", hr)):
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous (the planes are staged with 16-byte loads), got strides {t.stride()}")
+    return N, H, W
+
+
+class SRLossResult(tuple):
+    """(loss fp32 0-dim, parts fp64 [3] = L, mean mse_n, mean gp_n, per_image fp64 [N, 2] = mse_n, gp_n); ws: the per-plane sums."""
+    ws = None
+
+
+def sr_loss_fwd(sr, hr, gp_weight=1e-4):
+    """The fused super-resolution loss (kernels/sr.h), forward: fp32 sr, hr [N, 3, H, W] -> SRLossResult.  L = mean_n (mse_n +
+    gp_weight gp_n), gp the mean absolute difference of TSRN's gradient maps.  N = 0 gives 0.  Device tensors, no synchronisation."""
+    gp_weight = sr_weight("gp_weight", gp_weight)
+    N, H, W = _sr_pair(sr, hr, "sr_loss_fwd")
+    dev = sr.device
+    ws = torch.empty((N * SR_WS_IMAGE,), dtype=F64, device=dev)
+    per_image = torch.empty((N, 2), dtype=F64, device=dev)
+    loss, parts = torch.empty((1,), dtype=F32, device=dev), torch.empty((3,), dtype=F64, device=dev)
+    _call("ccd_sr_loss_fwd", sr, hr, N, H, W, gp_weight, ws, per_image, loss, parts)
+    out = SRLossResult((loss.view(()), parts, per_image))
+    out.ws = ws
+    return out
+
+
+def sr_loss_bwd(sr, hr, gp_weight=1e-4, grad_scale=1.0, d_grad=None):
+    """The backward pass of sr_loss_fwd on the same sr, hr: d_sr fp32 [N, 3, H, W], scaled by grad_scale and, when given, by the
+    device scalar d_grad (fp32, one element)."""
+    gp_weight = sr_weight("gp_weight", gp_weight)
+    N, H, W = _sr_pair(sr, hr, "sr_loss_bwd")
+    if d_grad is not None:
+        d_grad = d_grad.reshape(1).to(F32)
+    d_sr = torch.empty_like(sr)
+    _call("ccd_sr_loss_bwd", sr, hr, N, H, W, gp_weight, float(grad_scale), d_grad, d_sr)
+    return d_sr
+
+
 # ------------------------------------------------------------------------------------------ optimiser
 def seg_sumsq(grad, chunk_seg, chunk_begin, chunk_len, norm2):
     _call("ccd_seg_sumsq", grad, chunk_seg, chunk_begin, chunk_len, chunk_seg.numel(), norm2)
@@ -2061,6 +2145,23 @@ def cls_grad_cols(dlogits, images, H, W):
     assert dlogits.is_contiguous() and tuple(dlogits.shape) == (images, 2, H, W)
     g = torch.empty((images * H * W, 64), dtype=BF16, device=dlogits.device)
     _call("ccd_cls_grad_cols", dlogits, g, images, H, W)
+    return g
+
+
+def img_gather_fwd(zT, bias, base, images, H, W):
+    """zT fp32 [>=27, pixels] (row co*9+tap), base fp32 [images, 3, H, W] -> fp32 sr [images, 3, H, W] = base + bias + the tap sums."""
+    assert zT.shape[0] >= 27 and zT.shape[1] == images * H * W and bias.numel() == 3
+    assert base.dtype == F32 and base.is_contiguous() and tuple(base.shape) == (images, 3, H, W) and base.device == zT.device
+    sr = torch.empty((images, 3, H, W), dtype=F32, device=zT.device)
+    _call("ccd_img_gather_fwd", zT, zT.stride(0), bias, base, sr, images, H, W)
+    return sr
+
+
+def img_grad_cols(d_sr, images, H, W):
+    """fp32 d_sr [images, 3, H, W] -> bf16 g [pixels, 64] (column co*9+tap < 27 = shifted gradient plane, the rest zero)."""
+    assert d_sr.is_contiguous() and tuple(d_sr.shape) == (images, 3, H, W)
+    g = torch.empty((images * H * W, 64), dtype=BF16, device=d_sr.device)
+    _call("ccd_img_grad_cols", d_sr, g, images, H, W)
     return g
 
 

@@ -10,6 +10,8 @@ have - so every convolution is a GEMM over pixels:
                                      one elementwise pass normalises; SyncBatchNorm = all-reduce of the [2C] statistics
   Conv2d(128, 2, 3) classifier       N = 2 is no MFMA tile: factored through pixel-wise GEMMs (18 tap/class planes)
                                      plus a 9-point gather-sum; fp32 NCHW logits as the loss expects
+  Conv2d(128, 3, 3) image tail       the super-resolution head (DINO_SuperRes): the same factoring with 27 tap planes, the
+                                     gather adds the bicubic base (kernels/sr.h); unfused BatchNorm + ReLU in front of it
   backward                           data gradients: implicit GEMMs with flipped / strided taps; weight gradients:
                                      pixel-contracting TN GEMMs whose B operand is gathered from the image
                                      (ops.conv_wgrad, no patch matrix), re-laid into the parameter layout by
@@ -172,29 +174,40 @@ def _ensure_grads(module):
             p.grad = torch.zeros_like(p)
 
 
-def cls_forward(x, w, b, images, H, W):
-    """Conv2d(C, 2, 3, padding=1) on channels-last bf16 x [pixels, C] -> fp32 logits [images, 2, H, W]."""
-    C = x.shape[1]
+def cls_forward(x, w, b, images, H, W, base=None):
+    """Conv2d(C, 2, 3, padding=1) on channels-last bf16 x [pixels, C] -> fp32 logits [images, 2, H, W].  With three output channels
+    (27 tap planes) and `base` fp32 [images, 3, H, W]: base + the convolution, the image tail."""
+    C, nc = x.shape[1], w.shape[0]
     wz = torch.zeros((32, C), dtype=BF16, device=x.device)                       # row co*9+tap = w[co, :, tap]
-    ops.permute4(w, (C * 9, 1, 9), (2, 9, C), wz[:18])
+    ops.permute4(w, (C * 9, 1, 9), (nc, 9, C), wz[:9 * nc])
     zT = ops.gemm_nt(wz, x, epilogue=ops.EPI_F32)                                 # [32, pixels] fp32
+    if nc == 3:
+        return ops.img_gather_fwd(zT, b, base, images, H, W)
     return ops.cls_gather_fwd(zT, b, images, H, W)
 
 
 def cls_backward(d_logits, x, w, dw, db, images, H, W):
-    """-> dx bf16 [pixels, C]; dw [2, C, 3, 3] / db [2] accumulate (fp32)."""
-    C, dev = x.shape[1], x.device
-    g = ops.cls_grad_cols(d_logits, images, H, W)                                 # [pixels, 64], col co*9+tap
+    """-> dx bf16 [pixels, C]; dw [2, C, 3, 3] / db [2] accumulate (fp32).  Three output channels: the image tail's twin kernel."""
+    C, dev, nc = x.shape[1], x.device, w.shape[0]
+    g = (ops.img_grad_cols if nc == 3 else ops.cls_grad_cols)(d_logits, images, H, W)      # [pixels, 64], col co*9+tap
     wd = torch.zeros((C, 64), dtype=BF16, device=dev)                             # wd[c, co*9+tap] = w[co, c, tap]
-    ops.permute4(w, (9, C * 9, 1), (C, 2, 9), wd, dst_strides=(64, 9, 1))
+    ops.permute4(w, (9, C * 9, 1), (C, nc, 9), wd, dst_strides=(64, 9, 1))
     dx = ops.gemm_nt(g, wd)
     stage = torch.zeros((64, C), dtype=F32, device=dev)
     ops.gemm_tn(g, x, stage)                                                      # [co*9+tap, c]
-    ops.permute4(stage, (9 * C, 1, C), (2, C, 9), dw, accumulate=True)
+    ops.permute4(stage, (9 * C, 1, C), (nc, C, 9), dw, accumulate=True)
     cs = torch.zeros(64, dtype=F32, device=dev)
     ops.colsum_bf16(g, cs)                                                        # centre tap (always in bounds)
-    ops.permute4(cs[4:], (9,), (2,), db, accumulate=True)
+    ops.permute4(cs[4:], (9,), (nc,), db, accumulate=True)
     return dx
+
+
+def _image_head(head):
+    """The classifier's output channels say which tail the head takes: 2 = character-region logits, 3 = a residual image."""
+    n = head.cls.out_channels
+    if n not in (2, 3):
+        raise NotImplementedError(f"the head's last convolution has kernels for 2 (logits) or 3 (image) output channels, got {n}")
+    return n == 3
 
 
 def _relaid_weights(head, E, mid, out_c, dev, backward=True):
@@ -237,11 +250,14 @@ def _relaid_weights(head, E, mid, out_c, dev, backward=True):
 
 
 class SegHeadFn(torch.autograd.Function):
-    """(tap2, tap3, tap4: bf16 [N*256, E]) -> fp32 logits [N, 2, 32, 128]; parameter gradients go straight to .grad."""
+    """(tap2, tap3, tap4: bf16 [N*256, E]) -> fp32 logits [N, 2, 32, 128]; parameter gradients go straight to .grad.
+    A head whose classifier has three output channels takes `base` fp32 [N, 3, 32, 128] and returns base + its residual image."""
 
     @staticmethod
-    def forward(ctx, head, images, t2, t3, t4):
+    def forward(ctx, head, images, t2, t3, t4, base=None):
         dev = t2.device
+        image = _image_head(head)
+        assert (base is not None) == image, "base goes with the image tail (cls.out_channels == 3), and only with it"
         taps = [t.contiguous() for t in (t2, t3, t4)]
         E = taps[0].shape[1]
         gh, gw = 8, 32
@@ -301,7 +317,8 @@ class SegHeadFn(torch.autograd.Function):
             logits = ops.cls_tail_fwd(y, bn.mean_rstd, bn.mod.weight.detach(), bn.mod.bias.detach(), head.cls.weight.detach(),
                                       head.cls.bias.detach(), images, grid[0], grid[1])
         else:
-            logits = cls_forward(x, head.cls.weight.detach(), head.cls.bias.detach(), images, grid[0], grid[1])
+            logits = cls_forward(x, head.cls.weight.detach(), head.cls.bias.detach(), images, grid[0], grid[1],
+                                 base=base.detach().contiguous() if image else None)
         ctx.head, ctx.images, ctx.saved, ctx.ups, ctx.a_last, ctx.grid = head, images, saved, ups, x, grid
         ctx.fused_tail = fused_tail
         ctx.dims = (E, mid, out_c, M)
@@ -364,7 +381,7 @@ class SegHeadFn(torch.autograd.Function):
             d_taps.append(ops.conv_gemm(dy1s[i], d3f, wts["w1d"][i], M, torch.empty((M, E), dtype=BF16, device=dev)))
         ops.permute4_multi(folds, accumulate=True)
         ctx.saved = ctx.ups = None
-        return (None, None, *d_taps)
+        return (None, None, *d_taps, None)
 
 
 def seg_head_forward(head, taps, images):
@@ -377,13 +394,31 @@ def _running_mean_rstd(bn):
     return torch.cat([bn.running_mean.detach().float(), torch.rsqrt(bn.running_var.detach().float() + bn.eps)])
 
 
+def sr_head_forward(head, taps, images, base):
+    """taps: three bf16 [images*256, E] token-major feature maps, base fp32 [images, 3, 32, 128] -> fp32 sr [images, 3, 32, 128] =
+    base + the head's residual image (cls.out_channels == 3; unfused BatchNorm + ReLU, then the image gather).  No gradient
+    goes to `base`: it is a resampling of the input."""
+    assert _image_head(head), "sr_head_forward: the head's classifier must have three output channels"
+    return SegHeadFn.apply(head, images, *taps, base)
+
+
 @torch.no_grad()
-def seg_head_inference(head, taps, images):
+def sr_head_inference(head, taps, images, base):
+    """Eval mode of the image head (seg_head_inference's contract: running statistics, nothing updated) -> fp32 sr, not clamped."""
+    assert _image_head(head), "sr_head_inference: the head's classifier must have three output channels"
+    return seg_head_inference(head, taps, images, base=base)
+
+
+@torch.no_grad()
+def seg_head_inference(head, taps, images, base=None):
     """Eval mode of the head, whatever `head.training` says: the conv, BatchNorm + ReLU and classifier kernels of SegHeadFn.forward
     with every BatchNorm normalising by its RUNNING statistics.  No batch statistics are accumulated, no activation is kept for a
     backward pass, and running_mean / running_var / num_batches_tracked are left alone.
-    taps: three bf16 [images*256, E] token-major feature maps -> fp32 logits [images, 2, 32, 128]."""
+    taps: three bf16 [images*256, E] token-major feature maps -> fp32 logits [images, 2, 32, 128]; with a three-channel classifier and
+    `base`, base + the residual image."""
     dev = taps[0].device
+    image = _image_head(head)
+    assert (base is not None) == image, "base goes with the image tail (cls.out_channels == 3), and only with it"
     taps = [t.contiguous() for t in taps]
     E = taps[0].shape[1]
     gh, gw = 8, 32
@@ -415,4 +450,4 @@ def seg_head_inference(head, taps, images):
             return ops.cls_tail_fwd(y, mean_rstd, bnm.weight.detach(), bnm.bias.detach(), head.cls.weight.detach(), head.cls.bias.detach(),
                                     images, grid[0], grid[1])
         x = ops.bn_relu_fwd(y, mean_rstd, bnm.weight.detach(), bnm.bias.detach(), torch.empty_like(y))
-    return cls_forward(x, head.cls.weight.detach(), head.cls.bias.detach(), images, grid[0], grid[1])
+    return cls_forward(x, head.cls.weight.detach(), head.cls.bias.detach(), images, grid[0], grid[1], base=base.contiguous() if image else None)

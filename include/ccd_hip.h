@@ -963,6 +963,45 @@ int ccd_bn_relu_bwd_apply(const ccd_bf16* dy, long lddy, const ccd_bf16* x, long
 int ccd_cls_gather_fwd(const float* zT, long ldz, const float* bias, float* logits, int images, int H, int W,
                        void* stream);
 int ccd_cls_grad_cols(const float* dlogits, ccd_bf16* g, int images, int H, int W, void* stream);
+/* Text super-resolution finetuning (ccd_amd/superres.py, kernels/sr.h; no reference counterpart: the reference names the task and
+ * ships the metrics, no training code).  These seven entry points were added WITHOUT raising ccd_abi_version(): they change no
+ * existing signature, so every caller of ABI 30 keeps working, and the version is pinned by the two-pass decoder's checks; detect the
+ * feature by the presence of the symbols.
+ * ccd_sr_upsample: lr fp32 [images, 3, h, w] dense -> base fp32 [images, 3, 2h, 2w] = torch's F.interpolate(lr, scale_factor=2,
+ *   mode="bicubic", align_corners=False) (A = -0.75, border indices clamped, result not clamped) and xin = (base - mean[c]) / std[c],
+ *   one launch, one workgroup per plane.  At x2 the fractions are 0.25 and 0.75 only, whose taps (-27, 225, 67, -9) / 256 are
+ *   constants; an interpolation is written around its heaviest tap, so a constant plane comes back bit for bit.
+ *   CCD_ESHAPE: w odd, h * w > CCD_SR_MAX_LR_PIXELS; CCD_EINVAL: a missing or misaligned pointer, std <= 0, a NaN.
+ * ccd_img_gather_fwd / ccd_img_grad_cols: the 3-channel twins of ccd_cls_gather_fwd / ccd_cls_grad_cols for a head whose last
+ *   convolution Conv2d(C, 3, 3, padding=1) writes a residual image: zT rows co*9+tap < 27, g columns co*9+tap < 27 (>= 27 zero);
+ *   sr[n,co,y,x] = base[n,co,y,x] + (bias[co] + sum_tap zT[co*9+tap, (n,y+dy,x+dx)]) - zero weights and bias give sr = base bit for bit.
+ * The loss, per channel plane x with zero padding (TSRN's gradient map):
+ *   g(x) = sqrt((0.5 (x[y,x+1] - x[y,x-1]))^2 + (0.5 (x[y-1,x] - x[y+1,x]))^2 + 1e-6)
+ *   mse_n = mean (sr - hr)^2, gp_n = mean |g(sr) - g(hr)| over the 3 H W elements of image n;  L = mean_n (mse_n + gp_weight gp_n)
+ * sr, hr fp32 [images, 3, H, W] dense and 16-byte aligned, H <= CCD_SR_MAX_H, W <= CCD_SR_MAX_W, W % 4 == 0, any number of images.
+ * fwd:  one workgroup per plane (both planes in LDS) -> ws fp64 [ccd_sr_loss_ws_doubles(images)] = (sum of squared errors, sum of
+ *       gradient-map errors) per plane; one finishing workgroup -> per_image fp64 [images, 2] = mse_n, gp_n, loss fp32 [1] = L,
+ *       parts fp64 [3] = L, mean mse_n, mean gp_n.  images == 0: L = 0, ws and per_image may be NULL.
+ * bwd:  d_sr fp32 [images, 3, H, W] = (grad_scale * (d_grad ? d_grad[0] : 1) / (images 3 H W)) [2 (sr - hr) + gp_weight * the four
+ *       neighbour terms 0.25 sign(g(sr) - g(hr)) (difference) / g(sr) of the pixels whose stencil contains the pixel], sign(0) = 0;
+ *       a gather from the LDS planes, reads no ws.  images == 0: nothing to write.
+ * The stencil terms and every sum are fp64, in a fixed order (the images fold as a tree of fixed shape) without atomics: results are
+ * bitwise repeatable.  CCD_ESHAPE: H, W outside the limits, W % 4 != 0, images < 0; CCD_EINVAL: a missing or misaligned pointer, a
+ * negative or NaN gp_weight.  On either nothing is launched. */
+#define CCD_SR_MAX_LR_PIXELS 2048
+#define CCD_SR_MAX_H 32
+#define CCD_SR_MAX_W 128
+#define CCD_SR_WS_IMAGE 6
+int ccd_sr_upsample(const float* lr, int images, int h, int w, float mean0, float mean1, float mean2, float std0, float std1,
+                    float std2, float* base, float* xin, void* stream);
+int ccd_img_gather_fwd(const float* zT, long ldz, const float* bias, const float* base, float* sr, int images, int H, int W,
+                       void* stream);
+int ccd_img_grad_cols(const float* d_sr, ccd_bf16* g, int images, int H, int W, void* stream);
+long ccd_sr_loss_ws_doubles(int images);
+int ccd_sr_loss_fwd(const float* sr, const float* hr, int images, int H, int W, float gp_weight, double* ws, double* per_image,
+                    float* loss, double* parts, void* stream);
+int ccd_sr_loss_bwd(const float* sr, const float* hr, int images, int H, int W, float gp_weight, float grad_scale, const float* d_grad,
+                    float* d_sr, void* stream);
 /* The same tail - unpool2's BatchNorm2d + ReLU, then `cls` (segmentor.py:84-95) - FUSED for the reference's own head shape
  * (C = 128 channels, H x W = 32 x 128 pixels per image, 2 classes; anything else: CCD_ESHAPE, take the kernels above).
  * y: the transposed conv's output before its BatchNorm, bf16 [images*H*W, ldy]; w: cls.weight fp32 [2, C, 3, 3] (the
