@@ -23,6 +23,7 @@ _ALIASES = {
     "Dino.decoder": "ccd_amd.decoder",
     "Dino.decoder.nrtr_decoder": "ccd_amd.decoder.nrtr_decoder",
     "Dino.decoder.ctc_decoder": "ccd_amd.decoder.ctc_decoder",
+    "Dino.decoder.parallel_attn_decoder": "ccd_amd.decoder.parallel_attn_decoder",
     "Dino.convertor": "ccd_amd.convertor",
     "Dino.convertor.base": "ccd_amd.convertor.base",
     "Dino.convertor.attn": "ccd_amd.convertor.attn",

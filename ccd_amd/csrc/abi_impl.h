@@ -44,6 +44,7 @@
 #include "kernels/decoder_xattn.h"
 #include "kernels/nrtr_score.h"
 #include "kernels/nrtr_twopass.h"
+#include "kernels/posattn.h"
 
 #define CCD_CHECK(cond, code) \
     do {                      \
@@ -2485,6 +2486,61 @@ int ccd_nrtr_twopass_select(const int* paths, long sample_stride, long slot_stri
               CCD_EINVAL);
     CCD_LAUNCH(ccd::nrtr_twopass_select_kernel, dim3((unsigned)((batch + ccd::NTP_WAVES - 1) / ccd::NTP_WAVES)), dim3(64 * ccd::NTP_WAVES),
                0, stream, p, att, ctc, subset, weight, max_seq_len, out_paths, out_lengths, scores, att_scores, ctc_scores, source);
+    return ccd_rt_last_error();
+}
+
+// ------------------------------------------------------------------------------- parallel attention recognition head (posattn.h)
+static int ccd_posattn_shape(int N, int tokens, int E, int T) {
+    CCD_CHECK(N >= 0, CCD_EINVAL);
+    CCD_CHECK(tokens == ccd::PA_TOK && E >= 64 && E <= 768 && E % 64 == 0 && T >= 1 && T <= ccd::PA_TQ, CCD_ESHAPE);
+    return CCD_OK;
+}
+static bool ccd_posattn_view(const void* ptr, long ld, int E) { return ld >= E && ld % 8 == 0 && CCD_ALIGNED16(ptr); }
+int ccd_posattn_fwd(const ccd_bf16* P, long ldp, const ccd_bf16* X, long ldx, const ccd_bf16* Q0, const ccd_bf16* We, const float* be,
+                    float* attn, ccd_bf16* G, long ldg, int N, int tokens, int E, int T, void* stream) {
+    const int rc = ccd_posattn_shape(N, tokens, E, T);
+    if (rc != CCD_OK) return rc;
+    CCD_CHECK(ccd_posattn_view(P, ldp, E) && ccd_posattn_view(X, ldx, E) && ccd_posattn_view(G, ldg, E) && CCD_ALIGNED16(Q0) &&
+              CCD_ALIGNED16(We) && CCD_ALIGNED16(attn), CCD_ESHAPE);
+    if (N == 0) return CCD_OK;                                             // nothing to do (pointers may be null)
+    CCD_CHECK(P && X && Q0 && We && be && attn && G, CCD_EINVAL);
+    ccd::PosAttnParams a = ccd::PosAttnParams();
+    a.P = P; a.X = X; a.Q0 = Q0; a.We = We; a.be = be; a.attn = attn; a.G = G;
+    a.ldp = ldp; a.ldx = ldx; a.ldg = ldg; a.N = N; a.E = E; a.T = T;
+    CCD_LAUNCH(ccd::posattn_fwd_kernel, dim3((unsigned)N), dim3(256), (size_t)ccd::PA_FWD_SMEM, stream, a);
+    return ccd_rt_last_error();
+}
+int ccd_posattn_bwd(const ccd_bf16* dG, long lddg, const ccd_bf16* X, long ldx, const ccd_bf16* P, long ldp, const ccd_bf16* Q0,
+                    const ccd_bf16* We, const float* attn, ccd_bf16* dX1, long lddx, ccd_bf16* dP, long lddp, float* dWe_part,
+                    float* dbe_part, int N, int tokens, int E, int T, void* stream) {
+    const int rc = ccd_posattn_shape(N, tokens, E, T);
+    if (rc != CCD_OK) return rc;
+    CCD_CHECK(ccd_posattn_view(dG, lddg, E) && ccd_posattn_view(X, ldx, E) && ccd_posattn_view(P, ldp, E) &&
+              ccd_posattn_view(dX1, lddx, E) && ccd_posattn_view(dP, lddp, E) && CCD_ALIGNED16(Q0) && CCD_ALIGNED16(We) &&
+              CCD_ALIGNED16(attn) && CCD_ALIGNED16(dWe_part), CCD_ESHAPE);
+    if (N == 0) return CCD_OK;
+    CCD_CHECK(dG && X && P && Q0 && We && attn && dX1 && dP && dWe_part && dbe_part, CCD_EINVAL);
+    ccd::PosAttnParams a = ccd::PosAttnParams();
+    a.dG = dG; a.X = X; a.P = P; a.Q0 = Q0; a.We = We; a.attn = const_cast<float*>(attn); a.dX1 = dX1; a.dP = dP;
+    a.dWe_part = dWe_part; a.dbe_part = dbe_part;
+    a.ldg = lddg; a.ldx = ldx; a.ldp = ldp; a.lddx = lddx; a.lddp = lddp; a.N = N; a.E = E; a.T = T;
+    CCD_LAUNCH(ccd::posattn_bwd_kernel, dim3((unsigned)N), dim3(256), (size_t)ccd::PA_BWD_SMEM, stream, a);
+    return ccd_rt_last_error();
+}
+int ccd_posattn_fold(const ccd_bf16* dP, long lddp, const float* dWe_part, const float* dbe_part, float* dQ0, float* dWe, float* dbe,
+                     int N, int E, void* stream) {
+    const int rc = ccd_posattn_shape(N, ccd::PA_TOK, E, 1);
+    if (rc != CCD_OK) return rc;
+    CCD_CHECK(dQ0 && dWe && dbe && (N == 0 || (dP && dWe_part && dbe_part)), CCD_EINVAL);
+    CCD_CHECK((N == 0 || ccd_posattn_view(dP, lddp, E)) && CCD_ALIGNED16(dWe_part), CCD_ESHAPE);
+    if (N == 0) {                                                          // no images: zeros, without a launch
+        int rz = ccd_rt_memset_async(dQ0, 0, sizeof(float) * ccd::PA_TOK * E, stream);
+        if (!rz) rz = ccd_rt_memset_async(dWe, 0, sizeof(float) * ccd::PA_TQ * E, stream);
+        if (!rz) rz = ccd_rt_memset_async(dbe, 0, sizeof(float) * ccd::PA_TQ, stream);
+        return rz;
+    }
+    CCD_LAUNCH(ccd::posattn_fold_kernel, dim3((unsigned)(E + E / 8 + 1)), dim3(256), 0, stream, dP, lddp, dWe_part, dbe_part, dQ0, dWe, dbe,
+               N, E);
     return ccd_rt_last_error();
 }
 

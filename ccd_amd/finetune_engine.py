@@ -307,8 +307,16 @@ class TFLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets, pad_idx):
         B, T, C = logits.shape
-        assert logits.dtype == F32 and logits.stride(2) == 1 and logits.stride(0) == T * logits.stride(1)
-        lg2 = logits.as_strided((B * T, C), (logits.stride(1), 1))
+        assert logits.dtype == F32 and logits.stride(2) == 1
+        rows = T
+        if logits.stride(0) != T * logits.stride(1):
+            # the first T of `rows` rows per sample of a row-padded buffer (ParallelAttnFn: 32 rows): the kernels walk all of them, the
+            # rows behind T against <PAD> targets - they count nothing and get a zero gradient, row T - 1 included
+            rows = logits.stride(0) // max(logits.stride(1), 1)
+            assert rows > T and logits.stride(0) == rows * logits.stride(1) and logits._base is not None and \
+                logits.storage_offset() + (B * rows - 1) * logits.stride(1) + C <= logits._base.numel() + logits._base.storage_offset()
+            targets = torch.nn.functional.pad(targets, (0, rows - T), value=pad_idx)
+        lg2 = logits.as_strided((B * rows, C), (logits.stride(1), 1))
         row_lse, acc = ops.tf_loss_fwd(lg2, C, targets, pad_idx)
         ctx.saved, ctx.pad_idx = (logits, lg2, targets, row_lse, acc), pad_idx
         return acc[0] / acc[1]
@@ -323,7 +331,7 @@ class TFLossFn(torch.autograd.Function):
         if lg2.stride(0) == CLS_PAD and logits._base is not None:      # produced by DecoderFn: hand the bf16 buffer over
             _PARKED_LOGIT_GRADS[logits._base.data_ptr()] = d
             return torch.zeros((), dtype=F32, device=d.device).expand(logits.shape), None, None
-        return d[:, :C].float().view(B, T, C), None, None
+        return d[:, :C].float().view(B, -1, C)[:, :T], None, None
 
 
 @torch.no_grad()

@@ -347,7 +347,11 @@ class DINO_Finetune(ArenaModule):
     [0, 1] - it needs that head and `decoder.beam_width` in 1..16, and excludes a lexicon - makes `forward_beam` rescore every
     candidate with the CTC prefix probability of its characters (kernels/nrtr_joint.h).  `decoder.twopass_beam: N` (1..16, with
     `decoder.twopass_ctc_weight: w` in [0, 1], default 0.5) needs that head too and excludes the three other decoders: evaluation
-    scores rank 0 of `forward_twopass` - the CTC beam proposes N words, the decoder rescores them in one pass (kernels/nrtr_twopass.h)."""
+    scores rank 0 of `forward_twopass` - the CTC beam proposes N words, the decoder rescores them in one pass (kernels/nrtr_twopass.h).
+    `decoder.type: 'ParallelAttnDecoder'` builds the reference's parallel attention head (Dino/modules/attention.py `Attention` + `cls`):
+    backbone -> ParallelAttnDecoder on the backbone tokens -> TFLoss, with an AttnConvertor and no `encoder` Mlp.  It decodes greedily in
+    one pass: `forward_train` returns (loss, attn [N, T, 8, 32]), `forward_test` the probabilities, `forward_attn` both; every other
+    decoder's key and method is refused with a ValueError that names the head."""
 
     aux_ctc_weight = 0.0               # decoder.aux_ctc_weight; > 0: the model owns ctc_decoder and ctc_loss
     joint_ctc_weight = None            # decoder.joint_ctc_weight; a number: forward_beam decodes jointly
@@ -359,6 +363,10 @@ class DINO_Finetune(ArenaModule):
     def __init__(self, config):
         super().__init__()
         self.ctc = getattr(config, "decoder_type", None) == "CTCDecoder"
+        self.par = getattr(config, "decoder_type", None) == "ParallelAttnDecoder"
+        if self.par:
+            self._init_par(config)
+            return
         aux, joint = self._checked_hybrid_keys(config)
         twopass = self._checked_twopass_keys(config, aux, joint)
         if self.ctc:
@@ -455,6 +463,41 @@ class DINO_Finetune(ArenaModule):
             state_dict[keys[0]], state_dict[keys[1]] = self.ctc_decoder.fc.weight.detach(), self.ctc_decoder.fc.bias.detach()
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
 
+    _PAR_REFUSED_KEYS = ("beam_width", "lexicon", "lexicon_beam", "lm", "aux_ctc_weight", "joint_ctc_weight", "twopass_beam")
+
+    def _init_par(self, config):
+        """decoder.type 'ParallelAttnDecoder': the head decodes greedily in one pass and has no other decoder's machinery."""
+        from ..convertor.attn import AttnConvertor
+        from ..decoder.parallel_attn_decoder import ParallelAttnDecoder
+        from ..loss.ce_loss import TFLoss
+        from ..modules import vision_transformer as vits
+        for key in self._PAR_REFUSED_KEYS:
+            if getattr(config, "decoder_" + key, None):
+                raise ValueError(f"decoder.{key} is not for decoder.type 'ParallelAttnDecoder': the parallel attention head decodes greedily "
+                                 "in one pass (no beam, lexicon, language model, auxiliary CTC head, joint or two-pass decoding)")
+        self.label_convertor = AttnConvertor(dict_type='DICT90', max_seq_len=config.decoder_max_seq_len or 25, with_unknown=True)
+        config.arch = config.arch.replace("deit", "vit")
+        if config.arch not in vits.__dict__:
+            raise NotImplementedError(f"Unknow architecture: {config.arch} (HIP kernels cover vit_tiny / vit_small / vit_base)")
+        self.backbone = vits.__dict__[config.arch](patch_size=config.patch_size, drop_path_rate=config.drop_path_rate)
+        config.decoder_num_classes = self.label_convertor.num_classes()
+        self.decoder = ParallelAttnDecoder(in_features=self.backbone.embed_dim, num_classes=config.decoder_num_classes,
+                                           max_seq_len=config.decoder_max_seq_len or 25)
+        self.loss = TFLoss(ignore_index=self.label_convertor.padding_idx)
+
+    def _par_refuses(self, method):
+        if self.par:
+            raise ValueError(f"{method} is not for decoder.type 'ParallelAttnDecoder': the parallel attention head decodes greedily in one "
+                             "pass (forward_test, forward_attn)")
+
+    @torch.no_grad()
+    def forward_attn(self, img):
+        """The parallel attention head: img [N,3,32,128] -> (probabilities fp32 [N, T, C], attention maps fp32 [N, T, 8, 32])."""
+        if not self.par:
+            raise ValueError("forward_attn is the parallel attention head's (decoder.type: 'ParallelAttnDecoder')")
+        logits, attn = self.decoder.forward_train(self.extract_feat(img))
+        return logits.softmax(dim=-1), attn
+
     def _init_ctc(self, config):
         from ..convertor.ctc import CTCConvertor
         from ..decoder.ctc_decoder import CTCDecoder
@@ -480,7 +523,7 @@ class DINO_Finetune(ArenaModule):
     # ------------------------------------------------------------------------------------------- arena
     def _transposed_names(self):
         names = ["backbone." + n for n in self.backbone._transposed_names()]
-        if not self.ctc:
+        if not (self.ctc or self.par):
             names += ["encoder." + n for n in self.encoder._transposed_names()]
         names += ["decoder." + n for n in self.decoder._transposed_names()]
         if self.aux_ctc_weight > 0:
@@ -490,7 +533,7 @@ class DINO_Finetune(ArenaModule):
     def attach_arena(self, arena, prefix):
         super().attach_arena(arena, prefix)
         self.backbone.attach_arena(arena, prefix + "backbone.")
-        if not self.ctc:
+        if not (self.ctc or self.par):
             self.encoder.attach_arena(arena, prefix + "encoder.")
         self.decoder.attach_arena(arena, prefix + "decoder.")
         if self.aux_ctc_weight > 0:
@@ -522,6 +565,9 @@ class DINO_Finetune(ArenaModule):
         targets_dict = {'padded_targets': img_metas}
         if self.ctc:                                       # (no attention maps: the second value is None)
             return self.loss(self.decoder.forward_train(feat), targets_dict), None
+        if self.par:                                       # (attn [N, T, 8, 32])
+            logits, attn = self.decoder.forward_train(feat)
+            return self.loss(logits, targets_dict), attn
         out_enc = self.encoder(feat)
         out_dec, attn = self.decoder(feat, out_enc, targets_dict, train_mode=True)
         if not self.aux_ctc_weight > 0:
@@ -543,13 +589,14 @@ class DINO_Finetune(ArenaModule):
     def forward_ctc(self, img):
         """img [N,3,32,128] -> the auxiliary CTC head's frame probabilities fp32 [N, 32, 92] (class 0 the blank, class c + 1 the NRTR
         class c): what a CTCConvertor built beside the model decodes with any of its decoders."""
+        self._par_refuses("forward_ctc")
         if not self.aux_ctc_weight > 0:
             raise ValueError("forward_ctc: the model has no auxiliary CTC head (decoder.aux_ctc_weight)")
         return self.ctc_decoder.forward_test(self.extract_feat(img))
 
     def forward_test(self, img):
         feat = self.extract_feat(img)
-        if self.ctc:
+        if self.ctc or self.par:
             return self.decoder.forward_test(feat)
         return self.decoder(feat, self.encoder(feat), None, train_mode=False)
 
@@ -560,6 +607,7 @@ class DINO_Finetune(ArenaModule):
         joint_ctc_weight (default: `decoder.joint_ctc_weight`) = w in [0, 1] decodes jointly with the auxiliary CTC head: the beam runs
         over S = (1 - w) log p_att + w log p_ctc, the CTC part being the prefix probability of a live hypothesis and the word's
         probability of a finished one; `scores` is S and `last_att_scores` keeps the attention parts, fp32 [N, W]."""
+        self._par_refuses("forward_beam")
         if self.ctc:
             raise NotImplementedError("forward_beam is the NRTR head's; the CTC head's beam is CTCConvertor.tensor2nbest on forward_test")
         w = self.joint_ctc_weight if joint_ctc_weight is None else self._checked_joint_weight(joint_ctc_weight)
@@ -587,6 +635,7 @@ class DINO_Finetune(ArenaModule):
         proposals=(paths int32 [N, W, Tp], lengths int32 [N, W]): any decoder's hypotheses on forward_ctc(img), in CTC classes -
         ops.ctc_beam_search_lm, the paths of ops.ctc_beam_search_trie, a CTCConvertor's n-best; their own scores are not used.
         Nothing is read back."""
+        self._par_refuses("forward_twopass")
         if self.ctc:
             raise NotImplementedError("forward_twopass is the NRTR head's (its decoder rescores CTC proposals); the CTC head's beam is "
                                       "CTCConvertor.tensor2nbest on forward_test")
@@ -618,6 +667,7 @@ class DINO_Finetune(ArenaModule):
         label_convertor.lexicon_words, log_probs the exact log p(word <EOS> | image) - a hypothesis has one path, so the beam's
         score is the word's probability, comparable across words.  An empty slot is (-1, -inf, all -1, -1).  Device tensors, nothing
         is read back; AttnConvertor.paths2lexicon is the host-side view."""
+        self._par_refuses("forward_lexicon")
         if self.ctc:
             raise NotImplementedError("forward_lexicon is the NRTR head's; the CTC head's lexicon decoding is CTCConvertor.tensor2lexicon "
                                       "on forward_test")
@@ -636,6 +686,7 @@ class DINO_Finetune(ArenaModule):
         spans, per-character log-probabilities, the alignment's score - of `words` (a list of N transcriptions) or, words=None, of the
         `nbest` word(s) the convertor's configuration decodes (greedy, beam, LM-fused beam, lexicon).  A dict of device tensors;
         CTCConvertor.tensor2chars is the host-side view."""
+        self._par_refuses("forward_chars")
         if not self.ctc:
             raise NotImplementedError("forward_chars is the CTC head's: the NRTR decoder has no frame axis to align a word against "
                                       "(use decoder.type: 'CTCDecoder')")
@@ -646,6 +697,7 @@ class DINO_Finetune(ArenaModule):
 
     def _score_rows(self, img, words):
         from ..ops import csr_rows
+        self._par_refuses("forward_score / forward_words")
         if self.ctc:
             raise NotImplementedError(self._SCORE_IS_NRTR)
         if len(words) != img.shape[0]:
@@ -676,6 +728,6 @@ class DINO_Finetune(ArenaModule):
 
     def forward_test_speed(self, img):
         feat = self.extract_feat(img)
-        if self.ctc:                                       # (one pass either way: nothing to stop early)
+        if self.ctc or self.par:                           # (one pass either way: nothing to stop early)
             return self.decoder.forward_test(feat)
         return self.decoder(feat, self.encoder(feat), None, train_mode=False, test_speed=True)

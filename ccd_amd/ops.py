@@ -2350,3 +2350,70 @@ def greedy_step(logits, C, probs, step, seq):
     assert seq.dtype == I64 and seq.is_contiguous() and probs.is_contiguous()
     B = seq.shape[0]
     _call("ccd_greedy_step", logits, logits.stride(0), int(C), B, probs, probs.shape[1], int(step), seq, seq.shape[1])
+
+
+# ------------------------------------------------------------------------------------------ parallel attention head (kernels/posattn.h)
+POSATTN_TOKENS, POSATTN_MAX_T = 256, 32                   # posattn.h: PA_TOK, PA_TQ
+
+
+def _posattn_views(fn, E, **views):
+    for name, t in views.items():
+        if t.dtype != BF16:
+            raise TypeError(f"{fn}: {name} must be bfloat16, got {t.dtype}")
+        if t.dim() != 2 or t.shape[1] != E or (t.shape[0] > 0 and t.stride(1) != 1):
+            raise ValueError(f"{fn}: {name} must be a 2-D view of {E} dense columns, got {list(t.shape)}, strides {t.stride()}")
+
+
+def _posattn_ld(t):
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def posattn_fwd(P, X, Q0, We, be, T):
+    """The parallel attention head's scores, softmax and glimpses in one launch (kernels/posattn.h; tests/parallel_attn_np.py is the
+    specification): P = X Wv^T + bv and X bf16 [N * 256, E] 2-D views (any row stride that is a multiple of 8, 16-byte aligned rows), Q0
+    bf16 [256, E], We bf16 [32, E] with rows T.. zero, be fp32 [T] -> (attn fp32 [N, T, 256], G bf16 [N * 32, E]).  attn[n, t] = softmax
+    over the 256 tokens of be[t] + tanh(P_n + Q0) We[t]; G[n * 32 + t] = attn[n, t] X_n, rows T..31 of every image zero.  tanh(P + Q0) is
+    never stored.  E a multiple of 64 up to 768, 1 <= T <= 32; two runs give the same bits."""
+    E, T = int(Q0.shape[-1]), int(T)
+    _posattn_views("posattn_fwd", E, P=P, X=X, Q0=Q0, We=We)
+    if P.shape[0] != X.shape[0]:
+        raise ValueError(f"posattn_fwd: P has {P.shape[0]} rows, X {X.shape[0]}")
+    rows = P.shape[0]
+    N = rows // POSATTN_TOKENS
+    tokens = POSATTN_TOKENS if rows == N * POSATTN_TOKENS else rows      # (not whole images: the library refuses the shape)
+    if tuple(Q0.shape) != (POSATTN_TOKENS, E) or tuple(We.shape) != (POSATTN_MAX_T, E) or not Q0.is_contiguous() or not We.is_contiguous():
+        raise ValueError(f"posattn_fwd: Q0 must be a dense [256, {E}] and We a dense [32, {E}], got {list(Q0.shape)} and {list(We.shape)}")
+    if be.dtype != F32 or be.numel() < T:
+        raise ValueError(f"posattn_fwd: be must hold {T} fp32 values, got {be.dtype} {list(be.shape)}")
+    attn = torch.empty((N, max(T, 0), POSATTN_TOKENS), dtype=F32, device=P.device)
+    G = torch.empty((N * POSATTN_MAX_T, E), dtype=BF16, device=P.device)
+    _call("ccd_posattn_fwd", P, _posattn_ld(P), X, _posattn_ld(X), Q0, We, be, attn, G, E, N, tokens, E, T)
+    return attn, G
+
+
+def posattn_bwd(dG, X, P, Q0, We, attn, out=None):
+    """Backward of posattn_fwd given dG bf16 [N * 32, E] (rows T.. of an image are not read): -> (dX1 bf16 [N * 256, E] = attn^T dG, dP bf16
+    [N * 256, E] = dM (1 - tanh(P + Q0)^2), dQ0 fp32 [256, E] = sum_n dP_n, dWe fp32 [32, E], dbe fp32 [32]).  The gradient of X through
+    P (dP Wv), dWv and dbv are the caller's GEMMs on dP.  `out` = (dX1, dP) 2-D views to write into (row strides multiples of 8).  The
+    sums over the images are folded by a finishing launch in a fixed order (ccd_posattn_fold): no atomics, two runs give the same bits."""
+    E = int(Q0.shape[-1])
+    N, T = int(attn.shape[0]), int(attn.shape[1])
+    dX1, dP = out if out is not None else (torch.empty((N * POSATTN_TOKENS, E), dtype=BF16, device=X.device) for _ in range(2))
+    _posattn_views("posattn_bwd", E, dG=dG, X=X, P=P, Q0=Q0, We=We, dX1=dX1, dP=dP)
+    if attn.dtype != F32 or attn.dim() != 3 or attn.shape[2] != POSATTN_TOKENS or not attn.is_contiguous():
+        raise ValueError(f"posattn_bwd: attn must be a dense fp32 [N, T, 256], got {attn.dtype} {list(attn.shape)}")
+    for name, t, rows in (("dG", dG, N * POSATTN_MAX_T), ("X", X, N * POSATTN_TOKENS), ("P", P, N * POSATTN_TOKENS),
+                          ("dX1", dX1, N * POSATTN_TOKENS), ("dP", dP, N * POSATTN_TOKENS), ("Q0", Q0, POSATTN_TOKENS), ("We", We, POSATTN_MAX_T)):
+        if t.shape[0] != rows:
+            raise ValueError(f"posattn_bwd: {name} must have {rows} rows for {N} images, got {t.shape[0]}")
+    if not Q0.is_contiguous() or not We.is_contiguous():
+        raise ValueError("posattn_bwd: Q0 and We must be dense")
+    dWe_part = torch.empty((N, POSATTN_MAX_T, E), dtype=F32, device=X.device)
+    dbe_part = torch.empty((N, POSATTN_MAX_T), dtype=F32, device=X.device)
+    dQ0 = torch.empty((POSATTN_TOKENS, E), dtype=F32, device=X.device)
+    dWe = torch.empty((POSATTN_MAX_T, E), dtype=F32, device=X.device)
+    dbe = torch.empty(POSATTN_MAX_T, dtype=F32, device=X.device)
+    _call("ccd_posattn_bwd", dG, _posattn_ld(dG), X, _posattn_ld(X), P, _posattn_ld(P), Q0, We, attn, dX1, _posattn_ld(dX1), dP,
+          _posattn_ld(dP), dWe_part, dbe_part, N, POSATTN_TOKENS, E, T)
+    _call("ccd_posattn_fold", dP, _posattn_ld(dP), dWe_part, dbe_part, dQ0, dWe, dbe, N, E)
+    return dX1, dP, dQ0, dWe, dbe

@@ -1083,6 +1083,24 @@ int ccd_tf_loss_bwd(const float* logits, long ldl, int C, const int64_t* targets
  * seq[b,step+1] = argmax (first maximum). */
 int ccd_greedy_step(const float* logits, long ldl, int C, int B, float* probs, int steps, int step, int64_t* seq,
                     int seq_len, void* stream);
+/* Parallel (position) attention recognition head (Dino/modules/attention.py:5-30, kernels/posattn.h), per image n of 256 tokens:
+ *   M = tanh(P + Q0)   A[s, t] = be[t] + sum_e M[s, e] We[t, e]   attn[n, t, :] = softmax over the tokens s   G[t, :] = sum_s attn[t, s] X[s, :]
+ * P = X Wv^T + bv and X are bf16 2-D views [N * 256, E] with row strides ldp / ldx (multiples of 8, >= E, 16-byte aligned rows),
+ * Q0 bf16 [256, E] and We bf16 [32, E] (rows T.. zero) dense, be fp32 [T].  tokens must be 256, E a multiple of 64 up to 768,
+ * 1 <= T <= 32: anything else is CCD_ESHAPE before any launch; N = 0 returns without a launch.
+ * ccd_posattn_fwd writes attn fp32 [N, T, 256] and G bf16 [N * 32, E] (row stride ldg; rows T..31 of every image zero).
+ * ccd_posattn_bwd: given dG (bf16 [N * 32, E], row stride lddg; rows T.. are not read) writes dX1[s, :] = sum_t attn[t, s] dG[t, :] and
+ *   dP = dM (1 - M^2), dM[s, :] = sum_t dA[s, t] We[t, :], dA[s, t] = attn[t, s] (da[t, s] - sum_s' attn[t, s'] da[t, s']), da = dG X^T
+ *   (bf16 [N * 256, E] views, row strides lddx / lddp), and this image's fp32 partials dWe_part [N, 32, E] = dA^T M, dbe_part [N, 32].
+ * ccd_posattn_fold sums over the images in a fixed order: dQ0 fp32 [256, E] = sum_n dP_n, dWe fp32 [32, E], dbe fp32 [32] (all
+ *   overwritten; zeros for N = 0).  No atomics in any of the three: two runs give the same bits. */
+int ccd_posattn_fwd(const ccd_bf16* P, long ldp, const ccd_bf16* X, long ldx, const ccd_bf16* Q0, const ccd_bf16* We, const float* be,
+                    float* attn, ccd_bf16* G, long ldg, int N, int tokens, int E, int T, void* stream);
+int ccd_posattn_bwd(const ccd_bf16* dG, long lddg, const ccd_bf16* X, long ldx, const ccd_bf16* P, long ldp, const ccd_bf16* Q0,
+                    const ccd_bf16* We, const float* attn, ccd_bf16* dX1, long lddx, ccd_bf16* dP, long lddp, float* dWe_part,
+                    float* dbe_part, int N, int tokens, int E, int T, void* stream);
+int ccd_posattn_fold(const ccd_bf16* dP, long lddp, const float* dWe_part, const float* dbe_part, float* dQ0, float* dWe, float* dbe,
+                     int N, int E, void* stream);
 
 #ifdef __cplusplus
 }

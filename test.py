@@ -177,6 +177,9 @@ def main():
     if a.char_scores is not None and model.module.ctc:
         raise NotImplementedError("--char_scores is for the NRTR head only: the CTC head writes character spans and confidences with "
                                   "--alignments")
+    if (a.char_scores is not None or a.alignments is not None) and model.module.par:
+        raise NotImplementedError("--char_scores (the NRTR head) and --alignments (the CTC head) are not for the parallel attention head: "
+                                  "its attention maps are DINO_Finetune.forward_attn's")
     if a.alignments is not None:
         if not model.module.ctc:
             raise NotImplementedError("--alignments is for the CTC head only: the NRTR decoder has no frame axis to align a word against")
