@@ -46,6 +46,20 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// LayerNorm statistics of the fused epilogues (mlp_fused.h, rowgemm.h, gemm_row384.h), whose finished row is in registers: a first
+// sweep gives m0 = sum(v) / E (a long per-lane fp32 chain: good to a few ulp of |mean|), a second one d1 = sum(v - m0) and
+// d2 = sum((v - m0)^2).  mean = m0 + d1 / E takes the first sweep's rounding out again, and d2 / E - (d1 / E)^2 is the variance
+// about THAT mean, with nothing to cancel: rstd is good to a few 2^-24 at any |mean| / std, as layernorm.h's is.  (One sweep,
+// s2 / E - mean^2, loses log2(1 + mean^2 / var) bits: rstd off by 1e-3 at |mean| / std = 100 and by order 1 at 1000.)
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void ln_stats_finish(float m0, float d1, float d2, float inv_e, float eps, float& mean, float& rstd) {
+    const float dm = d1 * inv_e;
+    mean = m0 + dm;
+    float var = d2 * inv_e - dm * dm;
+    var = var > 0.f ? var : 0.f;
+    rstd = 1.0f / sqrtf(var + eps);
+}
+
 // erf-GELU as nn.GELU() computes it, and its derivative.  erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, far
 // below the bf16 resolution of every consumer): one v_rcp + one v_exp + 7 FMA-class ops, and the Gaussian term it needs,
 // exp(-x^2/2), is the same one the derivative's density uses.  (libm's erff + expf cost ~50 instructions per element

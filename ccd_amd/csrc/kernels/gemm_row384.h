@@ -340,7 +340,7 @@ __global__ __launch_bounds__(GR_THREADS, 1) void gemm_row384_kernel(GemmParams p
                             const bool row_ok = gm < p.M;
                             const float sc = sc_pre[step];
                             f32x4v o[3];
-                            float s1 = 0.f, sq = 0.f;
+                            float s1 = 0.f;
 #pragma unroll
                             for (int c3 = 0; c3 < 3; ++c3) {
                                 const int chunk = L + 32 * c3, gnc = 4 * chunk;
@@ -352,15 +352,24 @@ __global__ __launch_bounds__(GR_THREADS, 1) void gemm_row384_kernel(GemmParams p
                                     o[c3] = r + (v + b) * sc;
                                     *reinterpret_cast<f32x4v*>(reinterpret_cast<float*>(p.C) + (long)gm * p.ldc + gnc) = o[c3];
                                     s1 += (o[c3].x + o[c3].y) + (o[c3].z + o[c3].w);
-                                    sq += (o[c3].x * o[c3].x + o[c3].y * o[c3].y) + (o[c3].z * o[c3].z + o[c3].w * o[c3].w);
                                 }
                             }
 #pragma unroll
-                            for (int msk = 16; msk >= 1; msk >>= 1) { s1 += shfl_xor(s1, msk); sq += shfl_xor(sq, msk); }
-                            const float mean = s1 * inv_n;
-                            float var = sq * inv_n - mean * mean;
-                            var = var > 0.f ? var : 0.f;
-                            const float rstd = 1.0f / sqrtf(var + p.ln_eps);
+                            for (int msk = 16; msk >= 1; msk >>= 1) s1 += shfl_xor(s1, msk);
+                            // the variance about the mean, in a second sweep over the row in registers (ln_stats_finish, common.h)
+                            const float m0 = s1 * inv_n;
+                            float d1 = 0.f, sq = 0.f;
+#pragma unroll
+                            for (int c3 = 0; c3 < 3; ++c3)
+                                if (row_ok && 4 * (L + 32 * c3) < p.N) {
+                                    const f32x4v d = o[c3] - m0;
+                                    d1 += (d.x + d.y) + (d.z + d.w);
+                                    sq += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
+                                }
+#pragma unroll
+                            for (int msk = 16; msk >= 1; msk >>= 1) { d1 += shfl_xor(d1, msk); sq += shfl_xor(sq, msk); }
+                            float mean, rstd;
+                            ln_stats_finish(m0, d1, sq, inv_n, p.ln_eps, mean, rstd);
 #pragma unroll
                             for (int c3 = 0; c3 < 3; ++c3) {
                                 const int gnc = 4 * (L + 32 * c3);

@@ -362,21 +362,30 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void mlp_fused_kernel(MlpParams p) 
             for (int it = 0; it < 16; ++it) {
                 const unsigned rr = (unsigned)(r0 + 2 * it + hf);
                 f32x4v o[C3];
-                float s1 = 0.f, s2 = 0.f;
+                float s1 = 0.f;
 #pragma unroll
                 for (int c3 = 0; c3 < C3; ++c3) {
                     const int chunk = lq + 32 * c3;
                     o[c3] = f32x4v{0.f, 0.f, 0.f, 0.f};
                     if (chunk < E / 4) o[c3] = __builtin_bit_cast(f32x4v, buf_load16(rs_x, (unsigned)(chunk * 16), rr * (unsigned)(p.ldr * 4)));
                     s1 += (o[c3].x + o[c3].y) + (o[c3].z + o[c3].w);
-                    s2 += (o[c3].x * o[c3].x + o[c3].y * o[c3].y) + (o[c3].z * o[c3].z + o[c3].w * o[c3].w);
                 }
 #pragma unroll
-                for (int msk = 16; msk >= 1; msk >>= 1) { s1 += shfl_xor(s1, msk); s2 += shfl_xor(s2, msk); }
-                const float mean = s1 * inv_e;
-                float var = s2 * inv_e - mean * mean;
-                var = var > 0.f ? var : 0.f;
-                const float rstd = 1.0f / sqrtf(var + p.ln_eps);
+                for (int msk = 16; msk >= 1; msk >>= 1) s1 += shfl_xor(s1, msk);
+                // the variance about the mean, in a second sweep over the row in registers (ln_stats_finish, common.h)
+                const float m0 = s1 * inv_e;
+                float d1 = 0.f, d2 = 0.f;
+#pragma unroll
+                for (int c3 = 0; c3 < C3; ++c3)
+                    if (lq + 32 * c3 < E / 4) {
+                        const f32x4v d = o[c3] - m0;
+                        d1 += (d.x + d.y) + (d.z + d.w);
+                        d2 += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
+                    }
+#pragma unroll
+                for (int msk = 16; msk >= 1; msk >>= 1) { d1 += shfl_xor(d1, msk); d2 += shfl_xor(d2, msk); }
+                float mean, rstd;
+                ln_stats_finish(m0, d1, d2, inv_e, p.ln_eps, mean, rstd);
 #pragma unroll
                 for (int c3 = 0; c3 < C3; ++c3) {
                     const int chunk = lq + 32 * c3;
@@ -434,7 +443,7 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void mlp_fused_kernel(MlpParams p) 
         float mean = 0.f, rstd = 0.f;
         auto pass_a = [&](auto MODE, const buf_rsrc& rs_src, long ld_src, const float* vbias, float sc) __attribute__((always_inline)) {
             constexpr int mode = decltype(MODE)::value;      // 0: v = acc * sc;  1: v = x + (acc + bias) * sc;  2: v = x (read past the L1)
-            float s1 = 0.f, s2 = 0.f;
+            float s1 = 0.f;
             if constexpr (mode != 0) {
                 const unsigned so = (unsigned)r0 * (unsigned)(ld_src * 4), lo_x = LaneOff(t).frag(ld_src, 4, 4);
                 u32x4 xb[3][4];
@@ -460,7 +469,6 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void mlp_fused_kernel(MlpParams p) 
                             const float v = mode == 2 ? xx[e] : xx[e] + (acc[nt][4 * g + e] + bb[e]) * sc;
                             acc[nt][4 * g + e] = v;
                             s1 += v;
-                            s2 = fmaf(v, v, s2);
                         }
                     }
                 }
@@ -472,15 +480,30 @@ __global__ __launch_bounds__(MLP_THREADS, 1) void mlp_fused_kernel(MlpParams p) 
                         const float v = acc[nt][r] * sc;
                         acc[nt][r] = v;
                         s1 += v;
-                        s2 = fmaf(v, v, s2);
                     }
             }
             s1 += shfl_xor(s1, 32);
-            s2 += shfl_xor(s2, 32);
-            mean = s1 * inv_e;
-            float var = s2 * inv_e - mean * mean;
-            var = var > 0.f ? var : 0.f;
-            rstd = 1.0f / sqrtf(var + p.ln_eps);
+            // the variance about the mean, in a second sweep over the finished row - it is in the accumulators (ln_stats_finish,
+            // common.h)
+            const float m0 = s1 * inv_e;
+            // Two registers at a time (v_pk_add_f32 / v_pk_fma_f32: even and odd registers keep sums of their own), and E = 512
+            // walks the tiles backwards: forwards that instantiation - all 512 registers in use - spills more of them.
+            const f32x2v mm = {m0, m0};
+            f32x2v dd1 = {0.f, 0.f}, dd2 = {0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                const int nt = E == 512 ? NT - 1 - i : i;
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    const f32x2v d = f32x2v{acc[nt][r], acc[nt][r + 1]} - mm;
+                    dd1 += d;
+                    dd2 = __builtin_elementwise_fma(d, d, dd2);
+                }
+            }
+            float d1 = dd1.x + dd1.y, d2 = dd2.x + dd2.y;
+            d1 += shfl_xor(d1, 32);
+            d2 += shfl_xor(d2, 32);
+            ln_stats_finish(m0, d1, d2, inv_e, p.ln_eps, mean, rstd);
         };
         // Pass B, per pair of 32-column tiles: the rows (fp32, one tile at a time) and their LayerNorm (bf16, both tiles) leave through
         // the scratch image as 128-byte row segments (STORE), and / or the LayerNorm becomes the operand registers yf (TO_YF: the two

@@ -385,7 +385,7 @@ __global__ __launch_bounds__(RG_THREADS, 1) void rowgemm_kernel(RowGemmParams p)
             // (mlp_fused.h's epilogue)  Pass A: out = x + (acc + bias) * sc back into the accumulators, LayerNorm statistics
             float sc = 1.0f;
             if (p.rowscale) sc = p.rowscale[grow / p.rows_per_sample];
-            float s1 = 0.f, s2 = 0.f;
+            float s1 = 0.f;
             // (the vector tables are addressed from a per-tile opaque lane id: from the loop-invariant one the optimiser hoists
             // one address register per (tile, group) out of the persistent loop - 80 spilled registers, and every reload of a
             // spilled register is a scratch load behind `s_waitcnt vmcnt(0)`: a drain of the stores this epilogue streams)
@@ -416,7 +416,6 @@ __global__ __launch_bounds__(RG_THREADS, 1) void rowgemm_kernel(RowGemmParams p)
                             const float v = xx[e] + (acc[nt][4 * g + e] + bb[e]) * sc;
                             acc[nt][4 * g + e] = v;
                             s1 += v;
-                            s2 = fmaf(v, v, s2);
                         }
                     }
                     CCD_SCHED_FENCE();
@@ -424,11 +423,21 @@ __global__ __launch_bounds__(RG_THREADS, 1) void rowgemm_kernel(RowGemmParams p)
                 }
             }
             s1 += shfl_xor(s1, 32);
-            s2 += shfl_xor(s2, 32);
-            const float mean = s1 * inv_e;
-            float var = s2 * inv_e - mean * mean;
-            var = var > 0.f ? var : 0.f;
-            const float rstd = 1.0f / sqrtf(var + p.ln_eps);
+            // the variance about the mean, in a second sweep over the finished row in the accumulators (mlp_fused.h: pass_a)
+            const float m0 = s1 * inv_e;
+            float d1 = 0.f, d2 = 0.f;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float d = acc[nt][r] - m0;
+                    d1 += d;
+                    d2 = fmaf(d, d, d2);
+                }
+            d1 += shfl_xor(d1, 32);
+            d2 += shfl_xor(d2, 32);
+            float mean, rstd;
+            ln_stats_finish(m0, d1, d2, inv_e, p.ln_eps, mean, rstd);
             if (hf == 0 && row < p.M) { p.ln_mean[row] = mean; p.ln_rstd[row] = rstd; }
             const unsigned lo_o = lo.rows8(p.ldc, 4), lo_n = lo.rows8(p.ld_y, 2);
             // Pass B: out (fp32, one 32-column tile at a time) and ln_y (bf16, two tiles) through the scratch image
